@@ -18,7 +18,14 @@ second, shorter run of the bf16 path (configs[1]'s dtype) is reported under ``bf
 error, and one of the fp8 path (configs[4]'s precision: e4m3 MFMA operands) under ``fp8`` with its
 error and cosine similarity; neither is the headline.
 
-Launch: ``python bench.py`` (N=1) or
+A plain run (``python bench.py --gpus 1 --steps K --warmup W``) does only what the headline figure
+needs: set up, warm up, time the K steps, write the last step's outputs when ``--dump-outputs DIR``
+is given, print the result line.  Everything else described above and below (the event-profiled
+roofline pass, the oracle parity of clip 0, the caller lines, the bf16 / fp8 / fp32 secondary lines,
+the configs[4] lines, the CPU baseline) runs only with ``--full``, where the ``--no-*`` switches
+still take single legs out.
+
+Launch: ``python bench.py [--full]`` (N=1) or
 ``python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N``.
 Rank 0 prints ONE JSON line.
 """
@@ -183,6 +190,13 @@ def parse(argv=None):
     p.add_argument("--dtype", default="bf16x3", choices=["bf16x3", "fp32", "bf16", "fp8"])
     p.add_argument("--chunk", type=int, default=CNN_CHUNK,
                    help="frames per CNN pass (default: the engine's shipped m2s.config.CNN_CHUNK = one pass over the 64x30 step)")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline: the event-profiled roofline pass, the oracle parity, the caller lines, the "
+                        "bf16 / fp8 / fp32 secondary lines, the configs[4] lines and the CPU baseline (each leg can be "
+                        "taken out with its --no-* switch); without it only the headline is measured")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (mel_norm, mel_db, mel_log, wav of "
+                        "this rank) as DIR/<name>.npy in float32, at most 64 MB in all (a seeded sample of a larger array)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-seconds", type=float, default=10.0, help="C3 sample of the CPU baseline (seconds)")
     p.add_argument("--cpu-long-frames", type=int, default=1000, help="C5 clip length of the CPU baseline (0: skip)")
@@ -276,6 +290,25 @@ class RaggedPlan:
 def dp_mod():
     from m2s import dp
     return dp
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, cap=DUMP_CAP_BYTES, seed=4321):
+    """``--dump-outputs``: every array of `arrays` (name -> tensor) as ``dirname/<name>.npy`` in float32 (float64 stays
+    float64), `cap` bytes at the most in all.  An array over its equal share of `cap` is written as a 1-D sample of
+    its flattened elements at seeded, sorted positions: the same positions in every run of the same shapes, so two
+    builds compare element for element."""
+    os.makedirs(dirname, exist_ok=True)
+    share = cap // max(len(arrays), 1)
+    for i, (name, t) in enumerate(sorted(arrays.items())):
+        t = t.detach()
+        a = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(seed + i).integers(0, a.size, size=share // a.itemsize))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
 
 
 def make_frames(clips, frames, hw, rank, device):
@@ -650,6 +683,7 @@ def main():
 
         def step(p=None):
             plan.step((p or pipe).forward, fr_by_len, wav_buf, mel_buf, multi(world))
+            out.update(wav=wav_buf, mel_db=mel_buf)  # this rank's padded (clips, max length) results
     else:
         frames = make_frames(B, T, HW, rank, device)
         frames_per_step = world * B * T
@@ -668,6 +702,8 @@ def main():
         step()
     elapsed = timed_loop(step, args.steps, world, sync, device)
     pipe.ac.check()  # a BiLSTM hand-off timeout in the timed steps raises here (m2s_acoustic_status)
+    if rank == 0 and args.dump_outputs:  # the last timed step's results, before any later pass runs
+        dump_outputs(args.dump_outputs, out)
     frames_total = frames_per_step * args.steps
     fps = frames_total / elapsed
     audio_s = frames_total * HOP / SR
@@ -695,8 +731,9 @@ def main():
                    "parallelism": f"dp{world}", "chunk": args.chunk},
     }
 
+    full = args.full  # everything below the headline runs only with --full
     # roofline: a second pass identical to the timed region with HIP events around every launch
-    if not args.no_profile:
+    if full and not args.no_profile:
         _native.prof_enable(True)
         timed_loop(step, args.steps, world, sync, device)
         _native.prof_enable(False)
@@ -709,14 +746,14 @@ def main():
                       file=sys.stderr)
 
     ref0 = None
-    if rank == 0 and not args.no_parity:  # clip 0 of this rank's workload through the fp32 oracle
+    if full and rank == 0 and not args.no_parity:  # clip 0 of this rank's workload through the fp32 oracle
         if args.ragged:  # clip 0 of the first length group
             out.update(pipe.forward(frames))
         ref0 = oracle_clip(ac_sd, gen_sd, mean, std, frames[:1].cpu().numpy())
         result["parity"] = dict(parity_vs(ref0, out), clip=0, tolerance=FP32_TOL, reference="fp32 CPU oracle")
-    if world == 1 and not args.ragged and not args.no_caller:  # the caller's view: host I/O, one-clip latency, configs[1]
+    if full and world == 1 and not args.ragged and not args.no_caller:  # the caller's view: host I/O, one-clip latency, configs[1]
         result["caller"] = caller_lines(args, pipe, build, device, sync, world, (ac_sd, gen_sd, mean, std))
-    if world == 1 and not args.no_compare:  # secondary lines: the narrower dtypes on the same workload
+    if full and world == 1 and not args.no_compare:  # secondary lines: the narrower dtypes on the same workload
         del pipe
         for dt in ("bf16", "fp8", "fp32"):
             if dt == args.dtype:
@@ -735,9 +772,9 @@ def main():
                 par["within_tol"] = within if dt == "fp32" else par["within_cos_0.99"]
                 result[dt]["parity"] = par
             del p2
-    if world == 1 and not args.no_long and not (args.clips == 8 and args.frames == 1000):
+    if full and world == 1 and not args.no_long and not (args.clips == 8 and args.frames == 1000):
         result["configs4"] = long_clip_lines(args, build, device, sync, world, (ac_sd, gen_sd, mean, std))
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(args, ac_sd, gen_sd, mean, std)
     if rank == 0:
         print(json.dumps(result), flush=True)

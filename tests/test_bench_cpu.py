@@ -22,6 +22,31 @@ def test_parse_defaults_are_the_headline_workload():
     assert a.steps * 0.04 >= 3.0  # a timed region of about three seconds or more at ~42 ms per step
 
 
+def test_plain_run_is_the_headline_only_and_full_is_opt_in():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert bench.parse(["--full", "--dump-outputs", "d"]).full and bench.parse(["--dump-outputs", "d"]).dump_outputs == "d"
+
+
+def test_dump_outputs_writes_float_arrays_and_a_fixed_sample_within_the_cap(tmp_path):
+    import numpy as np
+    g = torch.Generator().manual_seed(3)
+    arrays = {"wav": torch.randn(4, 1000, generator=g), "mel_db": torch.randn(4, 5, 64, generator=g).to(torch.bfloat16),
+              "d": torch.randn(3, generator=g, dtype=torch.float64)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["wav"].dtype == got["mel_db"].dtype == np.float32 and got["d"].dtype == np.float64
+    assert got["wav"].shape == (4, 1000) and np.array_equal(got["wav"], arrays["wav"].numpy())
+    assert np.array_equal(got["mel_db"], arrays["mel_db"].float().numpy())
+    # over the cap: a 1-D sample at the same seeded positions in every run, cap bytes at the most in all
+    bench.dump_outputs(str(tmp_path / "b"), arrays, cap=3000)
+    bench.dump_outputs(str(tmp_path / "c"), arrays, cap=3000)
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in arrays}
+    assert sum(v.nbytes for v in b.values()) <= 3000 and b["wav"].ndim == 1 and b["d"].shape == (3,)
+    assert all(np.array_equal(b[k], np.load(tmp_path / "c" / f"{k}.npy")) for k in arrays)
+    assert np.isin(b["wav"], got["wav"]).all()
+
+
 def _launches(stats):
     """prof_launches()-style records (one per launch, in order, with a stage) from per-kernel totals."""
     out = []

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_co
   || { tail -40 "$OUT/pytest.log"; exit 1; }
 grep -E "passed|failed" "$OUT/pytest.log" | tail -3 | cut -c1-200
 for dt in "${@:-fp8 bf16}"; do
-  timeout -k 10 300 python -u bench.py --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
     --no-long > "$OUT/bench_$dt.json" 2> "$OUT/bench_$dt.err" || { tail -20 "$OUT/bench_$dt.err"; exit 1; }
   echo "$dt $(python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['ms_per_step'], 'ms', d['value'])" "$OUT/bench_$dt.json")"
 done

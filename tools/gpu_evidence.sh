@@ -23,7 +23,7 @@ pmc() {  # pmc <dir> <counters...>
      python3 "$ROOT/tools/profile_step.py" > "$ROOT/$OUT/$d.log" 2>&1)
 }
 (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/trace" -o run -- \
-   python3 "$ROOT/bench.py" --steps 5 --warmup 2 --no-cpu-baseline --no-compare --no-parity \
+   python3 "$ROOT/bench.py" --full --steps 5 --warmup 2 --no-cpu-baseline --no-compare --no-parity \
    > "$ROOT/$OUT/bench_under_rocprof.json" 2> "$ROOT/$OUT/trace.err") \
 && pmc fetch FETCH_SIZE \
 && pmc write WRITE_SIZE \

@@ -14,7 +14,7 @@ timeout -k 10 500 python -u -m pytest tests/test_gpu_fp8.py tests/test_gpu_confi
   || { tail -40 "$OUT/pytest.log"; exit 1; }
 grep -E "passed|failed|cos" "$OUT/pytest.log" | tail -30 | cut -c1-200
 for dt in fp8 bf16; do
-  timeout -k 10 300 python -u bench.py --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
     --no-long > "$OUT/bench_$dt.json" 2> "$OUT/bench_$dt.err" || { tail -20 "$OUT/bench_$dt.err"; exit 1; }
   cut -c1-300 "$OUT/bench_$dt.json"
 done

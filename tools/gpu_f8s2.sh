@@ -16,7 +16,7 @@ AB_DTYPE=fp8 AB_KERN=ir_pwdw AB_ROUNDS=2 timeout -k 10 300 python -u tools/ab_ke
 cut -c1-400 "$OUT/ab.txt"
 bl() {  # bl <name> <dtype> [env...]
   local n=$1 dt=$2; shift 2
-  env "$@" timeout -k 10 300 python -u bench.py --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare \
+  env "$@" timeout -k 10 300 python -u bench.py --full --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare \
     --no-cpu-baseline --no-long > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail -20 "$OUT/bench_$n.err"; return 1; }
   echo "$n $(python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['ms_per_step'], 'ms', d.get('parity'))" "$OUT/bench_$n.json" | cut -c1-300)"
 }

@@ -14,7 +14,7 @@ grep -E "cos|PASS|FAIL" "$OUT/pytest.log" | cut -c1-200
    --output-format csv -d "$ROOT/$OUT/long_fp8" -o run -- python3 "$ROOT/tools/profile_step.py" > "$ROOT/$OUT/long_fp8.log" 2>&1) || exit 1
 python3 tools/kstats.py "$OUT/long_fp8" 3 > "$OUT/kstats.txt" && head -25 "$OUT/kstats.txt"
 for dt in fp8 bf16; do
-  timeout -k 10 300 python -u bench.py --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --dtype $dt --clips 8 --frames 1000 --steps 3 --warmup 1 --no-compare --no-cpu-baseline \
     --no-long > "$OUT/bench_$dt.json" 2> "$OUT/bench_$dt.err" || { tail -20 "$OUT/bench_$dt.err"; exit 1; }
   cut -c1-300 "$OUT/bench_$dt.json"
 done

@@ -16,7 +16,7 @@ elif [ "$SEL" != "none" ]; then
   timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 120 --timeout-method thread -k "$SEL" > "$OUT/pytest_gpu.log" 2>&1; t=$?
 fi
 [ $t -eq 0 ] \
-&& timeout -k 10 300 python -u bench.py --steps 20 --no-compare --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" \
+&& timeout -k 10 300 python -u bench.py --full --steps 20 --no-compare --no-cpu-baseline > "$OUT/bench.json" 2> "$OUT/bench.err" \
 && (cd /tmp && STEPS=2 timeout -k 10 300 rocprofv3 --kernel-trace --output-format csv -d "$ROOT/$OUT/trace" -o run -- \
       python3 "$ROOT/tools/profile_step.py" > "$ROOT/$OUT/trace.log" 2>&1)
 rc=$?

@@ -9,7 +9,7 @@ ROOT=$(pwd)
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 export STEPS=2
-M2S_PROF_DETAIL=1 M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --steps 4 --warmup 2 --no-cpu-baseline \
+M2S_PROF_DETAIL=1 M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --full --steps 4 --warmup 2 --no-cpu-baseline \
     > "$OUT/bench_detail.json" 2> "$OUT/bench_detail.err" \
 && (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$ROOT/$OUT/fetch" -o run -- \
       python3 "$ROOT/tools/profile_step.py" > "$ROOT/$OUT/fetch.log" 2>&1) \

@@ -10,7 +10,7 @@ mkdir -p "$OUT"
 export TMPDIR=/tmp STEPS=2
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 \
 && (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/prof" -o run -- \
-      python3 "$ROOT/bench.py" --steps 10 --warmup 2 --no-cpu-baseline --no-compare --no-parity > "$ROOT/$OUT/bench_prof.json" 2> "$ROOT/$OUT/prof.err") \
+      python3 "$ROOT/bench.py" --full --steps 10 --warmup 2 --no-cpu-baseline --no-compare --no-parity > "$ROOT/$OUT/bench_prof.json" 2> "$ROOT/$OUT/prof.err") \
 && (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$ROOT/$OUT/fetch" -o run -- \
       python3 "$ROOT/tools/profile_step.py" > "$ROOT/$OUT/fetch.log" 2>&1) \
 && (cd /tmp && timeout -s KILL 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d "$ROOT/$OUT/write" -o run -- \

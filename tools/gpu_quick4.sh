@@ -12,7 +12,7 @@ if [ "$SEL" != "none" ]; then
     || { tail -40 "$OUT/pytest.log"; exit 1; }
   tail -2 "$OUT/pytest.log"
 fi
-M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-compare --no-cpu-baseline --no-parity --no-long "$@" \
+M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-compare --no-cpu-baseline --no-parity --no-long "$@" \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cut -c1-300 "$OUT/bench.json"
 grep "^#" "$OUT/bench.err" | head -25

@@ -13,7 +13,7 @@ if [ "${TESTS:-0}" = 1 ]; then
   && timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
   rc=$?
 fi
-[ $rc = 0 ] && timeout -k 10 500 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+[ $rc = 0 ] && timeout -k 10 500 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 rc=$?
 [ $rc = 0 ] && [ "${EVIDENCE:-1}" = 1 ] && bash tools/gpu_evidence.sh "${TAG}_ev" > "$OUT/evidence.log" 2>&1
 rc=$?

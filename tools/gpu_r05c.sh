@@ -11,7 +11,7 @@ timeout -k 10 400 python -u -m pytest tests/test_gpu_bf16x3.py tests/test_gpu_pa
 rc=$?
 tail -3 "$OUT/pytest.log"
 [ $rc = 0 ] || exit $rc
-M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --steps 20 --no-caller --no-long --no-compare --no-cpu-baseline \
+M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --full --steps 20 --no-caller --no-long --no-compare --no-cpu-baseline \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $?
 M2S_IR_WS_TRACE=1 timeout -k 10 200 python -u tools/trace_ir_ws.py > "$OUT/irws_trace.txt" 2>&1 || exit $?
 cut -c1-300 "$OUT/bench.json"; grep -E "ir_ws|se_ws|stem|er_sp" "$OUT/bench.err" | head -8

@@ -6,6 +6,6 @@ TAG=${1:-r06b}
 OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
-timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 cut -c1-400 "$OUT/bench.json"
 if [ -n "$2" ]; then bash tools/ab_bench_stages.sh "$TAG/ab" "$2" 2 || exit 1; fi

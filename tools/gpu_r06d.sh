@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 600 python -u -m pytest tests/test_gpu_bf16x3.py tests/test_gpu_configs.py tests/test_gpu_parity.py -m gpu -x -q \
   --timeout 300 --timeout-method thread > "$OUT/pytest.log" 2>&1 || { tail -40 "$OUT/pytest.log"; exit 1; }
 tail -2 "$OUT/pytest.log"
-timeout -k 10 300 python -u bench.py --steps 30 --warmup 3 --no-compare --no-long --no-cpu-baseline --no-caller \
+timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 3 --no-compare --no-long --no-cpu-baseline --no-caller \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']; print(d['value'], d['ms_per_step'], d['parity']['wav_max_abs'], r['kernel'], r['avg_launch_us'], r['bound'], r['frac']); print({k: v['ms_per_step'] for k, v in r['stages'].items()})"
 (cd /tmp && CHUNK=1920 STEPS=3 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv -d "$ROOT/$OUT/prof" -o run -- \

@@ -11,6 +11,6 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_bf16x3.py tests/test_gpu_co
 tail -2 "$OUT/pytest.log"
 AB_VALUES=0,1 timeout -k 10 300 python -u tools/ab_env.py M2S_SEWS_HALF 2 bf16x3 > "$OUT/ab.txt" 2>&1 || { tail -20 "$OUT/ab.txt"; exit 1; }
 grep -v amdgpu.ids "$OUT/ab.txt"
-timeout -k 10 300 python -u bench.py --steps 30 --warmup 3 --no-compare --no-long --no-cpu-baseline --no-caller \
+timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 3 --no-compare --no-long --no-cpu-baseline --no-caller \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 python3 -c "import json; d=json.load(open('$OUT/bench.json')); r=d['roofline']; print(d['value'], d['ms_per_step'], d['parity']['wav_max_abs'], r['kernel'], r['avg_launch_us'], r['bound'], r['frac'])"

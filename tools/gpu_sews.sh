@@ -11,7 +11,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 "$OUT/pytest.log"
 run() {  # run <name> <env...>
   local n=$1; shift
-  env "$@" M2S_BENCH_KERNELS=1 timeout -k 10 200 python -u bench.py --steps 20 --warmup 3 --no-compare --no-cpu-baseline \
+  env "$@" M2S_BENCH_KERNELS=1 timeout -k 10 200 python -u bench.py --full --steps 20 --warmup 3 --no-compare --no-cpu-baseline \
     --no-parity --no-long > "$OUT/bench_$n.json" 2> "$OUT/bench_$n.err" || { tail -20 "$OUT/bench_$n.err"; return 1; }
   echo "== $n: $(cut -c1-200 "$OUT/bench_$n.json")"
   grep -E "^# (se_ws|conv_gemm_kernel<128, 128, 4, 4, 2, 3, 2, 1>|ir_ws)" "$OUT/bench_$n.err"

@@ -10,7 +10,7 @@ export TMPDIR=/tmp
 timeout -k 10 500 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -k "${2:-bf16x3}" > "$OUT/pytest.log" 2>&1 \
   || { tail -40 "$OUT/pytest.log"; exit 1; }
 tail -2 "$OUT/pytest.log"
-timeout -k 10 300 python -u bench.py --steps 30 --warmup 3 --no-compare --no-cpu-baseline --no-long > "$OUT/bench.json" 2> "$OUT/bench.err" \
+timeout -k 10 300 python -u bench.py --full --steps 30 --warmup 3 --no-compare --no-cpu-baseline --no-long > "$OUT/bench.json" 2> "$OUT/bench.err" \
   || { tail -20 "$OUT/bench.err"; exit 1; }
 cut -c1-330 "$OUT/bench.json"
 for v in 1 0; do

@@ -10,7 +10,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout
 tail -2 "$OUT/pytest.log"
 M2S_IR_WS_TRACE=1 timeout -k 10 200 python -u tools/trace_ir_ws.py > "$OUT/trace.txt" 2>&1 || { tail -20 "$OUT/trace.txt"; exit 1; }
 grep -o "STEMTRACE.\{0,900\}" "$OUT/trace.txt" | head -1
-M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --steps 20 --warmup 3 --no-compare --no-cpu-baseline --no-parity --no-long \
+M2S_BENCH_KERNELS=1 timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 3 --no-compare --no-cpu-baseline --no-parity --no-long \
   > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 1; }
 cut -c1-250 "$OUT/bench.json"
 grep "stem_b0\|lstm" "$OUT/bench.err"
