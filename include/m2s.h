@@ -167,6 +167,35 @@ int m2s_pipeline_forward(m2s_acoustic* m, m2s_vocoder* v, const float* frames, i
                          const float* mean, const float* std, float* mel_norm, float* mel_db, float* mel_log,
                          float* wav, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- ragged batches ---- */
+/* Clips of different lengths in one call.  The data is PACKED: `lengths` is a HOST array of B integers, each
+ * >= 1; N = sum(lengths); clip b owns rows off_b .. off_b + lengths[b] - 1 of every (N, ...) tensor, off = the
+ * exclusive prefix sum.  Frames are (N,H,W), feats (N,208), mels (N,n_mels), wav (N*hop).  Padding to
+ * Tmax = max(lengths) exists only inside the workspace: the batched kernels run on (B,Tmax) blocks, with exact
+ * zeros written where a short clip's reverse LSTM direction and the generator's look-ahead (conv_pre, every
+ * ConvTranspose1d, conv_post) must see them, so each clip's result is the per-clip one (DESIGN.md "Ragged
+ * batches").  With all lengths equal every output is bit-identical to the dense entry point's on (B,T).
+ * M2S_E_ARG, before any launch, if B < 1, a length is < 1, or sum(lengths) != `rows`.  The clip table travels
+ * through an engine-owned pinned buffer per call, so these calls cannot be captured into a graph: M2S_E_STATE if
+ * `stream` is capturing.  The *_workspace_bytes queries return 0 for arguments the calls would reject. */
+size_t m2s_acoustic_ragged_workspace_bytes(const m2s_acoustic* m, const int* lengths, int B, int H, int W);
+/* feats (rows,208) -> y (rows,rnn_hidden) (may be NULL) and mel_norm (rows,n_mels) (may be NULL), packed. */
+int m2s_bilstm_summerge_ragged(m2s_acoustic* m, const float* feats, const int* lengths, int B, int rows, float* y,
+                               float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+/* frames (rows,H,W) fp32 in [0,1] -> mel_norm (rows,n_mels), packed. */
+int m2s_acoustic_forward_ragged(m2s_acoustic* m, const float* frames, const int* lengths, int B, int rows, int H,
+                                int W, float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+size_t m2s_vocoder_ragged_workspace_bytes(const m2s_vocoder* v, const int* lengths, int B);
+/* mel (rows,num_mels) fp32, packed layout 1 -> wav (rows*hop) fp32, packed. */
+int m2s_vocoder_forward_ragged(m2s_vocoder* v, const float* mel, const int* lengths, int B, int rows, float* wav,
+                               void* ws, size_t ws_bytes, void* stream);
+size_t m2s_pipeline_ragged_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, const int* lengths, int B,
+                                           int H, int W);
+/* frames (rows,H,W) -> mel_norm, mel_db, mel_log (rows,n_mels) and wav (rows*hop), packed.  mel_* may be NULL. */
+int m2s_pipeline_forward_ragged(m2s_acoustic* m, m2s_vocoder* v, const float* frames, const int* lengths, int B,
+                                int rows, int H, int W, const float* mean, const float* std, float* mel_norm,
+                                float* mel_db, float* mel_log, float* wav, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------- Grad-CAM (autograd) path ---- */
 /* compute_gradcam (scripts/mri_gradcam_formant.py:203-279) runs the model in train() and back-
  * propagates a mel-band power to the last feature map.  These entry points are that path, exact

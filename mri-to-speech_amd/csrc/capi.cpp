@@ -264,6 +264,91 @@ int m2s_pipeline_forward(m2s_acoustic* m, m2s_vocoder* v, const float* frames, i
   });
 }
 
+size_t m2s_acoustic_ragged_workspace_bytes(const m2s_acoustic* m, const int* lengths, int B, int H, int W) {
+  size_t r = 0;
+  if (!m) return 0;
+  guarded([&] { r = m->impl.ragged_workspace_bytes(lengths, B, H, W); });
+  return r;
+}
+
+int m2s_bilstm_summerge_ragged(m2s_acoustic* m, const float* feats, const int* lengths, int B, int rows, float* y,
+                               float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && feats && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.bilstm_ragged(feats, lengths, B, rows, y, mel_norm, w, S(stream));
+  });
+}
+
+int m2s_acoustic_forward_ragged(m2s_acoustic* m, const float* frames, const int* lengths, int B, int rows, int H,
+                                int W, float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && frames && mel_norm && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mel_norm, ws, ws_bytes, S(stream));
+  });
+}
+
+size_t m2s_vocoder_ragged_workspace_bytes(const m2s_vocoder* v, const int* lengths, int B) {
+  size_t r = 0;
+  if (!v) return 0;
+  guarded([&] { r = v->impl.ragged_workspace_bytes(lengths, B); });
+  return r;
+}
+
+int m2s_vocoder_forward_ragged(m2s_vocoder* v, const float* mel, const int* lengths, int B, int rows, float* wav,
+                               void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(v && mel && wav && ws, "null argument");
+    DeviceGuard g(v->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    v->impl.forward_ragged(mel, lengths, B, rows, wav, w, S(stream));
+  });
+}
+
+size_t m2s_pipeline_ragged_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, const int* lengths, int B,
+                                           int H, int W) {
+  size_t r = 0;
+  if (!m || !v) return 0;
+  guarded([&] {
+    const size_t a = m->impl.ragged_workspace_bytes(lengths, B, H, W), b = v->impl.ragged_workspace_bytes(lengths, B);
+    size_t rows = 0;
+    for (int i = 0; i < B; ++i) rows += (size_t)lengths[i];
+    m2s::Workspace w(nullptr, 0);
+    w.take<float>(rows * m->impl.n_mels());
+    w.take<char>(std::max(a, b));
+    r = w.used();
+  });
+  return r;
+}
+
+int m2s_pipeline_forward_ragged(m2s_acoustic* m, m2s_vocoder* v, const float* frames, const int* lengths, int B,
+                                int rows, int H, int W, const float* mean, const float* std, float* mel_norm,
+                                float* mel_db, float* mel_log, float* wav, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && v && frames && mean && std && wav && ws, "null argument");
+    M2S_CHECK(m->impl.device() == v->impl.device(), "acoustic model and vocoder on different devices");
+    M2S_CHECK(m->impl.n_mels() == v->impl.num_mels(), "n_mels mismatch between acoustic model and vocoder");
+    no_pending_error(m->impl);
+    m2s::ragged_dims(lengths, B, rows);
+    DeviceGuard g(m->impl.device());
+    const int nm = m->impl.n_mels();
+    m2s::Workspace w(ws, ws_bytes);
+    // the head writes the caller's mel_norm directly where there is one (packed rows: no internal layout)
+    float* own = w.take<float>((size_t)rows * nm);
+    float* mn = mel_norm ? mel_norm : own;
+    char* rest = w.take<char>(0);
+    const size_t rest_bytes = ws_bytes - (size_t)(rest - static_cast<char*>(ws));
+    // acoustic scratch is dead once mel_norm is written; the vocoder reuses it
+    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mn, rest, rest_bytes, S(stream));
+    m2s::Workspace vw(rest, rest_bytes);
+    v->impl.forward_from_norm_ragged(mn, mean, std, lengths, B, rows, mel_db, mel_log, wav, vw, S(stream));
+  });
+}
+
 int m2s_cam_create(const m2s_tensor* sd, int n, int device, m2s_cam** out) {
   return guarded([&] {
     M2S_CHECK(out && (sd || n == 0), "null argument");

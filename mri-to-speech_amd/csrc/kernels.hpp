@@ -294,6 +294,29 @@ void launch_conv1d_f8(const void* x8, int B, int L, int C, int k, int dil, const
                       const float* bias, const void* res, void* y, void* y8, float slope8, int accum, float accum_div,
                       hipStream_t s, double flops, double bytes);
 
+// Ragged batches (ragged.hip): clip b of len[b] steps owns packed rows off[b] .. off[b] + len[b] - 1; the dense
+// kernels run on (B, Tmax, ...) blocks.  tab = device table [off: B ints | len: B ints].
+// packed gate pre-activations (N, width) -> padded (B, Tmax, width), exact zero rows at t >= len[b]
+void launch_ragged_pre_scatter(const float* pre_packed, const int* tab, int B, int Tmax, int width, float* pre,
+                               hipStream_t s);
+// launch_mel_head (and the sum merge y = hs[0] + hs[1]) on the valid rows of hs (2, B, Tmax, H) -> packed
+// y (N, H) / mel_norm (N, n_mels); either may be null.  Rounds as mel_head_kernel / add2_kernel do.
+void launch_ragged_head_gather(const float* hs, const int* tab, int B, int Tmax, int H, const float* wt, const float* b,
+                               int n_mels, float* y, float* mel_norm, hipStream_t s);
+// packed x (N, n_mels) -> padded channel-last ln_t (B, Tmax, cs) with exact zeros at t >= len[b].  mean != null:
+// x is mel_norm, launch_mel_glue's arithmetic, packed db / ln (N, n_mels) outputs (may be null); mean == null: x
+// is the ln-mel itself (launch_mel_to_nlc, layout 1).
+template <typename T>
+void launch_ragged_glue(const float* x, const int* tab, int B, int Tmax, int n_mels, const float* mean,
+                        const float* std_, float* db, float* ln, T* ln_t, int cs, hipStream_t s);
+// zeroes `halo` rows from row len[b] * scale of clip b in a buffer of `rows` = Tmax * scale rows per clip, a row =
+// row_bytes contiguous bytes (fp32, bf16 or the split hi / lo pair); nothing past the clip's own rows
+void launch_ragged_tail_mask(void* x, const int* tab, int B, int rows, int scale, int halo, size_t row_bytes,
+                             hipStream_t s);
+// padded wav (B, Tmax * hop) -> packed (N * hop)
+void launch_ragged_wav_pack(const float* wav_padded, const int* tab, int B, int Tmax, int hop, float* wav,
+                            hipStream_t s);
+
 // (rows, cs) T -> (rows, C) fp32 dense (debug taps)
 template <typename T>
 void launch_unpad(const T* x, long rows, int C, int cs, float* y, hipStream_t s);

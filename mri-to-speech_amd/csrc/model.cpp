@@ -590,7 +590,7 @@ size_t Acoustic::workspace_bytes(int B, int T, int H, int W) const {
   ws.take<float>(BT * 8 * hidden_);
   ws.take<float>(2 * BT * hidden_);
   ws.take<float>((size_t)2 * B * hidden_);
-  ws.take<char>(std::max({lstm_persistent_sync_bytes(), lstm_small_sync_bytes(), lstm_mid_sync_bytes(), lstm_x3_sync_bytes(), lstm_x3g_sync_bytes()}));
+  ws.take<char>(lstm_sync_bytes());
   return ws.used();
 }
 
@@ -943,6 +943,44 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
   }
 }
 
+size_t Acoustic::lstm_sync_bytes() {
+  return std::max({lstm_persistent_sync_bytes(), lstm_small_sync_bytes(), lstm_mid_sync_bytes(), lstm_x3_sync_bytes(),
+                   lstm_x3g_sync_bytes()});
+}
+
+void Acoustic::lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps,
+                               double rows, hipStream_t s) {
+  const int H = hidden_;
+  const float* whh = static_cast<const float*>(arena_.ptr(whh_));
+  // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
+  const double bytes = 4.0 * 2 * 4 * H * H + 4.0 * rows * (8.0 * H + 2.0 * H);
+  const double f2 = 2.0 * 2 * 4.0 * H * H * seq_steps, f3 = 3.0 * 2 * 4.0 * H * H * seq_steps;
+  if (lstm_persistent_ && lstm_small_supported(B, H)) {
+    ProfScope ps("lstm_small_kernel", f2, bytes, s);
+    launch_lstm_small(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, &gsync_epoch_);
+  } else if (lstm_persistent_ && lstm_x3_ && lstm_x3g_ && dtype_ != M2S_DT_F32 && lstm_x3g_supported(B, H)) {
+    // 5..16 sequences (configs[4]'s 8 clips a GPU): the granule hand-off (lstm_persistent.hip lstm_x3g_kernel)
+    ProfScope ps("lstm_x3g_kernel", f3, bytes, s);
+    launch_lstm_x3g(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, &gsync_epoch_);
+  } else if (lstm_persistent_ && lstm_x3_ && dtype_ != M2S_DT_F32 && lstm_persistent_supported(H)) {
+    // split engines above the small-batch kernel: 4.1 / 5.2 / 9.9 us per step at B = 8 / 16 / 64 against
+    // lstm_mid's 7.2 / 11.9 and the f32 counter-barrier kernel's 24 (gpurun_out lstm2, lstm3_x3small)
+    ProfScope ps("lstm_x3_kernel", f3, bytes, s);
+    launch_lstm_x3(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
+  } else if (lstm_persistent_ && lstm_mid_ && lstm_mid_supported(B, H)) {
+    ProfScope ps("lstm_mid_kernel", f2, bytes, s);
+    launch_lstm_mid(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
+  } else if (lstm_persistent_ && lstm_persistent_supported(H)) {
+    ProfScope ps("lstm_persistent_kernel", f2, bytes, s);
+    launch_lstm_persistent(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
+  } else {
+    for (int st = 0; st < T; ++st) {
+      ProfScope ps("lstm_step_kernel", 2.0 * 2 * (rows / T) * 4.0 * H * H, 4.0 * 2 * 4 * H * H, s);
+      launch_lstm_step(pre, whh, hs, cst, B, T, H, st, s);
+    }
+  }
+}
+
 void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_norm, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "bilstm: empty input");
   const int H = hidden_;
@@ -958,38 +996,11 @@ void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_nor
   // small passes (<= 64 frames): the four waves of a row tile split K (one 30-frame clip: 20 -> 12 us); larger passes
   // keep four row groups a workgroup sharing the weight tile (K split there: the 1920-frame step's projection
   // 0.13 ms slower).  The K summation order therefore differs between the two size classes (fp32 rounding only).
+  // (keyed on the projection's row count M: a ragged call of N packed rows switches where a dense one of N does)
   a.kwave = BT <= 64 ? 1 : 0;
   run_conv<float>(a, lstm_ih_, s);
-  void* sync = ws.take<char>(std::max({lstm_persistent_sync_bytes(), lstm_small_sync_bytes(), lstm_mid_sync_bytes(), lstm_x3_sync_bytes(), lstm_x3g_sync_bytes()}));
-  if (lstm_persistent_ && lstm_small_supported(B, H)) {
-    ProfScope ps("lstm_small_kernel", 2.0 * 2 * B * 4.0 * H * H * (T - 1), 4.0 * 2 * 4 * H * H + 4.0 * BT * (8.0 * H + 2.0 * H), s);
-    launch_lstm_small(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s,
-                      &gsync_epoch_);
-  } else if (lstm_persistent_ && lstm_x3_ && lstm_x3g_ && dtype_ != M2S_DT_F32 && lstm_x3g_supported(B, H)) {
-    // 5..16 sequences (configs[4]'s 8 clips a GPU): the granule hand-off (lstm_persistent.hip lstm_x3g_kernel)
-    ProfScope ps("lstm_x3g_kernel", 3.0 * 2 * B * 4.0 * H * H * (T - 1), 4.0 * 2 * 4 * H * H + 4.0 * BT * (8.0 * H + 2.0 * H), s);
-    launch_lstm_x3g(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s,
-                    &gsync_epoch_);
-  } else if (lstm_persistent_ && lstm_x3_ && dtype_ != M2S_DT_F32 && lstm_persistent_supported(H)) {
-    // split engines above the small-batch kernel: 4.1 / 5.2 / 9.9 us per step at B = 8 / 16 / 64 against
-    // lstm_mid's 7.2 / 11.9 and the f32 counter-barrier kernel's 24 (gpurun_out lstm2, lstm3_x3small)
-    ProfScope ps("lstm_x3_kernel", 3.0 * 2 * B * 4.0 * H * H * (T - 1), 4.0 * 2 * 4 * H * H + 4.0 * BT * (8.0 * H + 2.0 * H), s);
-    launch_lstm_x3(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else if (lstm_persistent_ && lstm_mid_ && lstm_mid_supported(B, H)) {
-    ProfScope ps("lstm_mid_kernel", 2.0 * 2 * B * 4.0 * H * H * (T - 1), 4.0 * 2 * 4 * H * H + 4.0 * BT * (8.0 * H + 2.0 * H), s);
-    launch_lstm_mid(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else if (lstm_persistent_ && lstm_persistent_supported(H)) {
-    // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
-    ProfScope ps("lstm_persistent_kernel", 2.0 * 2 * B * 4.0 * H * H * (T - 1),
-                 4.0 * 2 * 4 * H * H + 4.0 * BT * (8.0 * H + 2.0 * H), s);
-    launch_lstm_persistent(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, B, T, H, sync, lstm_spin_max_,
-                           err_dev_, s);
-  } else {
-    for (int st = 0; st < T; ++st) {
-      ProfScope ps("lstm_step_kernel", 2.0 * 2 * B * 4.0 * H * H, 4.0 * 2 * 4 * H * H, s);
-      launch_lstm_step(pre, static_cast<const float*>(arena_.ptr(whh_)), hs, cst, B, T, H, st, s);
-    }
-  }
+  void* sync = ws.take<char>(lstm_sync_bytes());
+  lstm_recurrence(pre, hs, cst, sync, B, T, (double)B * (T - 1), (double)BT, s);
   if (mel_norm) {
     StageTag head("head");
     ProfScope ps("mel_head_kernel", 2.0 * BT * H * n_mels_, 4.0 * BT * (2 * H + n_mels_), s);
@@ -1006,6 +1017,120 @@ void Acoustic::forward(const float* frames, int B, int T, int H, int W, float* m
   float* feats = ws.take<float>((size_t)B * T * EFF_OUT);
   effnet(frames, B * T, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm(feats, B, T, nullptr, mel_norm, ws, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// Ragged batches (ragged.hip, DESIGN.md "Ragged batches")
+RaggedDims ragged_dims(const int* lengths, int B, long rows) {
+  M2S_CHECK(lengths && B >= 1, "ragged: at least one clip (lengths must not be empty)");
+  RaggedDims d;
+  d.B = B;
+  d.Tmin = lengths[0];
+  for (int b = 0; b < B; ++b) {
+    M2S_CHECK(lengths[b] >= 1, "ragged: clip " + std::to_string(b) + " has length " + std::to_string(lengths[b]) +
+                                   "; every length must be >= 1");
+    d.N += lengths[b];
+    d.Tmax = std::max(d.Tmax, lengths[b]);
+    d.Tmin = std::min(d.Tmin, lengths[b]);
+  }
+  M2S_CHECK(d.N == rows, "ragged: sum(lengths) = " + std::to_string(d.N) + " but the packed input has " +
+                             std::to_string(rows) + " rows");
+  // the dense path counts its B x T rows in an int (the projection's M, the kernels' row indices)
+  M2S_CHECK((double)B * d.Tmax <= 2147483647.0 && B <= 65535, "ragged: B x Tmax out of range");
+  return d;
+}
+
+RaggedTable::~RaggedTable() {
+  if (done_) (void)hipEventDestroy(done_);
+  if (host_) (void)hipHostFree(host_);
+}
+
+void ragged_check_stream(hipStream_t s) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  M2S_HIP(hipStreamIsCapturing(s, &cap));
+  if (cap != hipStreamCaptureStatusNone)
+    throw Error(M2S_E_STATE, "ragged calls cannot be captured into a graph (the clip table is staged per call)");
+}
+
+void RaggedTable::upload(const int* lengths, int B, int* dev, hipStream_t s) {
+  ragged_check_stream(s);
+  if (!done_) M2S_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+  M2S_HIP(hipEventSynchronize(done_));  // the previous call's copy has read the staging buffer
+  if (cap_ < (size_t)2 * B) {
+    if (host_) M2S_HIP(hipHostFree(host_));
+    host_ = nullptr;
+    cap_ = 0;
+    M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&host_), (size_t)2 * B * sizeof(int), hipHostMallocDefault));
+    cap_ = (size_t)2 * B;
+  }
+  int off = 0;
+  for (int b = 0; b < B; ++b) {
+    host_[b] = off;
+    host_[B + b] = lengths[b];
+    off += lengths[b];
+  }
+  M2S_HIP(hipMemcpyAsync(dev, host_, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, s));
+  M2S_HIP(hipEventRecord(done_, s));
+}
+
+size_t Acoustic::ragged_workspace_bytes(const int* lengths, int B, int H, int W) const {
+  long n = 0;
+  for (int b = 0; lengths && b < B; ++b) n += lengths[b];
+  const RaggedDims d = ragged_dims(lengths, B, n);
+  const size_t BT = (size_t)B * d.Tmax;
+  Workspace ws(nullptr, 0);
+  ws.take<float>((size_t)d.N * EFF_OUT);
+  ws.take<char>(effnet_ws((int)d.N, H, W));
+  ws.take<int>((size_t)2 * B);
+  ws.take<float>((size_t)d.N * 8 * hidden_);
+  ws.take<float>(BT * 8 * hidden_);
+  ws.take<float>(2 * BT * hidden_);
+  ws.take<float>((size_t)2 * B * hidden_);
+  ws.take<char>(lstm_sync_bytes());
+  return ws.used();
+}
+
+void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long N, float* y, float* mel_norm,
+                             Workspace& ws, hipStream_t s) {
+  const RaggedDims d = ragged_dims(lengths, B, N);
+  const int H = hidden_, T = d.Tmax;
+  const size_t BT = (size_t)B * T;
+  int* tab = ws.take<int>((size_t)2 * B);
+  float* pre_packed = ws.take<float>((size_t)N * 8 * H);
+  float* pre = ws.take<float>(BT * 8 * H);
+  float* hs = ws.take<float>(2 * BT * H);
+  float* cst = ws.take<float>((size_t)2 * B * H);
+  void* sync = ws.take<char>(lstm_sync_bytes());
+  rtab_.upload(lengths, B, tab, s);
+  StageTag tag("bilstm");
+  ConvArgs a = conv_args(lstm_ih_);
+  a.x = feats;
+  a.y = pre_packed;
+  a.M = (int)N;
+  a.kwave = N <= 64 ? 1 : 0;  // as bilstm: by the projection's row count
+  run_conv<float>(a, lstm_ih_, s);
+  {
+    ProfScope ps("ragged_pre_scatter_kernel", 0.0, 2.0 * 4.0 * N * 8.0 * H, s);
+    launch_ragged_pre_scatter(pre_packed, tab, B, T, 8 * H, pre, s);
+  }
+  // the dense kernels, Tmax steps for every clip: zero pre-activation rows keep the reverse direction's state at
+  // exactly zero until the clip's last frame, and the forward direction's padded steps are never read
+  lstm_recurrence(pre, hs, cst, sync, B, T, (double)(N - B), (double)N, s);
+  StageTag head("head");
+  ProfScope ps("ragged_head_gather_kernel", mel_norm ? 2.0 * N * H * n_mels_ : 0.0,
+               4.0 * N * (2 * H + (mel_norm ? n_mels_ : 0) + (y ? H : 0)), s);
+  launch_ragged_head_gather(hs, tab, B, T, H, static_cast<const float*>(arena_.ptr(head_wt_)),
+                            static_cast<const float*>(arena_.ptr(head_b_)), n_mels_, y, mel_norm, s);
+}
+
+void Acoustic::forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm,
+                              void* wsp, size_t wsb, hipStream_t s) {
+  ragged_dims(lengths, B, N);  // before the CNN launches
+  ragged_check_stream(s);
+  Workspace ws(wsp, wsb);
+  float* feats = ws.take<float>((size_t)N * EFF_OUT);
+  effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
+  bilstm_ragged(feats, lengths, B, N, nullptr, mel_norm, ws, s);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1276,6 +1401,69 @@ void Vocoder::forward_from_norm(const float* mel_norm, const float* mean, const 
     run_t<float>(ln_buf, B, T, wav, ws, s);
 }
 
+// Ragged batches.  Workspace: clip table, padded ln-mel, padded wav, then run_t's buffers for (B, Tmax).
+size_t Vocoder::ragged_workspace_bytes(const int* lengths, int B) const {
+  long n = 0;
+  for (int b = 0; lengths && b < B; ++b) n += lengths[b];
+  const RaggedDims d = ragged_dims(lengths, B, n);
+  const size_t es = act_bytes(dtype_);
+  Workspace ws(nullptr, 0);
+  ws.take<int>((size_t)2 * B);
+  ws.take<char>((size_t)B * d.Tmax * chan_stride(h_.num_mels) * es);
+  ws.take<float>((size_t)B * d.Tmax * hop_);
+  for (int i = 0; i < act_buffers(); ++i) ws.take<char>(act_elems(B, d.Tmax) * es);
+  return ws.used();
+}
+
+void Vocoder::ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
+                         float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s) {
+  const RaggedDims d = ragged_dims(lengths, B, N);
+  const int nm = h_.num_mels, cs = chan_stride(nm), T = d.Tmax;
+  int* tab = ws.take<int>((size_t)2 * B);
+  void* ln_buf = ws.take<char>((size_t)B * T * cs * act_bytes(dtype_));
+  float* wav_pad = ws.take<float>((size_t)B * T * hop_);
+  rtab_.upload(lengths, B, tab, s);
+  // the masks write only where a clip is shorter than Tmax: with equal lengths the generator runs as the dense call
+  const int* mask_tab = d.Tmin < T ? tab : nullptr;
+  {
+    StageTag tag("glue");
+    const double bytes = 4.0 * N * nm * (mean ? 4 : 2);
+    if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8) {
+      ProfScope ps("ragged_glue_kernel<unsigned short>", 0.0, bytes, s);
+      launch_ragged_glue<bf16_t>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<bf16_t*>(ln_buf), cs, s);
+    } else if (dtype_ == M2S_DT_BF16X3) {
+      ProfScope ps("ragged_glue_kernel<m2s::sp_t>", 0.0, bytes, s);
+      launch_ragged_glue<sp_t>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<sp_t*>(ln_buf), cs, s);
+    } else {
+      ProfScope ps("ragged_glue_kernel<float>", 0.0, bytes, s);
+      launch_ragged_glue<float>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<float*>(ln_buf), cs, s);
+    }
+  }
+  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)
+    run_t<bf16_t>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
+  else if (dtype_ == M2S_DT_BF16X3)
+    run_t<sp_t>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
+  else
+    run_t<float>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
+  StageTag tag("voc_post");
+  ProfScope ps("ragged_wav_pack_kernel", 0.0, 2.0 * 4.0 * N * hop_, s);
+  launch_ragged_wav_pack(wav_pad, tab, B, T, hop_, wav, s);
+}
+
+void Vocoder::forward_ragged(const float* mel, const int* lengths, int B, long N, float* wav, Workspace& ws,
+                             hipStream_t s) {
+  ragged_run(mel, nullptr, nullptr, lengths, B, N, nullptr, nullptr, wav, ws, s);
+}
+
+void Vocoder::forward_from_norm_ragged(const float* mel_norm, const float* mean, const float* std_, const int* lengths,
+                                       int B, long N, float* mel_db, float* mel_log, float* wav, Workspace& ws,
+                                       hipStream_t s) {
+  M2S_CHECK(mean && std_, "vocoder: null mel statistics");
+  ragged_run(mel_norm, mean, std_, lengths, B, N, mel_db, mel_log, wav, ws, s);
+}
+
+constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right pad of 6 (launch_conv_post)
+
 // split: + the batched stages' per-resblock buffers; fp8: + one for the e4m3 pair outputs (run_t)
 int Vocoder::act_buffers() const { return dtype_ == M2S_DT_BF16X3 ? 5 + 3 * CONV_BATCH : dtype_ == M2S_DT_FP8 ? 6 : 5; }
 
@@ -1363,8 +1551,16 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
 }
 
 template <typename T>
-void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s) {
+void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab) {
   constexpr bool SPL = std::is_same<T, sp_t>::value;
+  // ragged calls: zero the `halo` rows of S that the next consumer reads past the end of a short clip (they hold
+  // biases and resblock outputs of the padding; lrelu(0) = 0, so masking before the activation is equivalent)
+  auto mask_tail = [&](T* S, int L, int halo, int cs) {
+    if (!tab || halo <= 0) return;
+    const size_t row_bytes = sizeof(T) * Elem<T>::R * (size_t)cs;
+    ProfScope ps("ragged_tail_mask_kernel", 0.0, (double)B * halo * row_bytes, s);
+    launch_ragged_tail_mask(S, tab, B, L, L / Tn, halo, row_bytes, s);
+  };
   const size_t n = act_elems(B, Tn) * Elem<T>::R;
   T* X = ws.take<T>(n);
   T* Hb[2] = {ws.take<T>(n), ws.take<T>(n)};
@@ -1406,6 +1602,8 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     const PConv& up = ups_[i];
     const bool batched = is_batched(i);
     StageTag tag("ups_c" + std::to_string(up.cout));
+    // a transposed conv of rate u and padding p reads floor((u - 1 + p) / u) input rows ahead of its output
+    mask_tail(S, L, (up.ct_u - 1 + up.ct_pad) / up.ct_u, up.cs_in);
     ConvArgs a = conv_args(up);
     a.x = S;
     a.y = X;
@@ -1535,6 +1733,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     }
   }
   StageTag tag("voc_post");
+  mask_tail(S, L, CONV_POST_TAPS - 1, chan_stride(post_c_));
   ProfScope ps(tname<T>(post_c_ <= 64 ? "conv_post_tile_kernel" : "conv_post_kernel"), 2.0 * B * L * post_c_ * 7, (sizeof(T) * Elem<T>::R) * (double)B * L * post_c_ + 4.0 * B * L, s);
   launch_conv_post<T>(S, B, L, post_c_, chan_stride(post_c_), static_cast<const float*>(arena_.ptr(post_w_)), post_b_,
                       wav, s);

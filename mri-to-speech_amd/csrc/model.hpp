@@ -79,6 +79,35 @@ class Workspace {  // bump allocator over a caller-provided device buffer
   size_t used_ = 0;
 };
 
+// Ragged batches (ragged.hip): `lengths[B]` host integers >= 1, N = sum(lengths) packed rows, Tmax = max.
+struct RaggedDims {
+  int B = 0, Tmax = 0, Tmin = 0;
+  long N = 0;
+};
+// M2S_E_ARG unless B >= 1, every length >= 1, sum(lengths) == rows and B x Tmax rows fit the dense kernels' int
+// row counts; no launch happens before it
+RaggedDims ragged_dims(const int* lengths, int B, long rows);
+// M2S_E_STATE if `s` is capturing: a ragged call stages its clip table per call and cannot be replayed
+void ragged_check_stream(hipStream_t s);
+
+// The clip table of a ragged call, [off: B ints | len: B ints], on its way to the device: filled in an engine-owned
+// pinned buffer and copied stream-ordered.  The buffer is rewritten only after the previous call's copy has
+// completed (an event recorded behind it), so calls on different streams never race on it.  Stream capture of a
+// ragged call is not supported: M2S_E_STATE if `s` is capturing.
+class RaggedTable {
+ public:
+  RaggedTable() = default;
+  RaggedTable(const RaggedTable&) = delete;
+  RaggedTable& operator=(const RaggedTable&) = delete;
+  ~RaggedTable();
+  void upload(const int* lengths, int B, int* dev, hipStream_t s);
+
+ private:
+  int* host_ = nullptr;
+  size_t cap_ = 0;
+  hipEvent_t done_ = nullptr;
+};
+
 class Acoustic {
  public:
   Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int device);
@@ -139,8 +168,21 @@ class Acoustic {
   void effnet(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
               Workspace& ws, hipStream_t s);
   void bilstm(const float* feats, int B, int T, float* y, float* mel_norm, Workspace& ws, hipStream_t s);
+  // Ragged batches: packed feats (N, 208) / frames (N, H, W) of B clips, lengths[B] on the host; packed outputs
+  // y (N, hidden), mel_norm (N, n_mels).  The recurrence runs the dense kernels on a zero-padded (B, Tmax) block.
+  size_t ragged_workspace_bytes(const int* lengths, int B, int H, int W) const;
+  void bilstm_ragged(const float* feats, const int* lengths, int B, long N, float* y, float* mel_norm, Workspace& ws,
+                     hipStream_t s);
+  void forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm, void* ws,
+                      size_t wsb, hipStream_t s);
 
  private:
+  // the recurrence kernel for (B, T): the selection ladder shared by bilstm and bilstm_ragged.  seq_steps / rows:
+  // the recurrent steps and (b, t) rows that count as algorithmic work (a ragged call: the valid ones)
+  void lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps, double rows,
+                       hipStream_t s);
+  static size_t lstm_sync_bytes();
+  RaggedTable rtab_;
   struct Block {
     int type = 0;  // 0 cn, 1 er, 2 ir
     int stride = 1, cin = 0, cout = 0, mid = 0, rd = 0;
@@ -204,6 +246,13 @@ class Vocoder {
   // cast to the channel-last vocoder input (ln_buf: rows x cs(num_mels) x 4 bytes), then the generator.
   void forward_from_norm(const float* mel_norm, const float* mean, const float* std_, int B, int T, float* mel_db,
                          float* mel_log, void* ln_buf, float* wav, Workspace& ws, hipStream_t s);
+  // Ragged batches: packed layout-1 mel (N, num_mels) -> packed wav (N * hop); the generator runs on the padded
+  // (B, Tmax) block with zeros written where a short clip's consumers look past its end (run_t)
+  size_t ragged_workspace_bytes(const int* lengths, int B) const;
+  void forward_ragged(const float* mel, const int* lengths, int B, long N, float* wav, Workspace& ws, hipStream_t s);
+  // ... from packed mel_norm through the glue (packed mel_db / mel_log, may be null)
+  void forward_from_norm_ragged(const float* mel_norm, const float* mean, const float* std_, const int* lengths, int B,
+                                long N, float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
   size_t act_elems(int B, int T) const;
   bool mrf_fused_ = true;
   bool mrf_halo_ = true;   // split: C = 64 MRF convs with once-staged input rows (env M2S_MRF_HALO=0: conv_gemm)
@@ -215,8 +264,12 @@ class Vocoder {
   bool mrf_batch_ = true;  // split: resblocks of a conv_gemm MRF stage batched per launch (env M2S_MRF_BATCH=0 disables)  // bf16: fused ResBlock1 kernel for C in {32, 64} (env M2S_MRF_FUSED=0 disables)
 
  private:
+  // tab (ragged calls, with a clip shorter than Tn): the device clip table; the input S of every upsampler and of
+  // conv_post then gets the rows its consumer reads past a clip's end zeroed (launch_ragged_tail_mask)
   template <typename T>
-  void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s);
+  void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab = nullptr);
+  void ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
+                  float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
   template <typename T>
   void mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out, hipStream_t s);
   int act_buffers() const;  // activation buffers of act_elems() each in the workspace
@@ -245,6 +298,7 @@ class Vocoder {
   PConv pre_;
   std::vector<PConv> ups_;
   std::vector<RB> rbs_;
+  RaggedTable rtab_;
   size_t post_w_ = 0;
   float post_b_ = 0.f;
   int post_c_ = 0;

@@ -15,6 +15,7 @@
 //   hifigan_forward    Generator.forward                               models.py:113-131
 //   pipeline_forward   the no_grad section of main()                   run_mri_video_inference.py:222-242
 //   preprocess_frames  _preprocess_frame after the host decode         run_mri_video_inference.py:34-54
+//   *_ragged           the same forward passes over clips of different lengths, packed (include/m2s.h)
 //   cam_backbone       backbone(x) in train() (batch-statistics BN)    mri_gradcam_formant.py:153-160,221-225
 //   bilstm_train_*     model.rnn(seq) forward / autograd backward      mri_gradcam_formant.py:162-164,247-248
 //   linear_*           model.head(...) forward / autograd backward     mri_gradcam_formant.py:165
@@ -163,6 +164,85 @@ std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pipeline_forward(int6
                           mn.data_ptr<float>(), db.data_ptr<float>(), ln.data_ptr<float>(), wav.data_ptr<float>(),
                           ws.data_ptr(), ws.numel(), S()),
      "pipeline_forward");
+  return {mn, db, ln, wav};
+}
+
+// Ragged batches (include/m2s.h): packed tensors of N = sum(lengths) rows, clip b at rows off_b .. off_b + len_b - 1.
+// The C ABI validates lengths against the row count before any launch.
+std::vector<int> host_lengths(at::IntArrayRef lengths, const char* what) {
+  std::vector<int> l;
+  for (int64_t v : lengths) {
+    TORCH_CHECK(v >= INT32_MIN && v <= INT32_MAX, what, ": length out of range");
+    l.push_back((int)v);
+  }
+  return l;
+}
+
+// feats (N,208) -> (y (N,hidden), mel_norm (N,n_mels))
+std::tuple<at::Tensor, at::Tensor> bilstm_summerge_ragged(int64_t h, const at::Tensor& feats, at::IntArrayRef lengths,
+                                                          int64_t hidden, int64_t n_mels) {
+  TORCH_CHECK(feats.dim() == 2 && feats.size(1) == 208, "bilstm_summerge_ragged: feats must be packed (N,208)");
+  const Guard g(feats.device());
+  const at::Tensor x = f32_on_device(feats, "feats");
+  const std::vector<int> l = host_lengths(lengths, "bilstm_summerge_ragged");
+  const int N = x.size(0), B = (int)l.size();
+  at::Tensor y = at::empty({N, hidden}, x.options());
+  at::Tensor m = at::empty({N, n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_ragged_workspace_bytes(A(h), l.data(), B, 64, 64), x);
+  ok(m2s_bilstm_summerge_ragged(A(h), x.data_ptr<float>(), l.data(), B, N, y.data_ptr<float>(), m.data_ptr<float>(),
+                                ws.data_ptr(), ws.numel(), S()),
+     "bilstm_summerge_ragged");
+  return {y, m};
+}
+
+// frames (N,H,W) -> mel_norm (N,n_mels)
+at::Tensor acoustic_forward_ragged(int64_t h, const at::Tensor& frames, at::IntArrayRef lengths, int64_t n_mels) {
+  TORCH_CHECK(frames.dim() == 3, "acoustic_forward_ragged: frames must be packed (N,H,W)");
+  const Guard g(frames.device());
+  const at::Tensor x = f32_on_device(frames, "frames");
+  const std::vector<int> l = host_lengths(lengths, "acoustic_forward_ragged");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), B = (int)l.size();
+  at::Tensor out = at::empty({N, n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_ragged_workspace_bytes(A(h), l.data(), B, H, W), x);
+  ok(m2s_acoustic_forward_ragged(A(h), x.data_ptr<float>(), l.data(), B, N, H, W, out.data_ptr<float>(), ws.data_ptr(),
+                                 ws.numel(), S()),
+     "acoustic_forward_ragged");
+  return out;
+}
+
+// mel (N,num_mels) packed layout 1 -> wav (N*hop)
+at::Tensor hifigan_forward_ragged(int64_t v, const at::Tensor& mel, at::IntArrayRef lengths, int64_t hop) {
+  TORCH_CHECK(mel.dim() == 2, "hifigan_forward_ragged: mel must be packed (N,num_mels)");
+  const Guard g(mel.device());
+  const at::Tensor x = f32_on_device(mel, "mel");
+  const std::vector<int> l = host_lengths(lengths, "hifigan_forward_ragged");
+  const int N = x.size(0), B = (int)l.size();
+  at::Tensor wav = at::empty({(int64_t)N * hop}, x.options());
+  at::Tensor ws = workspace(m2s_vocoder_ragged_workspace_bytes(V(v), l.data(), B), x);
+  ok(m2s_vocoder_forward_ragged(V(v), x.data_ptr<float>(), l.data(), B, N, wav.data_ptr<float>(), ws.data_ptr(),
+                                ws.numel(), S()),
+     "hifigan_forward_ragged");
+  return wav;
+}
+
+// frames (N,H,W) -> (mel_norm, mel_db, mel_log (N,n_mels), wav (N*hop))
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pipeline_forward_ragged(
+    int64_t h, int64_t v, const at::Tensor& frames, at::IntArrayRef lengths, const at::Tensor& mean,
+    const at::Tensor& std_, int64_t n_mels, int64_t hop) {
+  TORCH_CHECK(frames.dim() == 3, "pipeline_forward_ragged: frames must be packed (N,H,W)");
+  const Guard g(frames.device());
+  const at::Tensor x = f32_on_device(frames, "frames");
+  const std::vector<int> l = host_lengths(lengths, "pipeline_forward_ragged");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), B = (int)l.size();
+  const at::Tensor mu = mean.to(x.device(), at::kFloat).contiguous(), sd = std_.to(x.device(), at::kFloat).contiguous();
+  TORCH_CHECK(mu.numel() == n_mels && sd.numel() == n_mels, "pipeline_forward_ragged: mean/std must have n_mels entries");
+  at::Tensor mn = at::empty({N, n_mels}, x.options()), db = at::empty_like(mn), ln = at::empty_like(mn);
+  at::Tensor wav = at::empty({(int64_t)N * hop}, x.options());
+  at::Tensor ws = workspace(m2s_pipeline_ragged_workspace_bytes(A(h), V(v), l.data(), B, H, W), x);
+  ok(m2s_pipeline_forward_ragged(A(h), V(v), x.data_ptr<float>(), l.data(), B, N, H, W, mu.data_ptr<float>(),
+                                 sd.data_ptr<float>(), mn.data_ptr<float>(), db.data_ptr<float>(), ln.data_ptr<float>(),
+                                 wav.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "pipeline_forward_ragged");
   return {mn, db, ln, wav};
 }
 
@@ -336,6 +416,11 @@ TORCH_LIBRARY(m2s, m) {
   m.def("hifigan_forward(int handle, Tensor mel, int layout, int hop) -> Tensor");
   m.def("pipeline_forward(int acoustic, int vocoder, Tensor frames, Tensor mean, Tensor std, int n_mels, int hop)"
         " -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("bilstm_summerge_ragged(int handle, Tensor feats, int[] lengths, int hidden, int n_mels) -> (Tensor, Tensor)");
+  m.def("acoustic_forward_ragged(int handle, Tensor frames, int[] lengths, int n_mels) -> Tensor");
+  m.def("hifigan_forward_ragged(int handle, Tensor mel, int[] lengths, int hop) -> Tensor");
+  m.def("pipeline_forward_ragged(int acoustic, int vocoder, Tensor frames, int[] lengths, Tensor mean, Tensor std,"
+        " int n_mels, int hop) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
   m.def("cam_backbone(int handle, Tensor frames) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -355,6 +440,10 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("mel_glue", &mel_glue);
   m.impl("hifigan_forward", &hifigan_forward);
   m.impl("pipeline_forward", &pipeline_forward);
+  m.impl("bilstm_summerge_ragged", &bilstm_summerge_ragged);
+  m.impl("acoustic_forward_ragged", &acoustic_forward_ragged);
+  m.impl("hifigan_forward_ragged", &hifigan_forward_ragged);
+  m.impl("pipeline_forward_ragged", &pipeline_forward_ragged);
   m.impl("preprocess_frames", &preprocess_frames);
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);

@@ -9,8 +9,8 @@ How it runs: every file in the directory is read up front, files of equal length
 together in one generator call (m2s/drivers.py), and the wavs are written afterwards.  Files that
 cannot be read or have the wrong number of bins are reported and skipped.  The weight norm is removed
 best-effort: the reference's ``generator.remove_weight_norm()`` raises on the never-normed conv_pre
-(models.py:94,139), which SURVEY.md §8f-3 lists as the thing to fix.  ``--dtype`` and ``--batch`` are
-additive.  There is no CPU path.
+(models.py:94,139), which SURVEY.md §8f-3 lists as the thing to fix.  ``--dtype``, ``--batch``, ``--ragged`` and
+``--max-pad-frac`` (files of different lengths in one call) are additive.  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -39,7 +39,12 @@ def parse_args(argv=None):
     p.add_argument("--checkpoint_file", required=True)
     p.add_argument("--dtype", choices=["bf16x3", "fp32", "bf16", "fp8"], default=None,
                    help="m2s compute dtype (default: M2S_DTYPE or bf16x3)")
-    p.add_argument("--batch", type=int, default=64, help="files of equal length per generator call")
+    p.add_argument("--batch", type=int, default=64, help="files per generator call (of equal length unless --ragged)")
+    p.add_argument("--ragged", action="store_true",
+                   help="batch files of different lengths into one call (padded inside the engine); default: one "
+                        "call per distinct length")
+    p.add_argument("--max-pad-frac", type=float, default=0.25,
+                   help="--ragged: largest fraction of padded frames a batch may carry")
     return p.parse_args(argv)
 
 
@@ -56,7 +61,7 @@ def main(argv=None):
     src = Path(args.input_mels_dir)
     jobs = [drivers.read_mel(drivers.Job(src / name, Path(name).stem), int(h.num_mels), conform=False)
             for name in sorted(os.listdir(src))]
-    drivers.vocode(gen, jobs, device, args.batch)
+    drivers.vocode(gen, jobs, device, args.batch, ragged=args.ragged, max_pad_frac=args.max_pad_frac)
 
     out_dir = Path(args.output_dir)
     out_dir.mkdir(parents=True, exist_ok=True)

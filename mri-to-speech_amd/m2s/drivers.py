@@ -6,7 +6,9 @@ The m2s command lines keep those scripts' flags and output files but run a diffe
 
 1. ``Job`` list: every input is read and conformed on the host first (unreadable / malformed inputs
    become failed jobs with the reason kept, the rest go on);
-2. ``plan_batches``: jobs whose arrays have the same shape form one batch (at most ``max_batch``);
+2. ``plan_batches``: jobs whose arrays have the same shape form one batch (at most ``max_batch``); or, with
+   ``--ragged``, ``plan_ragged_batches``: jobs of different lengths share a batch while its padding stays under
+   ``--max-pad-frac`` (a folder of utterances of arbitrary length otherwise degenerates to one clip per call);
 3. ``vocode`` / the acoustic model: each batch is ONE pinned host block, ONE H2D copy, ONE device call
    (``Generator.forward`` on (B, n_mels, T) runs ``torch.ops.m2s.hifigan_forward``), ONE D2H copy;
 4. the writers below produce the reference's files from the host results.
@@ -79,9 +81,85 @@ def run_batches(batches: Sequence[Sequence[Job]], fn: Callable[[torch.Tensor], t
             j.result = row
 
 
+def plan_ragged_batches(jobs: Iterable[Job], max_batch: int = 64, max_pad_frac: float = 0.25,
+                        time_axis: int = -1) -> List[List[Job]]:
+    """Group the runnable jobs into ragged batches: clips of different lengths (``array.shape[time_axis]``) share
+    one device call, which pads them to the longest inside the engine.
+
+    Jobs are sorted by length, longest first (stable), and a batch grows while it has fewer than ``max_batch``
+    clips and its padding stays bounded: ``1 - sum(len) / (B * Tmax) <= max_pad_frac``.  The padded steps cost
+    what valid ones do (the recurrence runs Tmax steps, the generator Tmax * hop rows per clip), so the bound
+    trades fewer, fuller calls against wasted rows; 0 reproduces grouping by equal length.  Jobs whose other axes
+    differ never share a batch."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be >= 1")
+    if not 0.0 <= max_pad_frac < 1.0:
+        raise ValueError("max_pad_frac must be in [0, 1)")
+    by_feat: Dict[tuple, List[Job]] = {}
+    for j in jobs:
+        if j.ok:
+            shape = list(j.array.shape)
+            shape.pop(time_axis)
+            by_feat.setdefault(tuple(shape), []).append(j)
+    batches: List[List[Job]] = []
+    for grp in by_feat.values():
+        grp = sorted(grp, key=lambda j: -j.array.shape[time_axis])  # sorted() is stable
+        cur: List[Job] = []
+        total = 0
+        for j in grp:
+            n = j.array.shape[time_axis]
+            tmax = cur[0].array.shape[time_axis] if cur else n
+            # valid / padded rows with j added (exact in integers: pad <= frac  <=>  valid >= (1 - frac) * padded)
+            if cur and (len(cur) >= max_batch or total + n < (1.0 - max_pad_frac) * (len(cur) + 1) * tmax):
+                batches.append(cur)
+                cur, total = [], 0
+            cur.append(j)
+            total += n
+        if cur:
+            batches.append(cur)
+    return batches
+
+
+def run_ragged_batches(batches: Sequence[Sequence[Job]], fn: Callable[[torch.Tensor, List[int]], torch.Tensor],
+                       device: torch.device, time_axis: int = -1) -> None:
+    """For every ragged batch: the clips, time axis first, concatenated into ONE pinned packed block -> one H2D
+    copy -> ``fn(packed, lengths)`` -> one D2H copy; ``fn`` returns a packed tensor whose axis 0 holds a whole
+    number of entries per time step (1 for mels, hop for a waveform), and every job gets its own rows as
+    ``result`` (time axis first).  A batch whose call raises marks each of its jobs failed, as ``run_batches``."""
+    for batch in batches:
+        rows = [np.moveaxis(np.asarray(j.array, np.float32), time_axis, 0) for j in batch]
+        lengths = [int(r.shape[0]) for r in rows]
+        host = torch.from_numpy(np.ascontiguousarray(np.concatenate(rows, axis=0), dtype=np.float32))
+        if device.type == "cuda":
+            host = host.pin_memory()
+        try:
+            with torch.no_grad():
+                out = fn(host.to(device, non_blocking=True), lengths).float().cpu().numpy()
+            per_step, rem = divmod(out.shape[0], sum(lengths))
+            if rem or per_step < 1:
+                raise ValueError(f"packed output of {out.shape[0]} rows for {sum(lengths)} time steps")
+        except Exception as e:  # noqa: BLE001 - reported per job
+            for j in batch:
+                j.error = f"{type(e).__name__}: {e}"
+            continue
+        off = 0
+        for j, n in zip(batch, lengths):
+            j.result = out[off * per_step:(off + n) * per_step]
+            off += n
+
+
+def _run_plan(jobs: Sequence[Job], fn, device: torch.device, max_batch: int, ragged: bool, max_pad_frac: float,
+              time_axis: int) -> None:
+    if ragged:
+        run_ragged_batches(plan_ragged_batches(jobs, max_batch, max_pad_frac, time_axis), fn, device, time_axis)
+    else:
+        run_batches(plan_batches(jobs, max_batch), fn, device)
+
+
 def run_sharded(jobs: Sequence[Job], fn: Callable[[torch.Tensor], torch.Tensor], device: torch.device,
                 lengths: Sequence[int], feat_shape: Sequence[int], max_batch: int = 16,
-                load: Optional[Callable[[Job], Job]] = None, time_axis: int = -1, per_step: int = 1) -> List[Job]:
+                load: Optional[Callable[[Job], Job]] = None, time_axis: int = -1, per_step: int = 1,
+                ragged: bool = False, max_pad_frac: float = 0.25, in_time_axis: int = -1) -> List[Job]:
     """``run_batches`` over one process per GPU (torch.distributed; a no-op wrapper at world 1).
 
     Every rank holds the same job list and ``lengths`` (time steps per job, e.g. frames), so every rank
@@ -93,14 +171,18 @@ def run_sharded(jobs: Sequence[Job], fn: Callable[[torch.Tensor], torch.Tensor],
     them; the other ranks return their own shard.
 
     A job's result is an array whose ``time_axis`` holds ``length * per_step`` steps and whose other
-    axes are ``feat_shape`` (an ln-mel: (n_mels, T), time_axis -1)."""
+    axes are ``feat_shape`` (an ln-mel: (n_mels, T), time_axis -1).
+
+    ``ragged``: a rank batches its shard with ``plan_ragged_batches`` (``max_pad_frac``; the jobs' input arrays
+    carry time on ``in_time_axis``) and ``fn`` is called as ``fn(packed, lengths)`` (``run_ragged_batches``); the
+    results, time axis first, must then be described by ``time_axis=0``."""
     import torch.distributed as dist
 
     from . import dp
 
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
         mine = [load(j) for j in jobs] if load else list(jobs)
-        run_batches(plan_batches(mine, max_batch), fn, device)
+        _run_plan(mine, fn, device, max_batch, ragged, max_pad_frac, in_time_axis)
         return list(jobs)
     world, rank = dist.get_world_size(), dist.get_rank()
     if len(lengths) != len(jobs):
@@ -109,7 +191,7 @@ def run_sharded(jobs: Sequence[Job], fn: Callable[[torch.Tensor], torch.Tensor],
     mine = [jobs[i] for i in shards[rank]]
     if load:
         mine = [load(j) for j in mine]
-    run_batches(plan_batches(mine, max_batch), fn, device)
+    _run_plan(mine, fn, device, max_batch, ragged, max_pad_frac, in_time_axis)
 
     comm = device if dist.get_backend() == "nccl" else torch.device("cpu")
     lens_by_rank = [[int(lengths[i]) for i in s] for s in shards]
@@ -143,8 +225,15 @@ def run_sharded(jobs: Sequence[Job], fn: Callable[[torch.Tensor], torch.Tensor],
     return list(jobs)
 
 
-def vocode(generator, jobs: Sequence[Job], device: torch.device, max_batch: int = 64) -> None:
-    """Every runnable job's (n_mels, T) ln-mel -> waveform (T * hop,) in ``job.result``."""
+def vocode(generator, jobs: Sequence[Job], device: torch.device, max_batch: int = 64, ragged: bool = False,
+           max_pad_frac: float = 0.25) -> None:
+    """Every runnable job's (n_mels, T) ln-mel -> waveform (T * hop,) in ``job.result``.  ``ragged``: mels of
+    different lengths share a call (``plan_ragged_batches``, ``Generator.forward_ragged``) instead of one call per
+    distinct shape."""
+    if ragged:
+        run_ragged_batches(plan_ragged_batches(jobs, max_batch, max_pad_frac, time_axis=-1),
+                           lambda x, lengths: generator.forward_ragged(x, lengths), device, time_axis=-1)
+        return
     run_batches(plan_batches(jobs, max_batch), lambda x: generator(x).reshape(x.shape[0], -1), device)
 
 

@@ -21,6 +21,8 @@ TORCH_LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libm2
 OPS = ("acoustic_forward", "effnet_forward", "effnet_features", "bilstm_summerge", "mel_glue", "hifigan_forward",
        "pipeline_forward", "preprocess_frames", "cam_backbone", "bilstm_train_forward", "bilstm_train_backward",
        "linear_forward", "linear_backward", "gap_forward", "gap_backward")
+# ragged batches: clips of different lengths in one call, packed tensors of sum(lengths) rows (include/m2s.h)
+RAGGED_OPS = ("bilstm_summerge_ragged", "acoustic_forward_ragged", "hifigan_forward_ragged", "pipeline_forward_ragged")
 
 # timm tf_efficientnetv2_b2 (features_only): stride and output channels of the stem (index 0) and of
 # the 29 blocks that follow (effnet_features' n_blocks = how many of them ran)
@@ -107,6 +109,25 @@ def _register_fakes():
         b, t = frames.shape[0], frames.shape[1]
         mel = [frames.new_empty((b, t, n_mels), dtype=torch.float32) for _ in range(3)]
         return mel[0], mel[1], mel[2], frames.new_empty((b, t * hop), dtype=torch.float32)
+
+    @f("m2s::bilstm_summerge_ragged")
+    def _bilstm_ragged(handle, feats, lengths, hidden, n_mels):
+        n = feats.shape[0]
+        return (feats.new_empty((n, hidden), dtype=torch.float32), feats.new_empty((n, n_mels), dtype=torch.float32))
+
+    @f("m2s::acoustic_forward_ragged")
+    def _acoustic_ragged(handle, frames, lengths, n_mels):
+        return frames.new_empty((frames.shape[0], n_mels), dtype=torch.float32)
+
+    @f("m2s::hifigan_forward_ragged")
+    def _hifigan_ragged(handle, mel, lengths, hop):
+        return mel.new_empty((mel.shape[0] * hop,), dtype=torch.float32)
+
+    @f("m2s::pipeline_forward_ragged")
+    def _pipeline_ragged(acoustic, vocoder, frames, lengths, mean, std, n_mels, hop):
+        n = frames.shape[0]
+        mel = [frames.new_empty((n, n_mels), dtype=torch.float32) for _ in range(3)]
+        return mel[0], mel[1], mel[2], frames.new_empty((n * hop,), dtype=torch.float32)
 
     @f("m2s::preprocess_frames")
     def _pre(frames):

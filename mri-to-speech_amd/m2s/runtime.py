@@ -9,6 +9,10 @@ allocate outputs and workspace with the torch caching allocator on the current H
 * ``VocoderEngine``   - packed HiFi-GAN generator (replaces Generator.forward, models.py:113-131)
 * ``mel_glue``        - denormalize_mel + dB -> ln-power (run_mri_video_inference.py:160-163,227-233)
 * ``Pipeline``        - frames -> mel_norm / mel_db / mel_log / wav in one call on one stream
+
+Every engine also has ``forward_ragged`` (and ``AcousticEngine.bilstm_ragged``): clips of different lengths in one
+call, as a packed tensor of ``sum(lengths)`` rows plus ``lengths``, or as a list of per-clip tensors; outputs are
+packed and ``split_packed`` returns the per-clip views.
 """
 from __future__ import annotations
 
@@ -35,6 +39,36 @@ def _as_f32(t: torch.Tensor, device: torch.device) -> torch.Tensor:
     if t.device != device:
         raise N.M2SError(f"input on {t.device}, engine on {device}")
     return t.to(torch.float32).contiguous()
+
+
+def _packed(x, lengths, device: torch.device, row_ndim: int):
+    """A ragged call's input as (packed fp32 tensor of sum(lengths) rows, lengths as a list of ints).  ``x`` is
+    either that packed tensor already or a list / tuple of per-clip tensors (clip b: ``lengths[b]`` rows of
+    ``row_ndim`` axes each; ``lengths`` may then be None), concatenated here."""
+    if isinstance(x, (list, tuple)):
+        if lengths is None:
+            lengths = [int(t.shape[0]) for t in x]
+        elif [int(t.shape[0]) for t in x] != [int(n) for n in lengths]:
+            raise N.M2SError("lengths do not match the per-clip tensors")
+        if not x:
+            raise N.M2SError("ragged call without clips")
+        x = torch.cat([_as_f32(t, device) for t in x], dim=0)
+    if lengths is None:
+        raise N.M2SError("a packed tensor needs its clip lengths")
+    lengths = [int(n) for n in lengths]
+    x = _as_f32(x, device)
+    if x.dim() != 1 + row_ndim:
+        raise N.M2SError(f"expected a packed tensor of {1 + row_ndim} axes, got {tuple(x.shape)}")
+    return x, lengths
+
+
+def split_packed(x: torch.Tensor, lengths, per_step: int = 1):
+    """Per-clip views of a packed tensor: clip b owns ``lengths[b] * per_step`` consecutive entries of axis 0
+    (``per_step`` = hop for a packed waveform)."""
+    sizes = [int(n) * int(per_step) for n in lengths]
+    if sum(sizes) != x.shape[0]:
+        raise ValueError(f"packed tensor has {x.shape[0]} rows, lengths give {sum(sizes)}")
+    return list(torch.split(x, sizes, dim=0))
 
 
 class AcousticEngine:
@@ -99,6 +133,21 @@ class AcousticEngine:
         """feats (B,T,208) -> (sum-merged BiLSTM output (B,T,H), head output (B,T,n_mels))."""
         return self.ops.bilstm_summerge(self.handle, _as_f32(feats, self.device), self.rnn_hidden, self.n_mels)
 
+    def forward_ragged(self, frames, lengths=None) -> torch.Tensor:
+        """Clips of different lengths in one call: packed frames (N,[1,]H,W), N = sum(lengths), or a list of
+        per-clip (T_b,[1,]H,W) tensors -> packed normalised mel (N,n_mels); ``split_packed`` gives the clips."""
+        if isinstance(frames, (list, tuple)):
+            frames = [f[:, 0] if f.dim() == 4 else f for f in frames]
+        elif frames.dim() == 4:
+            frames = frames[:, 0]
+        x, lengths = _packed(frames, lengths, self.device, 2)
+        return self.ops.acoustic_forward_ragged(self.handle, x, lengths, self.n_mels)
+
+    def bilstm_ragged(self, feats, lengths=None):
+        """packed feats (N,208) or a list of (T_b,208) -> packed (BiLSTM output (N,H), head output (N,n_mels))."""
+        x, lengths = _packed(feats, lengths, self.device, 1)
+        return self.ops.bilstm_summerge_ragged(self.handle, x, lengths, self.rnn_hidden, self.n_mels)
+
 
 class VocoderEngine:
     def __init__(self, state_dict: Dict, h, dtype: str = "bf16x3", device=None):
@@ -140,6 +189,14 @@ class VocoderEngine:
         if C_ != self.h["num_mels"]:
             raise N.M2SError(f"mel has {C_} bins, generator expects {self.h['num_mels']}")
         return self.ops.hifigan_forward(self.handle, x, int(layout), self.hop)
+
+    def forward_ragged(self, mel, lengths=None) -> torch.Tensor:
+        """Mels of different lengths in one call: packed (N,num_mels) ln-mel (time-major rows), or a list of
+        per-clip (T_b,num_mels) tensors -> packed waveform (N*hop,); ``split_packed(wav, lengths, hop)``."""
+        x, lengths = _packed(mel, lengths, self.device, 1)
+        if x.shape[1] != self.h["num_mels"]:
+            raise N.M2SError(f"mel has {x.shape[1]} bins, generator expects {self.h['num_mels']}")
+        return self.ops.hifigan_forward_ragged(self.handle, x, lengths, self.hop)
 
 
 def mel_glue(mel_norm: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):
@@ -185,3 +242,15 @@ class Pipeline:
                     out[k].copy_(v)
             return out
         return res
+
+    def forward_ragged(self, frames, lengths=None):
+        """Clips of different lengths in one call: packed frames (N,[1,]H,W) or a list of per-clip tensors ->
+        dict of packed mel_norm / mel_db / mel_log (N,n_mels) and wav (N*hop,)."""
+        if isinstance(frames, (list, tuple)):
+            frames = [f[:, 0] if f.dim() == 4 else f for f in frames]
+        elif frames.dim() == 4:
+            frames = frames[:, 0]
+        x, lengths = _packed(frames, lengths, self.device, 2)
+        mn, db, ln, wav = self.ac.ops.pipeline_forward_ragged(self.ac.handle, self.voc.handle, x, lengths, self.mean,
+                                                              self.std, self.ac.n_mels, self.voc.hop)
+        return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": wav}

@@ -11,8 +11,8 @@ duration_seconds, sampling_rate), with a trailing ``_mel`` dropped from ``base``
 reported and the run continues.
 
 How it runs: all inputs are read and conformed first, equal-length mels share one generator call
-(m2s/drivers.py), outputs are written afterwards.  ``--dtype`` / ``--batch`` are additive; there is no
-CPU path.
+(m2s/drivers.py), outputs are written afterwards.  ``--dtype`` / ``--batch`` are additive, as are ``--ragged`` /
+``--max-pad-frac`` (mels of different lengths in one call); there is no CPU path.
 """
 from __future__ import annotations
 
@@ -85,7 +85,12 @@ def parse_args(argv=None):
     p.add_argument("--max_files", default=20, type=int, help="Maximum number of files to process (if directory)")
     p.add_argument("--dtype", choices=["bf16x3", "fp32", "bf16", "fp8"], default=None,
                    help="m2s compute dtype (default: M2S_DTYPE or bf16x3)")
-    p.add_argument("--batch", type=int, default=64, help="mels of equal length per generator call")
+    p.add_argument("--batch", type=int, default=64, help="mels per generator call (of equal length unless --ragged)")
+    p.add_argument("--ragged", action="store_true",
+                   help="batch mels of different lengths into one call (padded inside the engine); default: one "
+                        "call per distinct length")
+    p.add_argument("--max-pad-frac", type=float, default=0.25,
+                   help="--ragged: largest fraction of padded frames a batch may carry")
     return p.parse_args(argv)
 
 
@@ -106,7 +111,7 @@ def main(argv=None):
 
     sr = int(h.sampling_rate)
     jobs = [drivers.read_mel(drivers.Job(p, stem_of(p)), int(h.num_mels)) for p in inputs]
-    drivers.vocode(gen, jobs, device, args.batch)
+    drivers.vocode(gen, jobs, device, args.batch, ragged=args.ragged, max_pad_frac=args.max_pad_frac)
 
     done = []
     for job in jobs:

@@ -163,6 +163,15 @@ class Generator(nn.Module):
             return self._engine(x.device).forward(x.unsqueeze(0), layout=0)[0]
         return self._engine(x.device).forward(x, layout=0)
 
+    def forward_ragged(self, mel, lengths=None):
+        """Mels of different lengths in one call: packed time-major ln-mel (N, num_mels) with ``lengths``,
+        N = sum(lengths), or a list of per-clip (T_b, num_mels) tensors -> packed waveform (N * hop,); each
+        clip's samples are what ``forward`` gives for that mel alone (m2s.runtime.VocoderEngine.forward_ragged)."""
+        first = mel[0] if isinstance(mel, (list, tuple)) else mel
+        if torch.is_grad_enabled() and first.requires_grad:
+            raise NotImplementedError("m2s generator has no autograd; run under torch.no_grad()")
+        return self._engine(first.device).forward_ragged(mel, lengths)
+
     def remove_weight_norm(self):
         """Mirrors models.py:133-140, including its failure on the never-normed conv_pre."""
         print("Removing weight norm...")

@@ -285,6 +285,14 @@ class OTNLikeCNNBiLSTM(nn.Module):
         self._check_grad(x)
         return self._engine(x.device).forward(x)
 
+    def forward_ragged(self, frames, lengths=None) -> torch.Tensor:
+        """Clips of different lengths in one fused call (eval only): packed frames (N,[1,]H,W) with ``lengths``,
+        N = sum(lengths), or a list of per-clip (T_b,[1,]H,W) tensors -> packed (N,n_mels); each clip's rows are
+        what ``forward`` gives for that clip alone (m2s.runtime.AcousticEngine.forward_ragged)."""
+        first = frames[0] if isinstance(frames, (list, tuple)) else frames
+        self._check_grad(first)
+        return self._engine(first.device).forward_ragged(frames, lengths)
+
 
 def build_acoustic_model(n_mels: int = 64, cnn_pretrained: bool = False, rnn_hidden: int = 640,
                          dropout: float = 0.5, use_checkpoint: bool = False, ckpt_segments: int = 2,

@@ -10,7 +10,8 @@ float32 per sample (meldataset.py:195-218 consumes them), skips existing outputs
 from ``--scaler_json``.
 
 How it runs: the sample list is read first, clips with the same frame-stack shape go through the
-acoustic model together (``--batch`` per call, m2s/drivers.py), and the de-normalisation
+acoustic model together (``--batch`` per call, m2s/drivers.py; with ``--ragged`` clips of different lengths
+share a call too, ``--max-pad-frac`` bounding the padding), and the de-normalisation
 y*std+mean -> 10^(x/10) -> clamp(1e-5) -> ln runs on the device (``torch.ops.m2s.mel_glue``) before
 the one copy back.  ``--cpu`` is refused: there is no CPU path.
 
@@ -163,8 +164,19 @@ def _export(args, out_dir, mean, std, world, rank, local) -> list:
         _, ln = mel_glue(model(frames[:, :, None]), mean, std)
         return ln.transpose(1, 2)
 
-    drivers.run_sharded(jobs, mels, device, lengths=[j.length for j in jobs], feat_shape=(mean.numel(),),
-                        max_batch=args.batch, load=load_frames, time_axis=-1)
+    def mels_ragged(frames, lengths):  # packed (N,H,W) -> packed (N, n_mels) ln-mel, time first
+        return mel_glue(model.forward_ragged(frames, lengths), mean, std)[1]
+
+    if args.ragged:  # clips of different lengths share a call; a job's result is (T, n_mels)
+        drivers.run_sharded(jobs, mels_ragged, device, lengths=[j.length for j in jobs], feat_shape=(mean.numel(),),
+                            max_batch=args.batch, load=load_frames, time_axis=0, ragged=True,
+                            max_pad_frac=args.max_pad_frac, in_time_axis=0)
+        for job in jobs:
+            if job.result is not None:
+                job.result = np.ascontiguousarray(job.result.T)
+    else:
+        drivers.run_sharded(jobs, mels, device, lengths=[j.length for j in jobs], feat_shape=(mean.numel(),),
+                            max_batch=args.batch, load=load_frames, time_axis=-1)
     if rank != 0:
         return []
     written = []
@@ -202,7 +214,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     p.add_argument("--overwrite", action="store_true", help="Regenerate files even if they already exist.")
     p.add_argument("--dtype", choices=["bf16x3", "fp32", "bf16", "fp8"], default=None,
                    help="m2s compute dtype (default: M2S_DTYPE or bf16x3)")
-    p.add_argument("--batch", type=int, default=16, help="clips of equal length per forward call")
+    p.add_argument("--batch", type=int, default=16, help="clips per forward call (of equal length unless --ragged)")
+    p.add_argument("--ragged", action="store_true",
+                   help="batch clips of different lengths into one call (padded inside the engine); default: one "
+                        "call per distinct clip shape")
+    p.add_argument("--max-pad-frac", type=float, default=0.25,
+                   help="--ragged: largest fraction of padded frames a batch may carry")
     return p.parse_args(argv)
 
 
