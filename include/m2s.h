@@ -106,6 +106,23 @@ int m2s_acoustic_set_lstm_spin_limit(m2s_acoustic* m, unsigned polls);
  * weight-slot wait, se_ws FULL / FREE waits; default 2^20) before it times out; 0 makes every such wait time out.
  * A timeout poisons the affected outputs with NaN and is reported by m2s_acoustic_status. */
 int m2s_acoustic_set_ws_spin_limit(m2s_acoustic* m, unsigned polls);
+/* Workspace contract, for every `ws` / `ws_bytes` pair and every *_workspace_bytes query of this header
+ * (tests/test_gpu_workspace.py holds each entry point to it):
+ *   - `ws` is caller-owned device memory, 256-byte aligned.  Its contents on entry are arbitrary: no call reads a
+ *     workspace byte it has not written itself during that call, so NaN bit patterns, random bytes or the leftovers
+ *     of any earlier call give bit-identical outputs.
+ *   - Nothing in the workspace persists between calls: it may be reused, overwritten or freed once the stream has
+ *     passed the call.  What an engine keeps across calls (the BiLSTM hand-off tags) it owns itself.
+ *   - The size a query reports is sufficient, and it is exact to its 256-byte granule for the call the query is named
+ *     after (m2s_acoustic_forward, m2s_vocoder_forward, m2s_pipeline_forward, their *_ragged forms,
+ *     m2s_cam_backbone, m2s_bilstm_train_backward): 256 bytes less is refused with M2S_E_ARG, nothing outside the
+ *     caller's buffers is written, and the engine stays usable.  The calls without a query of their own take the
+ *     enclosing call's and use a part of it: m2s_effnet_forward / m2s_effnet_probe on N frames that of
+ *     m2s_acoustic_workspace_bytes(m, N, 1, H, W); m2s_bilstm_summerge that of (m, B, T, H, W) for any valid frame
+ *     size, e.g. 64 x 64; m2s_bilstm_summerge_ragged that of m2s_acoustic_ragged_workspace_bytes likewise;
+ *     m2s_bilstm_train_forward that of m2s_bilstm_train_workspace_bytes.
+ *   - Every output is written completely, each element from this call's inputs alone, and no byte outside the
+ *     outputs and the workspace is written: outputs have exactly their documented size, with no slack. */
 size_t m2s_acoustic_workspace_bytes(const m2s_acoustic* m, int B, int T, int H, int W);
 /* frames (B,T,H,W) fp32 in [0,1] -> mel_norm (B,T,n_mels) fp32. */
 int m2s_acoustic_forward(m2s_acoustic* m, const float* frames, int B, int T, int H, int W, float* mel_norm,
