@@ -28,6 +28,10 @@
  *                          scripts/mri_gradcam_formant.py:165
  *   m2s_gap_*              GlobalAvgPool / feats.mean((2,3)) forward + backward
  *                          mri_acoustic_model.py:15-18, scripts/mri_gradcam_formant.py:162
+ *   m2s_melspec_*          mel_spectrogram (reflect pad, periodic-Hann STFT, magnitude, mel, ln)
+ *                          meldataset.py:57-93, as inference.py:25-26 and train.py:228-252 call it; and
+ *                          pre_emphasis + compute_mel_db up to the dB map (the caller supplies the mel basis)
+ *                          mri2speech_code/preprocess_rtmri_data.py:37-43,121-147
  */
 #ifndef M2S_H_
 #define M2S_H_
@@ -252,6 +256,38 @@ int m2s_linear_backward(const float* dy, const float* x, int rows, int in, int o
 int m2s_gap_forward(const float* x, int64_t nc, int p, float* y, void* stream);
 int m2s_gap_backward(const float* dy, int64_t nc, int p, float* dx, void* stream);
 
+/* ------------------------------------------------ analysis: waveform -> mel ---- */
+/* The opposite direction of the vocoder: wav (B,L) -> mel, exact fp32 (an f32-MFMA DFT with float64-built
+ * tables, the spectrum kept on chip; DESIGN.md "Mel-spectrogram front end").  The mel basis is the caller's: the
+ * engine does not know what a mel scale is. */
+typedef struct m2s_melspec_cfg {
+  int n_fft;     /* even, 16..4096 */
+  int hop;       /* >= 1 (<= n_fft with pad = 1) */
+  int win;       /* 1..n_fft, periodic Hann centred in the frame */
+  int n_mels;    /* 1..128 */
+  int pad;       /* 0 none: T = 1 + (L - n_fft)/hop;  1 reflect by (n_fft - hop)/2 (integer division) each side */
+  int power;     /* 1: sqrt(re^2 + im^2 + 1e-9);  2: re^2 + im^2 */
+  int out;       /* 0 ln(max(m,1e-5));  1 10*log10(max(m,1e-10));  2 linear */
+  float preemph; /* 0 off; y[0] = x[0], y[n] = x[n] - c*x[n-1], applied before padding */
+} m2s_melspec_cfg;
+typedef struct m2s_melspec m2s_melspec;
+/* mel_basis_host (n_mels, n_fft/2+1) fp32 row-major HOST memory, copied.  M2S_E_ARG for a config outside the
+ * ranges above.  Synchronous. */
+int m2s_melspec_create(const m2s_melspec_cfg* cfg, const float* mel_basis_host, int device, m2s_melspec** out);
+void m2s_melspec_destroy(m2s_melspec* m);
+/* the config's n_mels (what a caller holding only the handle needs to size `mel`) */
+int m2s_melspec_n_mels(const m2s_melspec* m);
+/* T for clips of L samples (trailing samples that do not fill a frame are ignored), or 0 where forward refuses L:
+ * L < n_fft with pad = 0; a reflect pad >= L or a padded length < n_fft with pad = 1. */
+int m2s_melspec_frames(const m2s_melspec* m, int L);
+/* 0 for arguments forward would reject.  The workspace holds the partial mel sums over the bins; how many there
+ * are per frame, and so the order in which a frame is summed, follows from the config alone, never from B or L. */
+size_t m2s_melspec_workspace_bytes(const m2s_melspec* m, int B, int L);
+/* wav (B,L) fp32 -> mel fp32, layout 0 = (B,n_mels,T), 1 = (B,T,n_mels).  M2S_E_ARG, before any launch, if
+ * B < 1 or m2s_melspec_frames(m, L) is 0.  A clip's result does not depend on B or on its place in the batch. */
+int m2s_melspec_forward(m2s_melspec* m, const float* wav, int B, int L, float* mel, int layout, void* ws,
+                        size_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------------------- profiling ---- */
 /* While enabled, every kernel launch is bracketed by HIP events on its own stream. */
 typedef struct m2s_prof_stat {
@@ -265,7 +301,7 @@ int m2s_prof_enable(int on);
 /* Synchronises on the recorded events, writes up to `max` stats, clears the record. */
 int m2s_prof_collect(m2s_prof_stat* out, int max, int* n_out);
 /* One recorded launch, in launch order: its kernel name, the stage of the path it belongs to
- * ("cnn", "bilstm", "head", "glue", "voc_pre", "ups_c<C>", "mrf_c<C>", "voc_post"; bench.py's
+ * ("cnn", "bilstm", "head", "glue", "voc_pre", "ups_c<C>", "mrf_c<C>", "voc_post", "melspec"; bench.py's
  * roofline.stages), event time, algorithmic FLOPs and bytes (compulsory in + out + weights of the
  * operation the kernel implements), and spill_bytes: an intermediate map the kernel writes only for a
  * later kernel of the same operation to read back (ir_ws: the IR block's expanded depthwise map, which

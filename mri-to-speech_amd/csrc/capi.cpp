@@ -5,6 +5,7 @@
 
 #include "../../include/m2s.h"
 #include "cam.hpp"
+#include "melspec.hpp"
 #include "model.hpp"
 
 struct m2s_acoustic {
@@ -15,6 +16,10 @@ struct m2s_vocoder {
 };
 struct m2s_cam {
   m2s::CamBackbone impl;
+};
+struct m2s_melspec {
+  m2s::MelSpec impl;
+  m2s_melspec(const m2s_melspec_cfg& c, const float* basis, int device) : impl(c, basis, device) {}
 };
 
 extern "C" int m2s_prof_enable_impl(int on);
@@ -444,6 +449,38 @@ int m2s_gap_backward(const float* dy, int64_t nc, int p, float* dx, void* stream
   return guarded([&] {
     M2S_CHECK(dy && dx && nc >= 0 && p > 0, "bad argument");
     m2s::launch_gap_nchw_bwd(dy, nc, p, dx, S(stream));
+  });
+}
+
+int m2s_melspec_create(const m2s_melspec_cfg* cfg, const float* mel_basis_host, int device, m2s_melspec** out) {
+  return guarded([&] {
+    M2S_CHECK(cfg && mel_basis_host && out, "null argument");
+    check_device(device);
+    DeviceGuard g(device);
+    *out = new m2s_melspec(*cfg, mel_basis_host, device);
+  });
+}
+
+void m2s_melspec_destroy(m2s_melspec* m) {
+  if (!m) return;
+  guarded([&] {
+    DeviceGuard g(m->impl.device());
+    delete m;
+  });
+}
+
+int m2s_melspec_n_mels(const m2s_melspec* m) { return m ? m->impl.n_mels() : 0; }
+
+int m2s_melspec_frames(const m2s_melspec* m, int L) { return m ? m->impl.frames(L) : 0; }
+
+size_t m2s_melspec_workspace_bytes(const m2s_melspec* m, int B, int L) { return m ? m->impl.workspace_bytes(B, L) : 0; }
+
+int m2s_melspec_forward(m2s_melspec* m, const float* wav, int B, int L, float* mel, int layout, void* ws,
+                        size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && wav && mel && ws, "null argument");
+    DeviceGuard g(m->impl.device());
+    m->impl.forward(wav, B, L, mel, layout, ws, ws_bytes, S(stream));
   });
 }
 

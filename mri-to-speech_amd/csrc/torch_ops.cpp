@@ -20,6 +20,8 @@
 //   bilstm_train_*     model.rnn(seq) forward / autograd backward      mri_gradcam_formant.py:162-164,247-248
 //   linear_*           model.head(...) forward / autograd backward     mri_gradcam_formant.py:165
 //   gap_*              feats.mean(dim=(2,3)) forward / backward        mri_gradcam_formant.py:162
+//   mel_spectrogram    mel_spectrogram / compute_mel_db up to the dB map   meldataset.py:57-93,
+//                      mri2speech_code/preprocess_rtmri_data.py:121-147
 #include <ATen/ATen.h>
 #include <ATen/hip/impl/HIPGuardImplMasqueradingAsCUDA.h>
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
@@ -405,9 +407,29 @@ at::Tensor gap_backward(const at::Tensor& dy_, int64_t h, int64_t w) {
   return dx;
 }
 
+// wav (B,L) -> mel (B,n_mels,T) [layout 0] or (B,T,n_mels) [layout 1]; handle = an m2s_melspec*, whose n_mels
+// and frame count are asked of the engine itself
+at::Tensor mel_spectrogram(int64_t h, const at::Tensor& wav, int64_t layout) {
+  TORCH_CHECK(h != 0, "null melspec handle");
+  TORCH_CHECK(wav.dim() == 2 && (layout == 0 || layout == 1), "mel_spectrogram: wav must be (B,L), layout 0 or 1");
+  m2s_melspec* m = reinterpret_cast<m2s_melspec*>(h);
+  const Guard g(wav.device());
+  const at::Tensor x = f32_on_device(wav, "wav");
+  TORCH_CHECK(x.size(1) <= INT32_MAX && x.size(0) <= INT32_MAX, "mel_spectrogram: wav too large");
+  const int B = x.size(0), L = x.size(1);
+  const int T = m2s_melspec_frames(m, L), nm = m2s_melspec_n_mels(m);
+  TORCH_CHECK(B >= 1 && T >= 1, "mel_spectrogram: B = ", B, ", L = ", L, ": no frame (clip shorter than n_fft, or than the reflect pad)");
+  at::Tensor out = layout == 0 ? at::empty({B, nm, T}, x.options()) : at::empty({B, T, nm}, x.options());
+  at::Tensor ws = workspace(m2s_melspec_workspace_bytes(m, B, L), x);
+  ok(m2s_melspec_forward(m, x.data_ptr<float>(), B, L, out.data_ptr<float>(), (int)layout, ws.data_ptr(), ws.numel(), S()),
+     "mel_spectrogram");
+  return out;
+}
+
 }  // namespace
 
 TORCH_LIBRARY(m2s, m) {
+  m.def("mel_spectrogram(int handle, Tensor wav, int layout) -> Tensor");
   m.def("acoustic_forward(int handle, Tensor frames, int n_mels) -> Tensor");
   m.def("effnet_forward(int handle, Tensor frames) -> Tensor");
   m.def("effnet_features(int handle, Tensor frames, int n_blocks) -> Tensor");
@@ -452,4 +474,5 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("linear_backward", &linear_backward);
   m.impl("gap_forward", &gap_forward);
   m.impl("gap_backward", &gap_backward);
+  m.impl("mel_spectrogram", &mel_spectrogram);
 }

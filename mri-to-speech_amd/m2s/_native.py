@@ -39,6 +39,11 @@ class HifiganH(C.Structure):
                 ("resblock_dilation_sizes", (C.c_int * 8) * 8)]
 
 
+class MelspecCfg(C.Structure):
+    _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("win", C.c_int), ("n_mels", C.c_int), ("pad", C.c_int),
+                ("power", C.c_int), ("out", C.c_int), ("preemph", C.c_float)]
+
+
 class ProfStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -106,6 +111,12 @@ def lib():
         "m2s_linear_backward": (i, [fp, fp, i, i, i, fp, fp, fp, fp, vp]),
         "m2s_gap_forward": (i, [fp, C.c_int64, i, fp, vp]),
         "m2s_gap_backward": (i, [fp, C.c_int64, i, fp, vp]),
+        "m2s_melspec_create": (i, [C.POINTER(MelspecCfg), fp, i, C.POINTER(vp)]),
+        "m2s_melspec_destroy": (None, [vp]),
+        "m2s_melspec_n_mels": (i, [vp]),
+        "m2s_melspec_frames": (i, [vp, i]),
+        "m2s_melspec_workspace_bytes": (sz, [vp, i, i]),
+        "m2s_melspec_forward": (i, [vp, fp, i, i, fp, i, vp, sz, vp]),
         "m2s_prof_enable": (i, [i]),
         "m2s_prof_collect": (i, [C.POINTER(ProfStat), i, C.POINTER(i)]),
         "m2s_prof_launches": (i, [C.POINTER(ProfLaunch), i, C.POINTER(i)]),
@@ -140,6 +151,8 @@ def exported_symbols() -> List[str]:
                         "m2s_cam_bn_channels", "m2s_cam_workspace_bytes", "m2s_cam_backbone",
                         "m2s_bilstm_train_workspace_bytes", "m2s_bilstm_train_forward", "m2s_bilstm_train_backward",
                         "m2s_linear_forward", "m2s_linear_backward", "m2s_gap_forward", "m2s_gap_backward",
+                        "m2s_melspec_create", "m2s_melspec_destroy", "m2s_melspec_n_mels", "m2s_melspec_frames",
+                        "m2s_melspec_workspace_bytes", "m2s_melspec_forward",
                         "m2s_prof_enable", "m2s_prof_collect", "m2s_prof_launches")]
 
 

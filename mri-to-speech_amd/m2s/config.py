@@ -21,6 +21,10 @@ HIFIGAN_H = {
     "sampling_rate": 11413,
 }
 
+# The analysis half of the same config (config_custom.json:48-53): what meldataset.mel_spectrogram is called
+# with.  Kept apart from HIFIGAN_H, which holds only what the Generator reads.
+HIFIGAN_MEL = {"n_fft": 2048, "win_size": 2048, "fmin": 0, "fmax": 8000}
+
 ACOUSTIC_DEFAULTS = dict(n_mels=64, cnn_pretrained=False, rnn_hidden=640, dropout=0.5,
                          use_checkpoint=False, ckpt_segments=2, use_reentrant=False)
 

@@ -23,6 +23,8 @@ OPS = ("acoustic_forward", "effnet_forward", "effnet_features", "bilstm_summerge
        "linear_forward", "linear_backward", "gap_forward", "gap_backward")
 # ragged batches: clips of different lengths in one call, packed tensors of sum(lengths) rows (include/m2s.h)
 RAGGED_OPS = ("bilstm_summerge_ragged", "acoustic_forward_ragged", "hifigan_forward_ragged", "pipeline_forward_ragged")
+# analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
+ANALYSIS_OPS = ("mel_spectrogram",)
 
 # timm tf_efficientnetv2_b2 (features_only): stride and output channels of the stem (index 0) and of
 # the 29 blocks that follow (effnet_features' n_blocks = how many of them ran)
@@ -49,6 +51,25 @@ def cam_bn_layers():
 CAM_BN_STATS = 2 * sum(c for _, c, _ in cam_bn_layers())
 
 _loaded = False
+
+# m2s_melspec* handle -> (n_fft, hop, reflect pad per side, n_mels): what mel_spectrogram's fake kernel needs to
+# shape its output without touching the device; MelSpectrogram registers itself here
+_MELSPEC_GEOMETRY = {}
+
+
+def register_melspec(handle: int, n_fft: int, hop: int, pad: int, n_mels: int) -> None:
+    _MELSPEC_GEOMETRY[int(handle)] = (int(n_fft), int(hop), int(pad), int(n_mels))
+
+
+def unregister_melspec(handle: int) -> None:
+    _MELSPEC_GEOMETRY.pop(int(handle), None)
+
+
+def melspec_geometry(handle: int):
+    try:
+        return _MELSPEC_GEOMETRY[int(handle)]
+    except KeyError:
+        raise M2SError(f"mel_spectrogram: handle {handle:#x} was not created by m2s.melspec.MelSpectrogram") from None
 
 
 def load():
@@ -128,6 +149,13 @@ def _register_fakes():
         n = frames.shape[0]
         mel = [frames.new_empty((n, n_mels), dtype=torch.float32) for _ in range(3)]
         return mel[0], mel[1], mel[2], frames.new_empty((n * hop,), dtype=torch.float32)
+
+    @f("m2s::mel_spectrogram")
+    def _melspec(handle, wav, layout):
+        n_fft, hop, pad, nm = melspec_geometry(handle)
+        t = (wav.shape[1] + 2 * pad - n_fft) // hop + 1  # shape arithmetic only: stays symbolic under tracing
+        shape = (wav.shape[0], nm, t) if layout == 0 else (wav.shape[0], t, nm)
+        return wav.new_empty(shape, dtype=torch.float32)
 
     @f("m2s::preprocess_frames")
     def _pre(frames):

@@ -10,6 +10,8 @@ allocate outputs and workspace with the torch caching allocator on the current H
 * ``mel_glue``        - denormalize_mel + dB -> ln-power (run_mri_video_inference.py:160-163,227-233)
 * ``Pipeline``        - frames -> mel_norm / mel_db / mel_log / wav in one call on one stream
 
+The opposite direction, waveform -> mel, is ``m2s.melspec.MelSpectrogram``.
+
 Every engine also has ``forward_ragged`` (and ``AcousticEngine.bilstm_ragged``): clips of different lengths in one
 call, as a packed tensor of ``sum(lengths)`` rows plus ``lengths``, or as a list of per-clip tensors; outputs are
 packed and ``split_packed`` returns the per-clip views.
@@ -242,6 +244,15 @@ class Pipeline:
                     out[k].copy_(v)
             return out
         return res
+
+    def roundtrip_error(self, out: Dict[str, torch.Tensor], h=None) -> torch.Tensor:
+        """The HiFi-GAN validation metric (train.py:228-252) of a ``forward`` result: per clip, the mean
+        |mel(out["wav"]) - out["mel_log"]|, with the mel taken on the device (m2s/melspec.py).  ``h``: the analysis
+        config (n_fft, win_size, fmin, fmax, ...); default: the vocoder's own config over config.HIFIGAN_MEL."""
+        from .config import HIFIGAN_MEL
+        from .melspec import mel_l1
+        cfg = {**HIFIGAN_MEL, **self.voc.h} if h is None else h
+        return mel_l1(out["wav"], out["mel_log"], cfg, layout=1)
 
     def forward_ragged(self, frames, lengths=None):
         """Clips of different lengths in one call: packed frames (N,[1,]H,W) or a list of per-clip tensors ->
