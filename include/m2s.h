@@ -217,6 +217,41 @@ int m2s_pipeline_forward_ragged(m2s_acoustic* m, m2s_vocoder* v, const float* fr
                                 int rows, int H, int W, const float* mean, const float* std, float* mel_norm,
                                 float* mel_db, float* mel_log, float* wav, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ windowed inference ---- */
+/* The acoustic checkpoint is trained on overlapping windows of ref_frames (default 4) frames, stride 1, with the
+ * BiLSTM starting from zero state in both directions on every window; the reference's own inference (and every
+ * entry point above) runs the recurrence over the whole clip.  These ADDITIVE calls run it over sliding windows
+ * instead (DESIGN.md "Windowed acoustic inference").  M(x) = the per-clip forward on k rows (projection, BiLSTM
+ * from zero state, sum merge, head), W = `window` (1..16), inputs packed as in the ragged calls:
+ *   M2S_WINDOW_LATEST  out[t] = M(x[max(0, t - W + 1) .. t])[last]: causal, the window ENDING at t; the first W - 1
+ *                      frames of a clip use the truncated window that starts at the clip's first row
+ *   M2S_WINDOW_MEAN    len <= W: out = M(x); otherwise out[t] = the mean, over the full windows w = 0 .. len - W that
+ *                      contain t, of M(x[w .. w + W - 1])[t - w] (a fixed-order average of the merged hidden rows,
+ *                      then the head)
+ * `context` (LATEST only, may be NULL) is a HOST array of B integers, 0 <= context[b] <= min(W - 1, lengths[b] - 1):
+ * the first context[b] rows of clip b are history that windows reach into but that get no output row, so the outputs
+ * hold rows = sum(lengths[b] - context[b]) packed rows in clip order.  That is the whole streaming state: keep the
+ * last W - 1 FEATURE rows of a stream, prepend them to the next chunk, and the rows are bit-identical to one call
+ * over the concatenation.  No hidden state crosses a call, and a row's bits do not depend on what else is in the
+ * batch.  The recurrence is a launch per step (lstm_window.hip): no cross-workgroup waits, nothing that can time
+ * out, and the asynchronous error word is not involved.
+ * M2S_E_ARG, before any launch: window outside 1..16, an unknown merge, a context with MEAN, a context entry out of
+ * range, rnn_hidden != 640, and the ragged calls' argument errors.  M2S_E_STATE if `stream` is capturing (the clip
+ * table is staged per call, as in the ragged calls).  The workspace contract above applies as written. */
+enum m2s_window_merge { M2S_WINDOW_LATEST = 0, M2S_WINDOW_MEAN = 1 };
+/* Exact size for m2s_acoustic_forward_windowed on (H, W) frames; with H = W = 0 the exact size for
+ * m2s_bilstm_windowed alone.  0 for arguments the calls would reject. */
+size_t m2s_acoustic_windowed_workspace_bytes(const m2s_acoustic* m, const int* lengths, const int* context, int B,
+                                             int H, int W, int window, int merge);
+/* feats (rows,208) -> y (out_rows,rnn_hidden) merged hidden rows (may be NULL) and mel_norm (out_rows,n_mels) (may
+ * be NULL), out_rows = rows - sum(context). */
+int m2s_bilstm_windowed(m2s_acoustic* m, const float* feats, const int* lengths, const int* context, int B, int rows,
+                        int window, int merge, float* y, float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+/* frames (rows,H,W) fp32 in [0,1] -> mel_norm (out_rows,n_mels).  The CNN runs once per frame row. */
+int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const int* lengths, const int* context, int B,
+                                  int rows, int H, int W, int window, int merge, float* mel_norm, void* ws,
+                                  size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------- Grad-CAM (autograd) path ---- */
 /* compute_gradcam (scripts/mri_gradcam_formant.py:203-279) runs the model in train() and back-
  * propagates a mel-band power to the last feature map.  These entry points are that path, exact

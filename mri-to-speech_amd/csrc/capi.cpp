@@ -297,6 +297,36 @@ int m2s_acoustic_forward_ragged(m2s_acoustic* m, const float* frames, const int*
   });
 }
 
+size_t m2s_acoustic_windowed_workspace_bytes(const m2s_acoustic* m, const int* lengths, const int* context, int B,
+                                             int H, int W, int window, int merge) {
+  size_t r = 0;
+  if (!m) return 0;
+  guarded([&] { r = m->impl.windowed_workspace_bytes(lengths, context, B, H, W, window, merge); });
+  return r;
+}
+
+int m2s_bilstm_windowed(m2s_acoustic* m, const float* feats, const int* lengths, const int* context, int B, int rows,
+                        int window, int merge, float* y, float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && feats && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.bilstm_windowed(feats, lengths, context, B, rows, window, merge, y, mel_norm, w, S(stream));
+  });
+}
+
+int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const int* lengths, const int* context, int B,
+                                  int rows, int H, int W, int window, int merge, float* mel_norm, void* ws,
+                                  size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && frames && mel_norm && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m->impl.forward_windowed(frames, lengths, context, B, rows, H, W, window, merge, mel_norm, ws, ws_bytes, S(stream));
+  });
+}
+
 size_t m2s_vocoder_ragged_workspace_bytes(const m2s_vocoder* v, const int* lengths, int B) {
   size_t r = 0;
   if (!v) return 0;

@@ -262,6 +262,29 @@ size_t lstm_x3_sync_bytes();
 void launch_lstm_x3(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
                     unsigned* err_host, hipStream_t s);
 
+// Sliding-window BiLSTM (lstm_window.hip): S independent windows of at most W <= 16 steps, one launch per step,
+// no cross-workgroup communication.  H = 640 only.
+bool lstm_window_supported(int H);
+// W_hh (4H, H) of the two directions -> [dir][unit group of 16][gate x 16 + unit][H] fp32 (2 x 4H x H floats): one
+// workgroup's 64 rows hold all four gates of its hidden units
+void pack_lstm_window_whh(const float* const whh[2], int H, float* out);
+// clip table tab = [off | len | ctx | wbase | obase] (B ints each) -> win[w] = {first projected row, k | delay << 8}.
+// latest: one window per output frame t >= ctx, k = min(W, t + 1), delay = W - k; mean: the len - min(len, W) + 1
+// full windows of a clip (one of k = len steps where len <= W), delay = 0.  max_windows: the largest count per clip
+void launch_lstm_window_table(const int* tab, int B, int W, bool mean, int max_windows, int2* win, hipStream_t s);
+// step 0 (elementwise): hop = the next step's operand [dirs][S] (fp32 rows of H, or split [hi H | lo H] bf16; null
+// if no step follows), c [dirs][S][H]; hf0 / hf1: fp32 h of the forward / reverse direction (may be null).  latest:
+// the reverse direction is this step alone, on the window's last frame, and is written to hf1 only
+void launch_lstm_window_step0(const float* pre, const int2* win, int S, bool latest, bool split, void* hop, float* c,
+                              float* hf0, float* hf1, hipStream_t s);
+// recurrent step j >= 1 of `dirs` directions: hin -> hout (operand layout; hout may be null on the last step), c
+// in place, hf (may be null) fp32 h at hf + dir * hf_dir_stride + window * H
+void launch_lstm_window_step(const float* pre, const float* wperm, const int2* win, int S, int j, int dirs, bool split,
+                             const void* hin, void* hout, float* c, float* hf, long hf_dir_stride, hipStream_t s);
+// mean merge: hf [2][W][S][H] -> hm [2][N][H] (forward | reverse averages per packed output row, fixed order)
+void launch_lstm_window_mean(const float* hf, const int* tab, int B, int W, int S, long N, int max_len, float* hm,
+                             hipStream_t s);
+
 // head: y = hs[0] + hs[1] (sum merge); out = y W^T + b.  wt (H, n_mels) transposed weight.
 void launch_mel_head(const float* hs, int rows, int H, const float* wt, const float* b, int n_mels,
                      float* out, hipStream_t s);

@@ -479,6 +479,10 @@ Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int d
   std::memcpy(wh.data(), whh[0], sizeof(float) * 4 * H * H);
   std::memcpy(wh.data() + (size_t)4 * H * H, whh[1], sizeof(float) * 4 * H * H);
   whh_ = arena_.add_vec(wh);
+  if (lstm_window_supported(H)) {  // the windowed path's copy: rows permuted so a workgroup's tile holds all four gates
+    pack_lstm_window_whh(whh, H, wh.data());
+    whh_win_ = arena_.add_vec(wh);
+  }
   const float* hw = need(sd, "head.weight", {n_mels, H}).data;
   const float* hb = need(sd, "head.bias", {n_mels}).data;
   std::vector<float> wt((size_t)H * n_mels);
@@ -1073,6 +1077,22 @@ void RaggedTable::upload(const int* lengths, int B, int* dev, hipStream_t s) {
   M2S_HIP(hipEventRecord(done_, s));
 }
 
+void RaggedTable::upload_ints(const int* src, size_t n, int* dev, hipStream_t s) {
+  ragged_check_stream(s);
+  if (!done_) M2S_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
+  M2S_HIP(hipEventSynchronize(done_));  // the previous call's copy has read the staging buffer
+  if (cap_ < n) {
+    if (host_) M2S_HIP(hipHostFree(host_));
+    host_ = nullptr;
+    cap_ = 0;
+    M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&host_), n * sizeof(int), hipHostMallocDefault));
+    cap_ = n;
+  }
+  std::memcpy(host_, src, n * sizeof(int));
+  M2S_HIP(hipMemcpyAsync(dev, host_, n * sizeof(int), hipMemcpyHostToDevice, s));
+  M2S_HIP(hipEventRecord(done_, s));
+}
+
 size_t Acoustic::ragged_workspace_bytes(const int* lengths, int B, int H, int W) const {
   long n = 0;
   for (int b = 0; lengths && b < B; ++b) n += lengths[b];
@@ -1131,6 +1151,141 @@ void Acoustic::forward_ragged(const float* frames, const int* lengths, int B, lo
   float* feats = ws.take<float>((size_t)N * EFF_OUT);
   effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm_ragged(feats, lengths, B, N, nullptr, mel_norm, ws, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// Windowed inference (lstm_window.hip, DESIGN.md "Windowed acoustic inference")
+WindowPlan window_plan(const int* lengths, const int* context, int B, long rows, int window, int merge) {
+  M2S_CHECK(window >= 1 && window <= 16, "windowed: window = " + std::to_string(window) + " outside 1..16");
+  M2S_CHECK(merge == M2S_WINDOW_LATEST || merge == M2S_WINDOW_MEAN, "windowed: unknown merge " + std::to_string(merge));
+  M2S_CHECK(!(context && merge == M2S_WINDOW_MEAN), "windowed: a context needs the latest merge");
+  const RaggedDims d = ragged_dims(lengths, B, rows);
+  WindowPlan p;
+  p.B = B;
+  p.W = window;
+  p.mean = merge == M2S_WINDOW_MEAN;
+  p.N = d.N;
+  p.max_len = d.Tmax;
+  p.tab.resize((size_t)5 * B);
+  long off = 0;
+  for (int b = 0; b < B; ++b) {
+    const int len = lengths[b], ctx = context ? context[b] : 0;
+    M2S_CHECK(ctx >= 0 && ctx <= window - 1 && ctx < len,
+              "windowed: context[" + std::to_string(b) + "] = " + std::to_string(ctx) + " outside 0..min(window - 1, " +
+                  "length - 1)");
+    const int k = std::min(len, window);
+    const int nwin = p.mean ? len - k + 1 : len - ctx;
+    p.tab[b] = (int)off;
+    p.tab[B + b] = len;
+    p.tab[2 * B + b] = ctx;
+    p.tab[3 * B + b] = (int)p.S;
+    p.tab[4 * B + b] = (int)p.R;
+    for (int j = 0; j < window; ++j)
+      p.active[j] += p.mean ? (k > j ? 2.0 * nwin : 0.0) : (double)std::max(0, len - std::max(ctx, window - 1 - j));
+    p.max_windows = std::max(p.max_windows, nwin);
+    off += len;
+    p.S += nwin;
+    p.R += len - ctx;
+  }
+  return p;
+}
+
+Acoustic::WindowBufs Acoustic::window_bufs(Workspace& ws, const WindowPlan& p) const {
+  const size_t H = (size_t)hidden_, S = (size_t)p.S, dirs = p.mean ? 2 : 1;
+  WindowBufs b;
+  b.tab = ws.take<int>((size_t)5 * p.B);
+  b.win = ws.take<int2>(S);
+  b.pre = ws.take<float>((size_t)p.N * 8 * H);
+  if (p.W > 1) {  // the step operands (fp32 rows or split pairs: 4 bytes an element either way) and the cell state
+    b.hop[0] = ws.take<float>(dirs * S * H);
+    if (p.W > 2) b.hop[1] = ws.take<float>(dirs * S * H);
+    b.c = ws.take<float>(dirs * S * H);
+  }
+  b.hm = ws.take<float>((size_t)2 * p.R * H);
+  if (p.mean) b.hf = ws.take<float>((size_t)2 * p.W * S * H);
+  return b;
+}
+
+size_t Acoustic::windowed_workspace_bytes(const int* lengths, const int* context, int B, int H, int W, int window,
+                                          int merge) const {
+  long n = 0;
+  for (int b = 0; lengths && b < B; ++b) n += lengths[b];
+  M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
+  const WindowPlan p = window_plan(lengths, context, B, n, window, merge);
+  Workspace ws(nullptr, 0);
+  if (H != 0 || W != 0) {
+    ws.take<float>((size_t)p.N * EFF_OUT);
+    ws.take<char>(effnet_ws((int)p.N, H, W));
+  }
+  window_bufs(ws, p);
+  return ws.used();
+}
+
+void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window,
+                               int merge, float* y, float* mel_norm, Workspace& ws, hipStream_t s) {
+  M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
+  const WindowPlan p = window_plan(lengths, context, B, N, window, merge);
+  ragged_check_stream(s);
+  const int H = hidden_, W = p.W, S = (int)p.S, dirs = p.mean ? 2 : 1;
+  const bool split = dtype_ != M2S_DT_F32;
+  const WindowBufs b = window_bufs(ws, p);
+  rtab_.upload_ints(p.tab.data(), p.tab.size(), b.tab, s);
+  StageTag tag("bilstm");
+  // the projection, once per FRAME row; one K order for every row count (kwave stays 0: a row's bits must not
+  // depend on how many rows the call holds, or a stream's chunking would show)
+  ConvArgs a = conv_args(lstm_ih_);
+  a.x = feats;
+  a.y = b.pre;
+  a.M = (int)N;
+  a.kwave = 0;
+  run_conv<float>(a, lstm_ih_, s);
+  {
+    ProfScope ps("lstm_window_table_kernel", 0.0, 4.0 * (5.0 * B + 2.0 * S), s);
+    launch_lstm_window_table(b.tab, B, W, p.mean, p.max_windows, b.win, s);
+  }
+  const size_t plane = (size_t)S * H;
+  {
+    // step 0: three gates of one projected row per (window, unit); latest adds the reverse step of every window
+    const double cells = p.active[0] + (p.mean ? 0.0 : (double)S);
+    ProfScope ps("lstm_window_step0_kernel", 0.0, 4.0 * cells * H * (3.0 + 2.0), s);
+    launch_lstm_window_step0(b.pre, b.win, S, !p.mean, split, b.hop[0], b.c, p.mean ? b.hf : (W == 1 ? b.hm : nullptr),
+                             p.mean ? b.hf + (size_t)W * plane : b.hm + (size_t)p.R * H, s);
+  }
+  const float* wperm = static_cast<const float*>(arena_.ptr(whh_win_));
+  for (int j = 1; j < W; ++j) {
+    const void* hin = b.hop[(j - 1) & 1];
+    void* hout = j + 1 < W ? b.hop[j & 1] : nullptr;
+    float* hf = p.mean ? b.hf + (size_t)j * plane : (j == W - 1 ? b.hm : nullptr);
+    // algorithmic work of the VALID window steps: W_hh of the launched directions once, and per cell update the
+    // four gathered gates, h in and out, c in and out
+    ProfScope ps(split ? "lstm_window_step_kernel<split>" : "lstm_window_step_kernel<f32>",
+                 (split ? 3.0 : 2.0) * 4.0 * H * H * p.active[j], 4.0 * dirs * 4 * H * H + 4.0 * p.active[j] * H * 8.0, s);
+    launch_lstm_window_step(b.pre, wperm, b.win, S, j, dirs, split, hin, hout, b.c, hf, (long)((size_t)W * plane), s);
+  }
+  if (p.mean) {
+    double contrib = 0.0;  // (window, step, direction) rows read: every valid one once
+    for (int j = 0; j < W; ++j) contrib += p.active[j];
+    ProfScope ps("lstm_window_mean_kernel", contrib * H, 4.0 * H * (contrib + 2.0 * p.N), s);
+    launch_lstm_window_mean(b.hf, b.tab, B, W, S, p.N, p.max_len, b.hm, s);
+  }
+  if (mel_norm) {
+    StageTag head("head");
+    ProfScope ps("mel_head_kernel", 2.0 * p.R * H * n_mels_, 4.0 * p.R * (2 * H + n_mels_), s);
+    launch_mel_head(b.hm, (int)p.R, H, static_cast<const float*>(arena_.ptr(head_wt_)),
+                    static_cast<const float*>(arena_.ptr(head_b_)), n_mels_, mel_norm, s);
+  }
+  if (y) launch_add2(b.hm, b.hm + (size_t)p.R * H, y, (long)((size_t)p.R * H), s);
+}
+
+void Acoustic::forward_windowed(const float* frames, const int* lengths, const int* context, int B, long N, int H,
+                                int W, int window, int merge, float* mel_norm, void* wsp, size_t wsb, hipStream_t s) {
+  M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
+  window_plan(lengths, context, B, N, window, merge);  // before the CNN launches
+  ragged_check_stream(s);
+  Workspace ws(wsp, wsb);
+  float* feats = ws.take<float>((size_t)N * EFF_OUT);
+  effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
+  bilstm_windowed(feats, lengths, context, B, N, window, merge, nullptr, mel_norm, ws, s);
 }
 
 // ------------------------------------------------------------------------------------------

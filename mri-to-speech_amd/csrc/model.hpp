@@ -101,12 +101,28 @@ class RaggedTable {
   RaggedTable& operator=(const RaggedTable&) = delete;
   ~RaggedTable();
   void upload(const int* lengths, int B, int* dev, hipStream_t s);
+  // any table of n ints through the same staging buffer (the windowed calls' five-column clip table)
+  void upload_ints(const int* src, size_t n, int* dev, hipStream_t s);
 
  private:
   int* host_ = nullptr;
   size_t cap_ = 0;
   hipEvent_t done_ = nullptr;
 };
+
+// Windowed calls (lstm_window.hip, DESIGN.md "Windowed acoustic inference"): the validated shape of one call.
+// N packed input rows, S windows, R output rows (= N - sum(context)); tab = [off | len | ctx | wbase | obase];
+// active[j]: window-directions that run a cell update at global step j (the algorithmic work of that launch).
+struct WindowPlan {
+  int B = 0, W = 0, max_windows = 0, max_len = 0;
+  bool mean = false;
+  long N = 0, S = 0, R = 0;
+  std::vector<int> tab;
+  double active[16] = {};
+};
+// M2S_E_ARG, before any launch: window outside 1..16, an unknown merge, a context with mean, a context entry outside
+// 0..min(W - 1, len - 1), and the ragged calls' own argument errors
+WindowPlan window_plan(const int* lengths, const int* context, int B, long rows, int window, int merge);
 
 class Acoustic {
  public:
@@ -175,8 +191,26 @@ class Acoustic {
                      hipStream_t s);
   void forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm, void* ws,
                       size_t wsb, hipStream_t s);
+  // Sliding windows of `window` frames over packed clips (m2s.h "windowed inference"): packed feats (N, 208) /
+  // frames (N, H, W) -> y (R, hidden), mel_norm (R, n_mels), R = N - sum(context).  H = W = 0 in the query: the
+  // BiLSTM part alone (bilstm_windowed's exact size).
+  size_t windowed_workspace_bytes(const int* lengths, const int* context, int B, int H, int W, int window,
+                                  int merge) const;
+  void bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window, int merge,
+                       float* y, float* mel_norm, Workspace& ws, hipStream_t s);
+  void forward_windowed(const float* frames, const int* lengths, const int* context, int B, long N, int H, int W,
+                        int window, int merge, float* mel_norm, void* ws, size_t wsb, hipStream_t s);
 
  private:
+  struct WindowBufs {
+    int* tab = nullptr;
+    int2* win = nullptr;
+    float *pre = nullptr, *c = nullptr, *hm = nullptr, *hf = nullptr;
+    void* hop[2] = {nullptr, nullptr};
+  };
+  // the one carve of a windowed call's BiLSTM scratch, shared by the size query and the call
+  WindowBufs window_bufs(Workspace& ws, const WindowPlan& p) const;
+  size_t whh_win_ = 0;  // W_hh in lstm_window.hip's row order (pack_lstm_window_whh)
   // the recurrence kernel for (B, T): the selection ladder shared by bilstm and bilstm_ragged.  seq_steps / rows:
   // the recurrent steps and (b, t) rows that count as algorithmic work (a ragged call: the valid ones)
   void lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps, double rows,

@@ -212,6 +212,54 @@ at::Tensor acoustic_forward_ragged(int64_t h, const at::Tensor& frames, at::IntA
   return out;
 }
 
+// Windowed inference (include/m2s.h): sliding windows of `window` frames, merge 0 = latest, 1 = mean; `context`
+// empty = none.  Output rows = N - sum(context).
+int64_t windowed_out_rows(int64_t N, const std::vector<int>& c) {
+  int64_t r = N;
+  for (int v : c) r -= v;
+  return r < 0 ? 0 : r;
+}
+
+// feats (N,208) -> (y (R,hidden), mel_norm (R,n_mels))
+std::tuple<at::Tensor, at::Tensor> bilstm_windowed(int64_t h, const at::Tensor& feats, at::IntArrayRef lengths,
+                                                   at::IntArrayRef context, int64_t window, int64_t merge,
+                                                   int64_t hidden, int64_t n_mels) {
+  TORCH_CHECK(feats.dim() == 2 && feats.size(1) == 208, "bilstm_windowed: feats must be packed (N,208)");
+  TORCH_CHECK(context.empty() || context.size() == lengths.size(), "bilstm_windowed: one context entry per clip");
+  const Guard g(feats.device());
+  const at::Tensor x = f32_on_device(feats, "feats");
+  const std::vector<int> l = host_lengths(lengths, "bilstm_windowed"), c = host_lengths(context, "bilstm_windowed");
+  const int N = x.size(0), B = (int)l.size();
+  const int* cp = c.empty() ? nullptr : c.data();
+  const int64_t R = windowed_out_rows(N, c);
+  at::Tensor y = at::empty({R, hidden}, x.options());
+  at::Tensor m = at::empty({R, n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_windowed_workspace_bytes(A(h), l.data(), cp, B, 0, 0, (int)window, (int)merge), x);
+  ok(m2s_bilstm_windowed(A(h), x.data_ptr<float>(), l.data(), cp, B, N, (int)window, (int)merge, y.data_ptr<float>(),
+                         m.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "bilstm_windowed");
+  return {y, m};
+}
+
+// frames (N,H,W) -> mel_norm (R,n_mels)
+at::Tensor acoustic_forward_windowed(int64_t h, const at::Tensor& frames, at::IntArrayRef lengths,
+                                     at::IntArrayRef context, int64_t window, int64_t merge, int64_t n_mels) {
+  TORCH_CHECK(frames.dim() == 3, "acoustic_forward_windowed: frames must be packed (N,H,W)");
+  TORCH_CHECK(context.empty() || context.size() == lengths.size(), "acoustic_forward_windowed: one context entry per clip");
+  const Guard g(frames.device());
+  const at::Tensor x = f32_on_device(frames, "frames");
+  const std::vector<int> l = host_lengths(lengths, "acoustic_forward_windowed"),
+                         c = host_lengths(context, "acoustic_forward_windowed");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), B = (int)l.size();
+  const int* cp = c.empty() ? nullptr : c.data();
+  at::Tensor out = at::empty({windowed_out_rows(N, c), n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_windowed_workspace_bytes(A(h), l.data(), cp, B, H, W, (int)window, (int)merge), x);
+  ok(m2s_acoustic_forward_windowed(A(h), x.data_ptr<float>(), l.data(), cp, B, N, H, W, (int)window, (int)merge,
+                                   out.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "acoustic_forward_windowed");
+  return out;
+}
+
 // mel (N,num_mels) packed layout 1 -> wav (N*hop)
 at::Tensor hifigan_forward_ragged(int64_t v, const at::Tensor& mel, at::IntArrayRef lengths, int64_t hop) {
   TORCH_CHECK(mel.dim() == 2, "hifigan_forward_ragged: mel must be packed (N,num_mels)");
@@ -443,6 +491,10 @@ TORCH_LIBRARY(m2s, m) {
   m.def("hifigan_forward_ragged(int handle, Tensor mel, int[] lengths, int hop) -> Tensor");
   m.def("pipeline_forward_ragged(int acoustic, int vocoder, Tensor frames, int[] lengths, Tensor mean, Tensor std,"
         " int n_mels, int hop) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("bilstm_windowed(int handle, Tensor feats, int[] lengths, int[] context, int window, int merge, int hidden,"
+        " int n_mels) -> (Tensor, Tensor)");
+  m.def("acoustic_forward_windowed(int handle, Tensor frames, int[] lengths, int[] context, int window, int merge,"
+        " int n_mels) -> Tensor");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
   m.def("cam_backbone(int handle, Tensor frames) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -466,6 +518,8 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("acoustic_forward_ragged", &acoustic_forward_ragged);
   m.impl("hifigan_forward_ragged", &hifigan_forward_ragged);
   m.impl("pipeline_forward_ragged", &pipeline_forward_ragged);
+  m.impl("bilstm_windowed", &bilstm_windowed);
+  m.impl("acoustic_forward_windowed", &acoustic_forward_windowed);
   m.impl("preprocess_frames", &preprocess_frames);
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);

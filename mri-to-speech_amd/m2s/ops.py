@@ -23,6 +23,10 @@ OPS = ("acoustic_forward", "effnet_forward", "effnet_features", "bilstm_summerge
        "linear_forward", "linear_backward", "gap_forward", "gap_backward")
 # ragged batches: clips of different lengths in one call, packed tensors of sum(lengths) rows (include/m2s.h)
 RAGGED_OPS = ("bilstm_summerge_ragged", "acoustic_forward_ragged", "hifigan_forward_ragged", "pipeline_forward_ragged")
+# windowed inference: the BiLSTM over sliding windows of `window` frames (packed like the ragged ops; merge 0 = latest,
+# 1 = mean; `context` = leading history rows per clip that get no output row, [] = none)
+WINDOWED_OPS = ("bilstm_windowed", "acoustic_forward_windowed")
+WINDOW_MERGES = {"latest": 0, "mean": 1}
 # analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
 ANALYSIS_OPS = ("mel_spectrogram",)
 
@@ -149,6 +153,15 @@ def _register_fakes():
         n = frames.shape[0]
         mel = [frames.new_empty((n, n_mels), dtype=torch.float32) for _ in range(3)]
         return mel[0], mel[1], mel[2], frames.new_empty((n * hop,), dtype=torch.float32)
+
+    @f("m2s::bilstm_windowed")
+    def _bilstm_windowed(handle, feats, lengths, context, window, merge, hidden, n_mels):
+        r = feats.shape[0] - sum(context)
+        return (feats.new_empty((r, hidden), dtype=torch.float32), feats.new_empty((r, n_mels), dtype=torch.float32))
+
+    @f("m2s::acoustic_forward_windowed")
+    def _acoustic_windowed(handle, frames, lengths, context, window, merge, n_mels):
+        return frames.new_empty((frames.shape[0] - sum(context), n_mels), dtype=torch.float32)
 
     @f("m2s::mel_spectrogram")
     def _melspec(handle, wav, layout):

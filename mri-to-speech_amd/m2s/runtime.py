@@ -150,6 +150,37 @@ class AcousticEngine:
         x, lengths = _packed(feats, lengths, self.device, 1)
         return self.ops.bilstm_summerge_ragged(self.handle, x, lengths, self.rnn_hidden, self.n_mels)
 
+    # ---- windowed inference (include/m2s.h "windowed inference"): the BiLSTM on sliding windows of `window` frames,
+    # the distribution the checkpoint was trained on; additive, the whole-clip calls above stay the default
+    @staticmethod
+    def _window_args(x, lengths, window, merge, context):
+        if merge not in _ops.WINDOW_MERGES:
+            raise N.M2SError(f"unknown window merge {merge!r}; one of {sorted(_ops.WINDOW_MERGES)}")
+        if lengths is None and not isinstance(x, (list, tuple)):
+            lengths = [int(x.shape[0])]  # one clip
+        context = [] if context is None else [int(c) for c in context]
+        return lengths, int(window), _ops.WINDOW_MERGES[merge], context
+
+    def bilstm_windowed(self, feats, lengths=None, window: int = 4, merge: str = "latest", context=None):
+        """packed feats (N,208) (one clip if ``lengths`` is None) or a list of (T_b,208) -> packed (merged BiLSTM
+        output (R,H), head output (R,n_mels)).  ``latest``: row t comes from the window ending at t (causal);
+        ``mean``: the average over the full windows containing t.  ``context[b]`` (latest only, <= window - 1):
+        leading rows of clip b that are history only, R = N - sum(context)."""
+        lengths, window, merge, context = self._window_args(feats, lengths, window, merge, context)
+        x, lengths = _packed(feats, lengths, self.device, 1)
+        return self.ops.bilstm_windowed(self.handle, x, lengths, context, window, merge, self.rnn_hidden, self.n_mels)
+
+    def forward_windowed(self, frames, lengths=None, window: int = 4, merge: str = "latest", context=None):
+        """packed frames (N,[1,]H,W) (one clip if ``lengths`` is None) or a list of per-clip tensors -> packed
+        normalised mel (R,n_mels) of the windowed model; the CNN runs once per frame."""
+        if isinstance(frames, (list, tuple)):
+            frames = [f[:, 0] if f.dim() == 4 else f for f in frames]
+        elif frames.dim() == 4:
+            frames = frames[:, 0]
+        lengths, window, merge, context = self._window_args(frames, lengths, window, merge, context)
+        x, lengths = _packed(frames, lengths, self.device, 2)
+        return self.ops.acoustic_forward_windowed(self.handle, x, lengths, context, window, merge, self.n_mels)
+
 
 class VocoderEngine:
     def __init__(self, state_dict: Dict, h, dtype: str = "bf16x3", device=None):
@@ -264,4 +295,16 @@ class Pipeline:
         x, lengths = _packed(frames, lengths, self.device, 2)
         mn, db, ln, wav = self.ac.ops.pipeline_forward_ragged(self.ac.handle, self.voc.handle, x, lengths, self.mean,
                                                               self.std, self.ac.n_mels, self.voc.hop)
+        return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": wav}
+
+    def forward_windowed(self, frames, lengths=None, window: int = 4, merge: str = "latest"):
+        """``forward_ragged`` with the windowed acoustic model (AcousticEngine.forward_windowed): the windowed
+        acoustic call, the mel glue, then the ragged vocoder leg on its mel_log, all on the device."""
+        if isinstance(frames, (list, tuple)):
+            lengths = [int(f.shape[0]) for f in frames] if lengths is None else lengths
+        elif lengths is None:
+            lengths = [int(frames.shape[0])]
+        mn = self.ac.forward_windowed(frames, lengths, window, merge)
+        db, ln = mel_glue(mn, self.mean, self.std)
+        wav = self.voc.forward_ragged(ln, lengths)
         return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": wav}

@@ -293,6 +293,24 @@ class OTNLikeCNNBiLSTM(nn.Module):
         self._check_grad(first)
         return self._engine(first.device).forward_ragged(frames, lengths)
 
+    def forward_windowed(self, x: torch.Tensor, window: int = 4, merge: str = "latest") -> torch.Tensor:
+        """(B,T,1,H,W) or (B,T,H,W) -> (B,T,n_mels) with the BiLSTM run on sliding windows of ``window`` frames,
+        the way the checkpoint was trained (eval only; additive: ``forward`` stays the reference's whole-clip
+        inference).  ``latest``: frame t from the window ending at t; ``mean``: averaged over the full windows
+        that contain t (m2s.runtime.AcousticEngine.forward_windowed)."""
+        if self.training:
+            raise NotImplementedError("forward_windowed is an inference mode: call model.eval() first")
+        self._check_grad(x)
+        if x.dim() == 5:
+            if x.size(2) != 1:
+                raise ValueError("expected a single grey channel")
+            x = x[:, :, 0]
+        if x.dim() != 4:
+            raise ValueError(f"expected (B,T,[1,]H,W) frames, got {tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[1]
+        out = self._engine(x.device).forward_windowed(x.reshape(B * T, *x.shape[-2:]), [T] * B, window, merge)
+        return out.view(B, T, -1)
+
 
 def build_acoustic_model(n_mels: int = 64, cnn_pretrained: bool = False, rnn_hidden: int = 640,
                          dropout: float = 0.5, use_checkpoint: bool = False, ckpt_segments: int = 2,

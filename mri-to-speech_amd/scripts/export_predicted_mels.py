@@ -161,7 +161,9 @@ def _export(args, out_dir, mean, std, world, rank, local) -> list:
                            load=world == 1)
 
     def mels(frames):  # (B,T,H,W) -> (B, n_mels, T) ln-mel
-        _, ln = mel_glue(model(frames[:, :, None]), mean, std)
+        x = frames[:, :, None]
+        mn = model.forward_windowed(x, args.window, args.window_merge) if args.window else model(x)
+        _, ln = mel_glue(mn, mean, std)
         return ln.transpose(1, 2)
 
     def mels_ragged(frames, lengths):  # packed (N,H,W) -> packed (N, n_mels) ln-mel, time first
@@ -220,7 +222,18 @@ def parse_args(argv=None) -> argparse.Namespace:
                         "call per distinct clip shape")
     p.add_argument("--max-pad-frac", type=float, default=0.25,
                    help="--ragged: largest fraction of padded frames a batch may carry")
-    return p.parse_args(argv)
+    p.add_argument("--window", type=int, default=0, metavar="N",
+                   help="run the BiLSTM on sliding windows of N frames (1..16; the checkpoint is trained on windows of "
+                        "ref_frames = 4) instead of the whole clip; default 0: whole-clip inference as the reference")
+    p.add_argument("--window-merge", choices=["latest", "mean"], default="latest",
+                   help="--window: frame t from the window ending at t (latest) or averaged over the full windows "
+                        "containing t (mean)")
+    args = p.parse_args(argv)
+    if args.window and args.ragged:
+        p.error("--window runs each clip shape in its own call; it is not combined with --ragged")
+    if args.window and not 1 <= args.window <= 16:
+        p.error("--window must be 1..16")
+    return args
 
 
 def main(argv=None):

@@ -177,8 +177,11 @@ def load_hifigan(config_path: Path, checkpoint_path: Path, device: torch.device,
 
 # ------------------------------------------------------------------------------------------------
 # run
-def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray):
+def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray, window: int = 0,
+        window_merge: str = "latest"):
     """(T,H,W) device frames -> dict mel_db (T,n_mels), mel_log (T,n_mels), audio (T*hop,) on the host.
+    ``window`` > 0: the BiLSTM on sliding windows of that many frames (runtime.Pipeline.forward_windowed) instead of
+    the reference's whole-clip recurrence.
 
     On the m2s path the acoustic engine's asynchronous failure report (a BiLSTM barrier timeout
     poisons the outputs with NaN, include/m2s.h m2s_acoustic_status) is read after the results reach
@@ -187,11 +190,17 @@ def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray):
     if hasattr(model, "_engine") and hasattr(gen, "_engine"):  # both are m2s plug-ins: one device call
         eng = model._engine(dev)
         pipe = runtime.Pipeline(eng, gen._engine(dev), mean, std)
-        out = pipe.forward(frames[None])
-        res = {"mel_db": out["mel_db"][0], "mel_log": out["mel_log"][0], "audio": out["wav"][0]}
+        if window:
+            out = pipe.forward_windowed(frames, None, window, window_merge)
+            res = {"mel_db": out["mel_db"], "mel_log": out["mel_log"], "audio": out["wav"]}
+        else:
+            out = pipe.forward(frames[None])
+            res = {"mel_db": out["mel_db"][0], "mel_log": out["mel_log"][0], "audio": out["wav"][0]}
         res = {k: v.float().cpu().numpy() for k, v in res.items()}
         eng.check()
         return res
+    if window:
+        raise RuntimeError("--window needs the m2s acoustic and vocoder plug-ins (a foreign plug-in has no windowed mode)")
     with torch.no_grad():  # a foreign plug-in: its forward, then the device glue and the generator
         mn = model(frames_to_tensor(frames))[0]
         db, ln = runtime.mel_glue(mn, torch.from_numpy(mean), torch.from_numpy(std))
@@ -244,7 +253,16 @@ def parse_args(argv=None):
     p.add_argument("--dtype", choices=["bf16x3", "fp32", "bf16", "fp8"], default=None,
                    help="m2s compute dtype (default: M2S_DTYPE or bf16x3)")
     p.add_argument("--decode-chunk", type=int, default=64, help="frames per decode / H2D chunk")
-    return p.parse_args(argv)
+    p.add_argument("--window", type=int, default=0, metavar="N",
+                   help="run the BiLSTM on sliding windows of N frames (1..16; the checkpoint is trained on windows of "
+                        "ref_frames = 4) instead of the whole clip; default 0: whole-clip inference as the reference")
+    p.add_argument("--window-merge", choices=["latest", "mean"], default="latest",
+                   help="--window: frame t from the window ending at t (latest) or averaged over the full windows "
+                        "containing t (mean)")
+    args = p.parse_args(argv)
+    if args.window and not 1 <= args.window <= 16:
+        p.error("--window must be 1..16")
+    return args
 
 
 def main(argv=None):
@@ -262,7 +280,7 @@ def main(argv=None):
     model = build_mri_model(args, device)
     gen, h = load_hifigan(Path(args.hifigan_config), Path(args.hifigan_checkpoint), device, args.dtype)
     frames = FrameStream(video, device, args.max_frames, chunk=args.decode_chunk).read()
-    res = run(model, gen, frames, mean, std)
+    res = run(model, gen, frames, mean, std, args.window, args.window_merge)
     paths = write_outputs(res, Path(args.output_dir), video.stem, int(h.sampling_rate))
     print(f"[m2s] {frames.shape[0]} frames -> mel {res['mel_db'].shape} -> {res['audio'].shape[0]} samples "
           f"@ {int(h.sampling_rate)} Hz ({model.m2s_dtype if hasattr(model, 'm2s_dtype') else 'plug-in'})")
