@@ -125,6 +125,7 @@ int m2s_acoustic_set_ws_spin_limit(m2s_acoustic* m, unsigned polls);
  *     m2s_acoustic_workspace_bytes(m, N, 1, H, W); m2s_bilstm_summerge that of (m, B, T, H, W) for any valid frame
  *     size, e.g. 64 x 64; m2s_bilstm_summerge_ragged that of m2s_acoustic_ragged_workspace_bytes likewise;
  *     m2s_bilstm_train_forward that of m2s_bilstm_train_workspace_bytes.
+ *   - Every size query returns 0 for a null handle.
  *   - Every output is written completely, each element from this call's inputs alone, and no byte outside the
  *     outputs and the workspace is written: outputs have exactly their documented size, with no slack. */
 size_t m2s_acoustic_workspace_bytes(const m2s_acoustic* m, int B, int T, int H, int W);

@@ -129,6 +129,9 @@ struct CamDims {
   size_t io = 0, mid = 0;  // per-frame floats of the block outputs / expanded maps
   int cs_mid = 0;
 };
+struct CamBufs {  // ping-pong block outputs, expanded maps, SE means / hidden / gates, BatchNorm partial sums
+  float *A, *B, *M, *M2, *sem, *hid, *gate, *scr;
+};
 }  // namespace
 
 static CamDims cam_dims(int H, int W) {
@@ -157,18 +160,22 @@ static CamDims cam_dims(int H, int W) {
   return d;
 }
 
+// the backbone's scratch: the size query and the call both run this
+static CamBufs cam_bufs(Workspace& w, int N, const CamDims& d) {
+  CamBufs b;
+  b.A = w.take<float>((size_t)N * d.io);
+  b.B = w.take<float>((size_t)N * d.io);
+  b.M = w.take<float>((size_t)N * d.mid);
+  b.M2 = w.take<float>((size_t)N * d.mid);
+  b.sem = w.take<float>((size_t)N * d.cs_mid);
+  b.hid = w.take<float>((size_t)N * SE_RD_MAX);
+  b.gate = w.take<float>((size_t)N * d.cs_mid);
+  b.scr = w.take<float>(bn_train_scratch_floats(0, std::max(d.cs_mid, 256)));
+  return b;
+}
+
 size_t CamBackbone::workspace_bytes(int N, int H, int W) const {
-  const CamDims d = cam_dims(H, W);
-  Workspace w(nullptr, 0);
-  w.take<float>((size_t)N * d.io);
-  w.take<float>((size_t)N * d.io);
-  w.take<float>((size_t)N * d.mid);
-  w.take<float>((size_t)N * d.mid);
-  w.take<float>((size_t)N * d.cs_mid);
-  w.take<float>((size_t)N * SE_RD_MAX);
-  w.take<float>((size_t)N * d.cs_mid);
-  w.take<float>(bn_train_scratch_floats(0, std::max(d.cs_mid, 256)));
-  return w.used();
+  return Workspace::bytes([&](Workspace& w) { cam_bufs(w, N, cam_dims(H, W)); });
 }
 
 void CamBackbone::forward(const float* frames, int N, int H, int W, float* const taps[5], float* bn_stats, void* ws,
@@ -176,14 +183,9 @@ void CamBackbone::forward(const float* frames, int N, int H, int W, float* const
   M2S_CHECK(N > 0 && H >= 32 && W >= 32, "cam backbone: bad input size");
   const CamDims d = cam_dims(H, W);
   Workspace w(ws, wsb);
-  float* A = w.take<float>((size_t)N * d.io);
-  float* Bf = w.take<float>((size_t)N * d.io);
-  float* M = w.take<float>((size_t)N * d.mid);
-  float* M2 = w.take<float>((size_t)N * d.mid);
-  float* sem = w.take<float>((size_t)N * d.cs_mid);
-  float* hid = w.take<float>((size_t)N * SE_RD_MAX);
-  float* gate = w.take<float>((size_t)N * d.cs_mid);
-  float* scr = w.take<float>(bn_train_scratch_floats(0, std::max(d.cs_mid, 256)));
+  const CamBufs cb = cam_bufs(w, N, d);
+  float *const A = cb.A, *const Bf = cb.B, *const M = cb.M, *const M2 = cb.M2;
+  float *const sem = cb.sem, *const hid = cb.hid, *const gate = cb.gate, *const scr = cb.scr;
   // the conv kernels index their inputs with 32-bit offsets: run them over frame chunks
   const int fc = (int)std::max<size_t>(1, std::min<size_t>(N, 2147483647ull / std::max(d.io, d.mid)));
   std::vector<size_t> st_off(bn_.size());
@@ -280,15 +282,26 @@ void CamBackbone::forward(const float* frames, int N, int H, int W, float* const
 }
 
 // ---- BiLSTM / Linear autograd entry points -------------------------------------------------------
-size_t bilstm_train_workspace_bytes(int B, int T, int C, int H) {
+namespace {
+struct LstmTrainBufs {  // one layout for the forward (pre, whh) and the backward (dg, wt, hp, dc)
+  float* pre_dg;  // fwd: gate pre-activations (BT, 8H); bwd: dG (2, BT, 4H)
+  float* whh_wt;  // fwd: W_hh of both directions; bwd: W_hh^T
+  float *hp, *dc;  // bwd: h_prev (2, BT, H), the carried cell gradient (2, B, H)
+};
+}  // namespace
+
+static LstmTrainBufs lstm_train_bufs(Workspace& w, int B, int T, int H) {
   const size_t BT = (size_t)B * T;
-  Workspace w(nullptr, 0);
-  w.take<float>(std::max(BT * 8 * H, (size_t)2 * BT * 4 * H));  // fwd: gate pre-activations; bwd: dG
-  w.take<float>((size_t)2 * 4 * H * H);                         // W_hh of both directions (or W_hh^T)
-  w.take<float>(std::max((size_t)2 * B * H, (size_t)2 * BT * H));  // bwd: dc, then h_prev
-  w.take<float>((size_t)2 * B * H);
-  (void)C;
-  return w.used();
+  LstmTrainBufs b;
+  b.pre_dg = w.take<float>(std::max(BT * 8 * H, (size_t)2 * BT * 4 * H));
+  b.whh_wt = w.take<float>((size_t)2 * 4 * H * H);
+  b.hp = w.take<float>(std::max((size_t)2 * B * H, (size_t)2 * BT * H));
+  b.dc = w.take<float>((size_t)2 * B * H);
+  return b;
+}
+
+size_t bilstm_train_workspace_bytes(int B, int T, int, int H) {
+  return Workspace::bytes([&](Workspace& w) { lstm_train_bufs(w, B, T, H); });
 }
 
 void bilstm_train_forward(const float* x, int B, int T, int C, int H, const float* const w_ih[2],
@@ -297,8 +310,8 @@ void bilstm_train_forward(const float* x, int B, int T, int C, int H, const floa
   M2S_CHECK(B > 0 && T > 0 && C > 0 && H > 0 && H % 8 == 0, "bilstm_train: shape");
   const long BT = (long)B * T;
   Workspace w(ws, wsb);
-  float* pre = w.take<float>(std::max(BT * 8 * H, 2 * BT * 4 * (long)H));
-  float* whh = w.take<float>((size_t)2 * 4 * H * H);
+  const LstmTrainBufs b = lstm_train_bufs(w, B, T, H);
+  float *const pre = b.pre_dg, *const whh = b.whh_wt;
   for (int d = 0; d < 2; ++d) {
     // pre[bt][d*4H + n] = sum_c x[bt][c] W_ih[n][c] + b_ih[n] + b_hh[n]
     launch_gemm_f32((int)BT, 4 * H, C, x, C, 1, w_ih[d], 1, C, pre + (size_t)d * 4 * H, 8L * H, b_ih[d], b_hh[d], false, s);
@@ -316,10 +329,8 @@ void bilstm_train_backward(const float* x, const float* dy, int B, int T, int C,
   const long BT = (long)B * T;
   const int G = 4 * H;
   Workspace w(ws, wsb);
-  float* dg = w.take<float>(std::max(BT * 8 * H, 2 * BT * (long)G));
-  float* wt = w.take<float>((size_t)2 * G * H);
-  float* hp = w.take<float>(std::max((size_t)2 * B * H, (size_t)2 * BT * H));
-  float* dc = w.take<float>((size_t)2 * B * H);
+  const LstmTrainBufs b = lstm_train_bufs(w, B, T, H);
+  float *const dg = b.pre_dg, *const wt = b.whh_wt, *const hp = b.hp, *const dc = b.dc;
   for (int d = 0; d < 2; ++d) launch_transpose(w_hh[d], 1, G, H, wt + (size_t)d * G * H, s);
   for (int st = 0; st < T; ++st) launch_lstm_bptt_step(wt, dy, gates, cells, dc, dg, B, T, H, st, s);
   launch_lstm_hprev(hid, hp, B, T, H, s);

@@ -74,6 +74,14 @@ void check_device(int device) {
 
 hipStream_t S(void* s) { return static_cast<hipStream_t>(s); }
 
+// a size query: 0 for a null handle, and for arguments the call would reject (m2s_last_error says why)
+template <class F>
+size_t size_query(bool handles, F f) {
+  size_t r = 0;
+  if (handles) guarded([&] { r = f(); });
+  return r;
+}
+
 // an earlier launch of this engine hit a BiLSTM barrier timeout (its outputs hold NaN): fail loudly
 void no_pending_error(m2s::Acoustic& a) {
   const unsigned e = a.take_async_error();
@@ -137,9 +145,7 @@ int m2s_acoustic_set_ws_spin_limit(m2s_acoustic* m, unsigned polls) {
 }
 
 size_t m2s_acoustic_workspace_bytes(const m2s_acoustic* m, int B, int T, int H, int W) {
-  size_t r = 0;
-  guarded([&] { r = m->impl.workspace_bytes(B, T, H, W); });
-  return r;
+  return size_query(m, [&] { return m->impl.workspace_bytes(B, T, H, W); });
 }
 
 int m2s_acoustic_forward(m2s_acoustic* m, const float* frames, int B, int T, int H, int W, float* mel_norm, void* ws,
@@ -148,7 +154,8 @@ int m2s_acoustic_forward(m2s_acoustic* m, const float* frames, int B, int T, int
     M2S_CHECK(m && frames && mel_norm && ws, "null argument");
     no_pending_error(m->impl);
     DeviceGuard g(m->impl.device());
-    m->impl.forward(frames, B, T, H, W, mel_norm, ws, ws_bytes, S(stream));
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.forward(frames, B, T, H, W, mel_norm, w, S(stream));
   });
 }
 
@@ -216,9 +223,7 @@ int m2s_vocoder_create(const m2s_tensor* sd, int n, const m2s_hifigan_h* h, int 
 void m2s_vocoder_destroy(m2s_vocoder* v) { delete v; }
 
 size_t m2s_vocoder_workspace_bytes(const m2s_vocoder* v, int B, int T) {
-  size_t r = 0;
-  guarded([&] { r = v->impl.workspace_bytes(B, T); });
-  return r;
+  return size_query(v, [&] { return v->impl.workspace_bytes(B, T); });
 }
 
 int m2s_vocoder_forward(m2s_vocoder* v, const float* mel, int mel_layout, int B, int T, float* wav, void* ws,
@@ -233,16 +238,9 @@ int m2s_vocoder_forward(m2s_vocoder* v, const float* mel, int mel_layout, int B,
 }
 
 size_t m2s_pipeline_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, int B, int T, int H, int W) {
-  size_t r = 0;
-  guarded([&] {
-    const size_t rows = (size_t)B * T;
-    m2s::Workspace w(nullptr, 0);
-    w.take<float>(rows * m->impl.n_mels());
-    w.take<char>(rows * m2s::chan_stride(m->impl.n_mels()) * 4);
-    w.take<char>(std::max(m->impl.workspace_bytes(B, T, H, W), v->impl.workspace_bytes(B, T)));
-    r = w.used();
+  return size_query(m && v, [&] {
+    return m2s::Workspace::bytes([&](m2s::Workspace& w) { m2s::pipeline_bufs(w, m->impl, v->impl, B, T, H, W); });
   });
-  return r;
 }
 
 int m2s_pipeline_forward(m2s_acoustic* m, m2s_vocoder* v, const float* frames, int B, int T, int H, int W,
@@ -254,26 +252,20 @@ int m2s_pipeline_forward(m2s_acoustic* m, m2s_vocoder* v, const float* frames, i
     M2S_CHECK(m->impl.n_mels() == v->impl.num_mels(), "n_mels mismatch between acoustic model and vocoder");
     no_pending_error(m->impl);
     DeviceGuard g(m->impl.device());
-    const size_t rows = (size_t)B * T;
-    const int nm = m->impl.n_mels(), cs = m2s::chan_stride(nm);
     m2s::Workspace w(ws, ws_bytes);
-    float* mn = w.take<float>(rows * nm);
-    void* ln_t = w.take<char>(rows * cs * 4);
-    char* rest = w.take<char>(0);
-    const size_t rest_bytes = ws_bytes - (size_t)(rest - static_cast<char*>(ws));
+    const m2s::PipelineBufs b = m2s::pipeline_bufs(w, m->impl, v->impl, B, T, H, W);
     // acoustic scratch is dead once mel_norm is written; the vocoder reuses it
-    m->impl.forward(frames, B, T, H, W, mn, rest, rest_bytes, S(stream));
-    if (mel_norm) M2S_HIP(hipMemcpyAsync(mel_norm, mn, rows * nm * sizeof(float), hipMemcpyDeviceToDevice, S(stream)));
-    m2s::Workspace vw(rest, rest_bytes);
-    v->impl.forward_from_norm(mn, mean, std, B, T, mel_db, mel_log, ln_t, wav, vw, S(stream));
+    m2s::Workspace aw(b.rest, b.rest_bytes), vw(b.rest, b.rest_bytes);
+    m->impl.forward(frames, B, T, H, W, b.mn, aw, S(stream));
+    if (mel_norm)
+      M2S_HIP(hipMemcpyAsync(mel_norm, b.mn, (size_t)B * T * m->impl.n_mels() * sizeof(float), hipMemcpyDeviceToDevice,
+                             S(stream)));
+    v->impl.forward_from_norm(b.mn, mean, std, B, T, mel_db, mel_log, b.ln_t, wav, vw, S(stream));
   });
 }
 
 size_t m2s_acoustic_ragged_workspace_bytes(const m2s_acoustic* m, const int* lengths, int B, int H, int W) {
-  size_t r = 0;
-  if (!m) return 0;
-  guarded([&] { r = m->impl.ragged_workspace_bytes(lengths, B, H, W); });
-  return r;
+  return size_query(m, [&] { return m->impl.ragged_workspace_bytes(lengths, B, H, W); });
 }
 
 int m2s_bilstm_summerge_ragged(m2s_acoustic* m, const float* feats, const int* lengths, int B, int rows, float* y,
@@ -293,16 +285,14 @@ int m2s_acoustic_forward_ragged(m2s_acoustic* m, const float* frames, const int*
     M2S_CHECK(m && frames && mel_norm && ws, "null argument");
     no_pending_error(m->impl);
     DeviceGuard g(m->impl.device());
-    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mel_norm, ws, ws_bytes, S(stream));
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mel_norm, w, S(stream));
   });
 }
 
 size_t m2s_acoustic_windowed_workspace_bytes(const m2s_acoustic* m, const int* lengths, const int* context, int B,
                                              int H, int W, int window, int merge) {
-  size_t r = 0;
-  if (!m) return 0;
-  guarded([&] { r = m->impl.windowed_workspace_bytes(lengths, context, B, H, W, window, merge); });
-  return r;
+  return size_query(m, [&] { return m->impl.windowed_workspace_bytes(lengths, context, B, H, W, window, merge); });
 }
 
 int m2s_bilstm_windowed(m2s_acoustic* m, const float* feats, const int* lengths, const int* context, int B, int rows,
@@ -323,15 +313,13 @@ int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const in
     M2S_CHECK(m && frames && mel_norm && ws, "null argument");
     no_pending_error(m->impl);
     DeviceGuard g(m->impl.device());
-    m->impl.forward_windowed(frames, lengths, context, B, rows, H, W, window, merge, mel_norm, ws, ws_bytes, S(stream));
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.forward_windowed(frames, lengths, context, B, rows, H, W, window, merge, mel_norm, w, S(stream));
   });
 }
 
 size_t m2s_vocoder_ragged_workspace_bytes(const m2s_vocoder* v, const int* lengths, int B) {
-  size_t r = 0;
-  if (!v) return 0;
-  guarded([&] { r = v->impl.ragged_workspace_bytes(lengths, B); });
-  return r;
+  return size_query(v, [&] { return v->impl.ragged_workspace_bytes(lengths, B); });
 }
 
 int m2s_vocoder_forward_ragged(m2s_vocoder* v, const float* mel, const int* lengths, int B, int rows, float* wav,
@@ -346,18 +334,10 @@ int m2s_vocoder_forward_ragged(m2s_vocoder* v, const float* mel, const int* leng
 
 size_t m2s_pipeline_ragged_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, const int* lengths, int B,
                                            int H, int W) {
-  size_t r = 0;
-  if (!m || !v) return 0;
-  guarded([&] {
-    const size_t a = m->impl.ragged_workspace_bytes(lengths, B, H, W), b = v->impl.ragged_workspace_bytes(lengths, B);
-    size_t rows = 0;
-    for (int i = 0; i < B; ++i) rows += (size_t)lengths[i];
-    m2s::Workspace w(nullptr, 0);
-    w.take<float>(rows * m->impl.n_mels());
-    w.take<char>(std::max(a, b));
-    r = w.used();
+  return size_query(m && v, [&] {
+    return m2s::Workspace::bytes(
+        [&](m2s::Workspace& w) { m2s::pipeline_ragged_bufs(w, m->impl, v->impl, lengths, B, H, W); });
   });
-  return r;
 }
 
 int m2s_pipeline_forward_ragged(m2s_acoustic* m, m2s_vocoder* v, const float* frames, const int* lengths, int B,
@@ -370,16 +350,13 @@ int m2s_pipeline_forward_ragged(m2s_acoustic* m, m2s_vocoder* v, const float* fr
     no_pending_error(m->impl);
     m2s::ragged_dims(lengths, B, rows);
     DeviceGuard g(m->impl.device());
-    const int nm = m->impl.n_mels();
     m2s::Workspace w(ws, ws_bytes);
+    const m2s::PipelineBufs b = m2s::pipeline_ragged_bufs(w, m->impl, v->impl, lengths, B, H, W);
     // the head writes the caller's mel_norm directly where there is one (packed rows: no internal layout)
-    float* own = w.take<float>((size_t)rows * nm);
-    float* mn = mel_norm ? mel_norm : own;
-    char* rest = w.take<char>(0);
-    const size_t rest_bytes = ws_bytes - (size_t)(rest - static_cast<char*>(ws));
+    float* mn = mel_norm ? mel_norm : b.mn;
     // acoustic scratch is dead once mel_norm is written; the vocoder reuses it
-    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mn, rest, rest_bytes, S(stream));
-    m2s::Workspace vw(rest, rest_bytes);
+    m2s::Workspace aw(b.rest, b.rest_bytes), vw(b.rest, b.rest_bytes);
+    m->impl.forward_ragged(frames, lengths, B, rows, H, W, mn, aw, S(stream));
     v->impl.forward_from_norm_ragged(mn, mean, std, lengths, B, rows, mel_db, mel_log, wav, vw, S(stream));
   });
 }
@@ -402,10 +379,7 @@ int m2s_cam_bn_channels(const m2s_cam* c, int layer) {
 }
 
 size_t m2s_cam_workspace_bytes(const m2s_cam* c, int N, int H, int W) {
-  size_t r = 0;
-  if (!c) return 0;  // like the other size queries: 0 for a null handle
-  guarded([&] { r = c->impl.workspace_bytes(N, H, W); });
-  return r;
+  return size_query(c, [&] { return c->impl.workspace_bytes(N, H, W); });
 }
 
 int m2s_cam_backbone(m2s_cam* c, const float* frames, int N, int H, int W, float* const* taps, float* bn_stats,
@@ -418,9 +392,7 @@ int m2s_cam_backbone(m2s_cam* c, const float* frames, int N, int H, int W, float
 }
 
 size_t m2s_bilstm_train_workspace_bytes(int B, int T, int C, int H) {
-  size_t r = 0;
-  guarded([&] { r = m2s::bilstm_train_workspace_bytes(B, T, C, H); });
-  return r;
+  return size_query(true, [&] { return m2s::bilstm_train_workspace_bytes(B, T, C, H); });
 }
 
 int m2s_bilstm_train_forward(const float* x, int B, int T, int C, int H, const float* const* w, float* y,

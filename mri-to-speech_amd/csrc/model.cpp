@@ -567,72 +567,352 @@ int Acoustic::pass_frames(int N) const {
   return even <= chunk + chunk / 16 ? even : chunk;
 }
 
-size_t Acoustic::effnet_ws(int N, int H, int W) const {
+template <typename T>
+Acoustic::EffBufs<T> Acoustic::effnet_bufs(Workspace& ws, int N, int H, int W) const {
   size_t io, mid, se;
   effnet_dims(H, W, &io, &mid, &se);
-  const size_t es = act_bytes(dtype_);
-  const size_t nc = pass_frames(N);
-  Workspace ws(nullptr, 0);
-  ws.take<char>(nc * io * es);
-  ws.take<char>(nc * io * es);
-  ws.take<char>(nc * mid * es);
-  ws.take<char>(nc * mid * es);
-  ws.take<float>(nc * se);
-  ws.take<char>(nc * max_mid_cs_ * es);   // SE means
-  ws.take<char>(nc * SE_RD_MAX * es);     // SE hidden (rd <= 64)
-  ws.take<char>(nc * max_mid_cs_ * es);   // SE gates
-  ws.take<char>(nc * effnet_x8(H, W));    // fp8: e4m3 expand operands, two buffers
-  ws.take<char>(nc * effnet_x8(H, W));
-  return ws.used();
+  const size_t nc = pass_frames(N), R = Elem<T>::R;  // split fp32: hi + lo planes
+  EffBufs<T> b{};
+  b.A = ws.take<T>(nc * io * R);
+  b.B = ws.take<T>(nc * io * R);
+  b.M = ws.take<T>(nc * mid * R);
+  b.M2 = ws.take<T>(nc * mid * R);
+  b.sums = ws.take<float>(nc * se);
+  b.se_mean = ws.take<T>(nc * max_mid_cs_ * R);
+  b.se_hid = ws.take<T>(nc * SE_RD_MAX * R);
+  b.scale = ws.take<T>(nc * max_mid_cs_ * R);
+  if (const size_t x8b = effnet_x8(H, W))
+    for (uint8_t*& x : b.X8) x = ws.take<uint8_t>(nc * x8b);
+  return b;
 }
 
+void Acoustic::effnet_ws(Workspace& ws, int N, int H, int W) const {
+  dispatch_act(dtype_, [&](auto t) { effnet_bufs<typename decltype(t)::type>(ws, N, H, W); });
+}
+
+float* Acoustic::feats_buf(Workspace& ws, size_t rows) const { return ws.take<float>(rows * EFF_OUT); }
+
 size_t Acoustic::workspace_bytes(int B, int T, int H, int W) const {
-  const size_t BT = (size_t)B * T;
-  Workspace ws(nullptr, 0);
-  ws.take<float>(BT * EFF_OUT);
-  ws.take<char>(effnet_ws(B * T, H, W));
-  ws.take<float>(BT * 8 * hidden_);
-  ws.take<float>(2 * BT * hidden_);
-  ws.take<float>((size_t)2 * B * hidden_);
-  ws.take<char>(lstm_sync_bytes());
-  return ws.used();
+  return Workspace::bytes([&](Workspace& ws) {
+    feats_buf(ws, (size_t)B * T);
+    effnet_ws(ws, B * T, H, W);
+    lstm_bufs(ws, B, T);
+  });
 }
 
 void Acoustic::effnet(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe,
                       int* probe_dims, Workspace& ws, hipStream_t s) {
   StageTag tag("cnn");
-  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)
-    effnet_t<bf16_t>(frames, N, H, W, feats, stop_after, probe, probe_dims, ws, s);
-  else if (dtype_ == M2S_DT_BF16X3)
-    effnet_t<sp_t>(frames, N, H, W, feats, stop_after, probe, probe_dims, ws, s);
-  else
-    effnet_t<float>(frames, N, H, W, feats, stop_after, probe, probe_dims, ws, s);
+  dispatch_act(dtype_, [&](auto t) {
+    effnet_t<typename decltype(t)::type>(frames, N, H, W, feats, stop_after, probe, probe_dims, ws, s);
+  });
+}
+
+template <class Pass>  // a k x k conv of the pass's block: input oh x ow, output nh x nw
+static ConvArgs conv2d_args(const Pass& p, const PConv& pc, const void* x, void* y) {
+  ConvArgs a = conv_args(pc);
+  a.x = x;
+  a.y = y;
+  a.IH = p.oh;
+  a.IW = p.ow;
+  a.OH = p.nh;
+  a.OW = p.nw;
+  a.pad_t = p.qt;
+  a.pad_l = p.ql;
+  a.M = p.nc * p.nh * p.nw;
+  return a;
+}
+
+template <typename T>
+void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
+  const Block& b = blocks_[k];
+  ConvArgs a = conv2d_args(p, b.c1, p.cur, p.nxt);
+  a.act = ACT_SILU;
+  a.res = b.skip ? p.cur : nullptr;
+  run_conv<T>(a, b.c1, p.s);
+}
+
+template <typename T>
+void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
+  const Block& b = blocks_[k];
+  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  T *const cur = p.cur, *const nxt = p.nxt, *const M = p.b.M;
+  uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
+  hipStream_t s = p.s;
+  const double px = (double)nc * nh * nw;
+  // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
+  // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
+  // er8_fused to its in-kernel conversion)
+  uint8_t* const er8_next = X8[0] && f8_er_ && k + 1 < blocks_.size() &&
+                                    ((er8_x8_ && blocks_[k + 1].er8) || (f8_er2_ && blocks_[k + 1].er8w))
+                                ? (cur8 == X8[0] ? X8[1] : X8[0])
+                                : nullptr;
+  if (std::is_same<T, sp_t>::value && er_fused_ && b.er_sp &&
+      er_sp_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
+    launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout), arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt,
+                 2.0 * px * b.mid * (9.0 * b.cin + b.cout), 4.0 * px * (b.c1.cs_in + chan_stride(b.cout)), s, er_mrg_);
+  } else if (std::is_same<T, sp_t>::value && er_fused_ && b.ers_sp && b.stride == 2 &&
+             ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
+    launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, chan_stride(b.cout), arena_.ptr(b.er_wexp),
+                   b.c1.b, arena_.ptr(b.er_wpwl), b.c2.b, nxt, 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                   4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * chan_stride(b.cout)), s);
+  } else if (std::is_same<T, bf16_t>::value && er_fused_ && f8_er_ && b.er8 &&
+             er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
+    uint8_t* y8 = cur8 && er8_next && er8_fused_supported(nh, nw, b.cout, b.mid, b.cout) ? er8_next : nullptr;
+    launch_er8_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw, static_cast<const uint8_t*>(arena_.ptr(b.er8_wexp)),
+                     static_cast<const float*>(arena_.ptr(b.er8_sexp)), b.c1.b,
+                     static_cast<const uint8_t*>(arena_.ptr(b.er8_wpwl)), static_cast<const float*>(arena_.ptr(b.er8_spwl)),
+                     b.c2.b, reinterpret_cast<bf16_t*>(nxt), 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                     2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, cur8, y8);
+    next8 = y8;
+  } else if (std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag &&
+             er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+    launch_er_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw,
+                    static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)), b.c1.b,
+                    static_cast<const bf16_t*>(arena_.ptr(b.er_wpwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt),
+                    2.0 * px * b.mid * (9.0 * b.cin + b.cout), 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
+  } else if (std::is_same<T, bf16_t>::value && er_fused_ && f8_er_ && f8_er2_ && b.er8w && cur8 &&
+             er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
+    uint8_t* y8 = er8_next && blocks_[k + 1].er8w ? er8_next : nullptr;
+    launch_er8w_fused(reinterpret_cast<const bf16_t*>(cur), cur8, nc, nh, nw, static_cast<const uint8_t*>(arena_.ptr(b.er8w_w)),
+                      static_cast<const float*>(arena_.ptr(b.er8w_sexp)), b.c1.b,
+                      static_cast<const float*>(arena_.ptr(b.er8w_spwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt), y8,
+                      2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                      // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
+                      px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
+    next8 = y8;
+  } else if (std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag &&
+             er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+    launch_er2_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw, static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)),
+                     b.c1.b, b.c2.b, reinterpret_cast<bf16_t*>(nxt), 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                     2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
+  } else if (std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag && b.stride == 2 &&
+             ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout), b.c1.kp, b.c2.kp)) {
+    // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
+    uint8_t* y8 = er8_next && ((chan_stride(b.cout) == 32 && blocks_[k + 1].er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
+                               (chan_stride(b.cout) == 64 && blocks_[k + 1].er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
+                      ? er8_next
+                      : nullptr;
+    launch_ers2_fused(reinterpret_cast<const bf16_t*>(cur), nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid,
+                      chan_stride(b.cout), static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)), b.c1.b,
+                      static_cast<const bf16_t*>(arena_.ptr(b.er_wpwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt),
+                      2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                      2.0 * ((double)nc * oh * ow * b.c1.cs_in + px * chan_stride(b.cout)) + (y8 ? px * 32 : 0.0), s, y8);
+    next8 = y8;
+  } else {
+    ConvArgs a = conv2d_args(p, b.c1, cur, M);
+    a.act = ACT_SILU;
+    run_conv<T>(a, b.c1, s);
+    ConvArgs q = conv_args(b.c2);
+    q.x = M;
+    q.y = nxt;
+    q.M = nc * nh * nw;
+    q.OH = nh * nw;
+    q.res = b.skip ? cur : nullptr;
+    run_conv<T>(q, b.c2, s);
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
+  const Block& b = blocks_[k];
+  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  T *const cur = p.cur, *const M = p.b.M, *const M2 = p.b.M2, *const se_mean = p.b.se_mean;
+  float* const sums = p.b.sums;
+  uint8_t *&cur8 = p.cur8, *const *const X8 = p.b.X8;
+  hipStream_t s = p.s;
+  const int cs = chan_stride(b.mid);
+  constexpr bool SPL = std::is_same<T, sp_t>::value;
+  const bool FUSABLE = (std::is_same<T, bf16_t>::value && (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)) || SPL;
+  p.f8 = p.mid_f32 = false;
+  bool &f8 = p.f8, &mid_f32 = p.mid_f32;  // fp8 engine: e4m3 depthwise output -> the e4m3 SE GEMM
+  // bf16 feeds the fused kernel bf16 depthwise taps (dword halves), split fp32 the fp32 taps
+  const void* wdw = arena_.ptr(SPL ? b.dw_w : b.dw_w2);
+  const bool big = nc >= irws_min_;  // persistent ir_ws only where its one-image workgroups fill the chip
+  // the SE-gated conv_pwl runs on se_ws (effnet_ir_pwl): then ir_ws hands it the expanded map as plain fp32 rows
+  // (one 16-byte store per 4 channels, no split; se_ws gates the fp32 value before its one split)
+  const bool sews = p.sews = SPL && se_ws_ && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
+                             // se_ws runs one persistent workgroup per tile (256 rows; 128 at 8 x 8) up to one per CU:
+                             // below a full round of tiles the split-K conv_gemm SE GEMM fills the chip instead
+                             ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sews_min_cus_ * device_cus();
+  if (SPL && b.stride == 1 && ir_fused_ && ir_ws_ && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
+    const double P = (double)nh * nw;
+    launch_ir_ws(cur, nc, nh, nw, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
+                 static_cast<const float*>(arena_.ptr(b.dw_b)), M2, se_mean, 2.0 * nc * P * b.mid * (b.c1.cin + 9),
+                 // algorithmic bytes on the real channel counts (split fp32: 4 B an element): compulsory = the
+                 // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
+                 // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
+                 4.0 * nc * P * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), 1, 0, 0,
+                 0, 0, 4.0 * nc * P * b.mid, mid_f32 = sews && irws_f32_);
+  } else if (FUSABLE && b.stride == 1 && ir_fused_ && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
+    const double P = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    f8 = b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    const bool f8x = f8 && f8_expand_ && b.f8_pw && X8[0];  // the expand on e4m3 (x8 of the block input)
+    if (f8x && !cur8) {  // no e4m3 producer wrote this input: convert it
+      cur8 = X8[0];
+      launch_rows_e4m3(cur, (long)nc * nh * nw, b.c1.cs_in, cur8, b.f8x_kp, s);
+    }
+    launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, static_cast<const float*>(arena_.ptr(b.dw_b)),
+                   nh, nw, cs, M2, se_mean, SPL, 2.0 * nc * P * b.mid * (b.c1.cin + 9),
+                   nc * P * ((f8x ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid), s, f8, f8x ? cur8 : nullptr,
+                   f8x ? arena_.ptr(b.f8x_w) : nullptr, f8x ? static_cast<const float*>(arena_.ptr(b.f8x_s)) : nullptr,
+                   b.f8x_kp);
+  } else if (SPL && b.stride == 2 && ir_fused_ && ir_ws_ && ir_ws_s2_ && big &&
+             ir_ws_s2_supported(oh, ow, b.c1.cs_in, b.c1.kp, cs, nh, nw, qt, ql)) {
+    const double Pi = (double)oh * ow, Po = (double)nh * nw;
+    launch_ir_ws(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
+                 static_cast<const float*>(arena_.ptr(b.dw_b)), M2, se_mean, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
+                 4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), 2, nh, nw,
+                 qt, ql, 4.0 * nc * Po * b.mid, mid_f32 = sews && irws_f32_);
+  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
+             nh * nw <= 64) {
+    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    // fp8 engines (blocks.5.0): e4m3 depthwise output for the e4m3 SE GEMM, the expand on e4m3 as for stride 1
+    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    const bool f8x = f8 && f8_expand_ && b.f8_pw && X8[0];
+    if (f8x && !cur8) {  // no e4m3 producer wrote this input: convert it
+      cur8 = X8[0];
+      launch_rows_e4m3(cur, (long)nc * oh * ow, b.c1.cs_in, cur8, b.f8x_kp, s);
+    }
+    launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, static_cast<const float*>(arena_.ptr(b.dw_b)),
+                      oh, ow, nh, nw, qt, ql, cs, M2, se_mean, SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
+                      nc * ((f8x ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8,
+                      f8x ? cur8 : nullptr, f8x ? arena_.ptr(b.f8x_w) : nullptr,
+                      f8x ? static_cast<const float*>(arena_.ptr(b.f8x_s)) : nullptr, b.f8x_kp);
+  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_s2band_ &&
+             ir_s2band_supported(oh, ow, nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
+    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    // fp8 engines (blocks.3.0): e4m3 depthwise output for the e4m3 SE GEMM (the expand stays bf16)
+    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
+                     static_cast<const float*>(arena_.ptr(b.dw_b)), nh, nw, qt, ql, cs, M2, sums, SPL,
+                     2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
+                     nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
+    ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * ir_s2band_bands(nh) + es * nc * cs, s);
+    launch_se_mean<T>(sums, nc, ir_s2band_bands(nh), cs, 1.0f / (float)(nh * nw), se_mean, s);
+  } else {
+    ConvArgs e = conv_args(b.c1);
+    e.x = cur;
+    e.y = M;
+    e.M = nc * oh * ow;
+    e.OH = oh * ow;
+    e.act = ACT_SILU;
+    run_conv<T>(e, b.c1, s);
+    {
+      ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
+                   (sizeof(T) * Elem<T>::R) * (double)nc * (oh * ow + nh * nw) * b.mid, s);
+      launch_dwconv<T>(M, nc, oh, ow, nh, nw, b.stride, qt, ql, b.mid, cs,
+                       static_cast<const float*>(arena_.ptr(b.dw_w)), static_cast<const float*>(arena_.ptr(b.dw_b)),
+                       M2, sums, s);
+    }
+    {
+      ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * dw_pixel_blocks(nh, nw) + (sizeof(T) * Elem<T>::R) * (double)nc * cs, s);
+      launch_se_mean<T>(sums, nc, dw_pixel_blocks(nh, nw), cs, 1.0f / (float)(nh * nw), se_mean, s);
+    }
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
+  const Block& b = blocks_[k];
+  const int nc = p.nc, cs = chan_stride(b.mid);
+  T *const se_mean = p.b.se_mean, *const se_hid = p.b.se_hid, *const scale = p.b.scale;
+  hipStream_t s = p.s;
+  constexpr bool SPL = std::is_same<T, sp_t>::value;
+  const bool FUSABLE = (std::is_same<T, bf16_t>::value && (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)) || SPL;
+  if (FUSABLE && se_fused_ && se_excite_supported(b.rd, b.se2.kp, cs)) {
+    launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
+                     SPL, s);
+  } else {
+    ConvArgs r1 = conv_args(b.se1);  // conv_reduce + SiLU, all images of the chunk at once
+    r1.x = se_mean;
+    r1.y = se_hid;
+    r1.M = nc;
+    r1.act = ACT_SILU;
+    run_conv<T>(r1, b.se1, s);
+    ConvArgs r2 = conv_args(b.se2);  // conv_expand + sigmoid -> per-(image, channel) gates
+    r2.x = se_hid;
+    r2.y = scale;
+    r2.M = nc;
+    r2.act = ACT_SIGMOID;
+    run_conv<T>(r2, b.se2, s);
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
+  const Block& b = blocks_[k];
+  const int nc = p.nc, nh = p.nh, nw = p.nw, cs = chan_stride(b.mid);
+  T *const cur = p.cur, *const nxt = p.nxt, *const M2 = p.b.M2, *const scale = p.b.scale;
+  uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
+  hipStream_t s = p.s;
+  constexpr bool SPL = std::is_same<T, sp_t>::value;
+  const bool f8 = p.f8, sews = p.sews, mid_f32 = p.mid_f32;
+  // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
+  // ir_pwdw_s2, whose input map is this block's nh x nw output)
+  const bool want8 = X8[0] && f8_expand_ && k + 1 < blocks_.size() && blocks_[k + 1].f8_pw &&
+                     (blocks_[k + 1].stride == 1 ||
+                      (f8_s2_ && ir_fused_s2_supported(nh, nw, blocks_[k + 1].c1.cs_in, chan_stride(blocks_[k + 1].mid), false)));
+  // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
+  const int ld8 = want8 ? blocks_[k + 1].f8x_kp : 0;
+  if (f8 && want8 && se_y8_) next8 = cur8 == X8[0] ? X8[1] : X8[0];
+  if (f8 && se_ws_ && se_ws_f8_supported(nh * nw, cs, chan_stride(b.cout))) {
+    const double rows = (double)nc * nh * nw;
+    launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad,
+                    static_cast<const float*>(arena_.ptr(b.f8_s)), static_cast<const float*>(arena_.ptr(b.f8_b)),
+                    scale, b.skip ? cur : nullptr, nxt, chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
+                    rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
+                        (next8 ? rows * b.cout : 0.0),
+                    next8, ld8, ws_report());
+  } else if (f8) {
+    const double rows = (double)nc * nh * nw, co = chan_stride(b.cout);
+    launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad,
+                      static_cast<const float*>(arena_.ptr(b.f8_s)), static_cast<const float*>(arena_.ptr(b.f8_b)),
+                      scale, b.skip ? cur : nullptr, nxt, chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
+                      rows * cs + 2.0 * rows * co * (b.skip ? 2.0 : 1.0) + (double)b.f8_npad * b.f8_kp +
+                          2.0 * nc * cs + (next8 ? rows * ld8 : 0.0),
+                      next8, ld8);
+  } else if (sews) {
+    const double rows = (double)nc * nh * nw;
+    launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,
+                 chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
+                 4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
+                 ws_report(), mid_f32);
+  } else if (SPL && se_sp_ && se_gemm_sp_supported(nh * nw, cs, chan_stride(b.cout))) {
+    const double rows = (double)nc * nh * nw, co = chan_stride(b.cout);
+    launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,
+                      chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
+                      4.0 * rows * cs + 4.0 * rows * co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
+                          4.0 * nc * cs);
+  } else {
+    ConvArgs q = conv_args(b.c2);
+    q.x = M2;
+    q.y = nxt;
+    q.M = nc * nh * nw;
+    q.OH = nh * nw;
+    q.in_xform = IN_SE_SCALE;
+    q.in_scale = scale;
+    q.res = b.skip ? cur : nullptr;
+    run_conv<T>(q, b.c2, s);
+  }
 }
 
 template <typename T>
 void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe,
                         int* probe_dims, Workspace& ws, hipStream_t s) {
   M2S_CHECK(N > 0 && H >= 32 && W >= 32, "effnet: bad input size");
-  size_t io, mid, se;
-  effnet_dims(H, W, &io, &mid, &se);
   const int nc_max = pass_frames(N);
-  constexpr int R = Elem<T>::R;  // split fp32: hi + lo planes
-  T* A = ws.take<T>((size_t)nc_max * io * R);
-  T* Bb = ws.take<T>((size_t)nc_max * io * R);
-  T* M = ws.take<T>((size_t)nc_max * mid * R);
-  T* M2 = ws.take<T>((size_t)nc_max * mid * R);
-  float* sums = ws.take<float>((size_t)nc_max * se);
-  T* se_mean = ws.take<T>((size_t)nc_max * max_mid_cs_ * R);
-  T* se_hid = ws.take<T>((size_t)nc_max * SE_RD_MAX * R);
-  T* scale = ws.take<T>((size_t)nc_max * max_mid_cs_ * R);
-  // fp8: e4m3 copies of IR block inputs (the e4m3 expand's operand), written by the previous block's SE GEMM
-  // (y8) or converted (the expand reads no byte past cs_in of a row)
-  const size_t x8b = effnet_x8(H, W);
-  uint8_t* X8[2] = {x8b ? ws.take<uint8_t>((size_t)nc_max * x8b) : nullptr, x8b ? ws.take<uint8_t>((size_t)nc_max * x8b) : nullptr};
-
+  EffPass<T> p{};
+  p.b = effnet_bufs<T>(ws, N, H, W);
+  p.s = s;
+  T* const A = p.b.A;
+  int &oh = p.oh, &ow = p.ow;
+  T*& cur = p.cur;
   for (int n0 = 0; n0 < N; n0 += nc_max) {
     const int nc = std::min(nc_max, N - n0);
-    int oh, ow, pt, pl;
+    p.nc = nc;
+    p.n0 = n0;
+    int pt, pl;
     same_pad(H, 3, 2, &oh, &pt);
     same_pad(W, 3, 2, &ow, &pl);
     // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
@@ -642,8 +922,9 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
                        blocks_[0].cout == 16 && blocks_[0].c1.cs_in == 32 && blocks_[0].c1.kp == 288 &&
                        blocks_[1].type == 0 && blocks_[1].stride == 1 && blocks_[1].skip && blocks_[1].cout == 16 &&
                        blocks_[1].c1.cs_in == 16 && blocks_[1].c1.kp == 160 && chan_stride(16) == 16;
-    T* cur = A;
-    T* nxt = Bb;
+    cur = A;
+    p.nxt = p.b.B;
+    p.cur8 = nullptr;
     int cc = EFF_STEM;
     int bi = 0;
     if (front) {
@@ -673,267 +954,24 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     };
     if (tap(bi)) continue;  // bi = 0, or 2 after the fused front
     bool stopped = false;
-    uint8_t* cur8 = nullptr;  // fp8: the e4m3 copy of cur in X8[0] / X8[1], when one was written
     for (size_t k = front ? 2 : 0; k < blocks_.size(); ++k) {
       const Block& b = blocks_[k];
-      uint8_t* next8 = nullptr;  // the e4m3 copy of this block's output, if its SE GEMM wrote one
-      int nh, nw, qt, ql;
-      same_pad(oh, 3, b.stride, &nh, &qt);
-      same_pad(ow, 3, b.stride, &nw, &ql);
-      // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
-      // ir_pwdw_s2, whose input map is this block's nh x nw output)
-      const bool want8 = X8[0] && f8_expand_ && k + 1 < blocks_.size() && blocks_[k + 1].f8_pw &&
-                         (blocks_[k + 1].stride == 1 ||
-                          (f8_s2_ && ir_fused_s2_supported(nh, nw, blocks_[k + 1].c1.cs_in, chan_stride(blocks_[k + 1].mid), false)));
-      // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
-      // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
-      // er8_fused to its in-kernel conversion)
-      uint8_t* const er8_next = X8[0] && f8_er_ && k + 1 < blocks_.size() &&
-                                        ((er8_x8_ && blocks_[k + 1].er8) || (f8_er2_ && blocks_[k + 1].er8w))
-                                    ? (cur8 == X8[0] ? X8[1] : X8[0])
-                                    : nullptr;
-      auto a2d = [&](const PConv& pc, const void* x, void* y) {
-        ConvArgs a = conv_args(pc);
-        a.x = x;
-        a.y = y;
-        a.IH = oh;
-        a.IW = ow;
-        a.OH = nh;
-        a.OW = nw;
-        a.pad_t = qt;
-        a.pad_l = ql;
-        a.M = nc * nh * nw;
-        return a;
-      };
+      p.next8 = nullptr;  // the e4m3 copy of this block's output, if the block wrote one
+      same_pad(oh, 3, b.stride, &p.nh, &p.qt);
+      same_pad(ow, 3, b.stride, &p.nw, &p.ql);
       if (b.type == 0) {
-        ConvArgs a = a2d(b.c1, cur, nxt);
-        a.act = ACT_SILU;
-        a.res = b.skip ? cur : nullptr;
-        run_conv<T>(a, b.c1, s);
-      } else if (b.type == 1 && std::is_same<T, sp_t>::value && er_fused_ && b.er_sp &&
-                 er_sp_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
-        const double px = (double)nc * nh * nw;
-        launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout), arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt,
-                     2.0 * px * b.mid * (9.0 * b.cin + b.cout), 4.0 * px * (b.c1.cs_in + chan_stride(b.cout)), s, er_mrg_);
-      } else if (b.type == 1 && std::is_same<T, sp_t>::value && er_fused_ && b.ers_sp && b.stride == 2 &&
-                 ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
-        const double px = (double)nc * nh * nw;
-        launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, chan_stride(b.cout), arena_.ptr(b.er_wexp),
-                       b.c1.b, arena_.ptr(b.er_wpwl), b.c2.b, nxt, 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
-                       4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * chan_stride(b.cout)), s);
-      } else if (b.type == 1 && std::is_same<T, bf16_t>::value && er_fused_ && f8_er_ && b.er8 &&
-                 er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
-        const double px = (double)nc * nh * nw;
-        uint8_t* y8 = cur8 && er8_next && er8_fused_supported(nh, nw, b.cout, b.mid, b.cout) ? er8_next : nullptr;
-        launch_er8_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw, static_cast<const uint8_t*>(arena_.ptr(b.er8_wexp)),
-                         static_cast<const float*>(arena_.ptr(b.er8_sexp)), b.c1.b,
-                         static_cast<const uint8_t*>(arena_.ptr(b.er8_wpwl)), static_cast<const float*>(arena_.ptr(b.er8_spwl)),
-                         b.c2.b, reinterpret_cast<bf16_t*>(nxt), 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
-                         2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, cur8, y8);
-        next8 = y8;
-      } else if (b.type == 1 && std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag &&
-                 er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-        const double px = (double)nc * nh * nw;
-        launch_er_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw,
-                        static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)), b.c1.b,
-                        static_cast<const bf16_t*>(arena_.ptr(b.er_wpwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt),
-                        2.0 * px * b.mid * (9.0 * b.cin + b.cout), 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
-      } else if (b.type == 1 && std::is_same<T, bf16_t>::value && er_fused_ && f8_er_ && f8_er2_ && b.er8w && cur8 &&
-                 er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
-        const double px = (double)nc * nh * nw;
-        uint8_t* y8 = er8_next && blocks_[k + 1].er8w ? er8_next : nullptr;
-        launch_er8w_fused(reinterpret_cast<const bf16_t*>(cur), cur8, nc, nh, nw, static_cast<const uint8_t*>(arena_.ptr(b.er8w_w)),
-                          static_cast<const float*>(arena_.ptr(b.er8w_sexp)), b.c1.b,
-                          static_cast<const float*>(arena_.ptr(b.er8w_spwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt), y8,
-                          2.0 * px * b.mid * (9.0 * b.cin + b.cout),
-                          // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
-                          px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
-        next8 = y8;
-      } else if (b.type == 1 && std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag &&
-                 er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-        const double px = (double)nc * nh * nw;
-        launch_er2_fused(reinterpret_cast<const bf16_t*>(cur), nc, nh, nw, static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)),
-                         b.c1.b, b.c2.b, reinterpret_cast<bf16_t*>(nxt), 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
-                         2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
-      } else if (b.type == 1 && std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag && b.stride == 2 &&
-                 ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout), b.c1.kp, b.c2.kp)) {
-        const double px = (double)nc * nh * nw;
-        // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
-        uint8_t* y8 = er8_next && ((chan_stride(b.cout) == 32 && blocks_[k + 1].er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
-                                   (chan_stride(b.cout) == 64 && blocks_[k + 1].er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
-                          ? er8_next
-                          : nullptr;
-        launch_ers2_fused(reinterpret_cast<const bf16_t*>(cur), nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid,
-                          chan_stride(b.cout), static_cast<const bf16_t*>(arena_.ptr(b.er_wexp)), b.c1.b,
-                          static_cast<const bf16_t*>(arena_.ptr(b.er_wpwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt),
-                          2.0 * px * b.mid * (9.0 * b.cin + b.cout),
-                          2.0 * ((double)nc * oh * ow * b.c1.cs_in + px * chan_stride(b.cout)) + (y8 ? px * 32 : 0.0), s, y8);
-        next8 = y8;
+        effnet_cn(p, k);
       } else if (b.type == 1) {
-        ConvArgs a = a2d(b.c1, cur, M);
-        a.act = ACT_SILU;
-        run_conv<T>(a, b.c1, s);
-        ConvArgs p = conv_args(b.c2);
-        p.x = M;
-        p.y = nxt;
-        p.M = nc * nh * nw;
-        p.OH = nh * nw;
-        p.res = b.skip ? cur : nullptr;
-        run_conv<T>(p, b.c2, s);
+        effnet_er(p, k);
       } else {
-        const int cs = chan_stride(b.mid);
-        constexpr bool SPL = std::is_same<T, sp_t>::value;
-        const bool FUSABLE = (std::is_same<T, bf16_t>::value && (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)) || SPL;
-        bool f8 = false;  // fp8 engine: e4m3 depthwise output -> the e4m3 SE GEMM
-        // bf16 feeds the fused kernel bf16 depthwise taps (dword halves), split fp32 the fp32 taps
-        const void* wdw = arena_.ptr(SPL ? b.dw_w : b.dw_w2);
-        const bool big = nc >= irws_min_;  // persistent ir_ws only where its one-image workgroups fill the chip
-        // the SE-gated conv_pwl runs on se_ws (below): then ir_ws hands it the expanded map as plain fp32 rows
-        // (one 16-byte store per 4 channels, no split; se_ws gates the fp32 value before its one split)
-        const bool sews = SPL && se_ws_ && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
-                          // se_ws runs one persistent workgroup per tile (256 rows; 128 at 8 x 8) up to one per CU:
-                          // below a full round of tiles the split-K conv_gemm SE GEMM fills the chip instead
-                          ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sews_min_cus_ * device_cus();
-        bool mid_f32 = false;
-        if (SPL && b.stride == 1 && ir_fused_ && ir_ws_ && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
-          const double P = (double)nh * nw;
-          launch_ir_ws(cur, nc, nh, nw, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
-                       static_cast<const float*>(arena_.ptr(b.dw_b)), M2, se_mean, 2.0 * nc * P * b.mid * (b.c1.cin + 9),
-                       // algorithmic bytes on the real channel counts (split fp32: 4 B an element): compulsory = the
-                       // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
-                       // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
-                       4.0 * nc * P * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), 1, 0, 0,
-                       0, 0, 4.0 * nc * P * b.mid, mid_f32 = sews && irws_f32_);
-        } else if (FUSABLE && b.stride == 1 && ir_fused_ && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
-          const double P = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-          f8 = b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-          const bool f8x = f8 && f8_expand_ && b.f8_pw && X8[0];  // the expand on e4m3 (x8 of the block input)
-          if (f8x && !cur8) {  // no e4m3 producer wrote this input: convert it
-            cur8 = X8[0];
-            launch_rows_e4m3(cur, (long)nc * nh * nw, b.c1.cs_in, cur8, b.f8x_kp, s);
-          }
-          launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, static_cast<const float*>(arena_.ptr(b.dw_b)),
-                         nh, nw, cs, M2, se_mean, SPL, 2.0 * nc * P * b.mid * (b.c1.cin + 9),
-                         nc * P * ((f8x ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid), s, f8, f8x ? cur8 : nullptr,
-                         f8x ? arena_.ptr(b.f8x_w) : nullptr, f8x ? static_cast<const float*>(arena_.ptr(b.f8x_s)) : nullptr,
-                         b.f8x_kp);
-        } else if (SPL && b.stride == 2 && ir_fused_ && ir_ws_ && ir_ws_s2_ && big &&
-                   ir_ws_s2_supported(oh, ow, b.c1.cs_in, b.c1.kp, cs, nh, nw, qt, ql)) {
-          const double Pi = (double)oh * ow, Po = (double)nh * nw;
-          launch_ir_ws(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
-                       static_cast<const float*>(arena_.ptr(b.dw_b)), M2, se_mean, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
-                       4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), 2, nh, nw,
-                       qt, ql, 4.0 * nc * Po * b.mid, mid_f32 = sews && irws_f32_);
-        } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
-                   nh * nw <= 64) {
-          const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-          // fp8 engines (blocks.5.0): e4m3 depthwise output for the e4m3 SE GEMM, the expand on e4m3 as for stride 1
-          f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-          const bool f8x = f8 && f8_expand_ && b.f8_pw && X8[0];
-          if (f8x && !cur8) {  // no e4m3 producer wrote this input: convert it
-            cur8 = X8[0];
-            launch_rows_e4m3(cur, (long)nc * oh * ow, b.c1.cs_in, cur8, b.f8x_kp, s);
-          }
-          launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, static_cast<const float*>(arena_.ptr(b.dw_b)),
-                            oh, ow, nh, nw, qt, ql, cs, M2, se_mean, SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
-                            nc * ((f8x ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8,
-                            f8x ? cur8 : nullptr, f8x ? arena_.ptr(b.f8x_w) : nullptr,
-                            f8x ? static_cast<const float*>(arena_.ptr(b.f8x_s)) : nullptr, b.f8x_kp);
-        } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_s2band_ &&
-                   ir_s2band_supported(oh, ow, nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
-          const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-          // fp8 engines (blocks.3.0): e4m3 depthwise output for the e4m3 SE GEMM (the expand stays bf16)
-          f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-          launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, static_cast<const float*>(arena_.ptr(b.dw_w)),
-                           static_cast<const float*>(arena_.ptr(b.dw_b)), nh, nw, qt, ql, cs, M2, sums, SPL,
-                           2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
-                           nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
-          ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * ir_s2band_bands(nh) + es * nc * cs, s);
-          launch_se_mean<T>(sums, nc, ir_s2band_bands(nh), cs, 1.0f / (float)(nh * nw), se_mean, s);
-        } else {
-        ConvArgs e = conv_args(b.c1);
-        e.x = cur;
-        e.y = M;
-        e.M = nc * oh * ow;
-        e.OH = oh * ow;
-        e.act = ACT_SILU;
-        run_conv<T>(e, b.c1, s);
-        {
-          ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
-                       (sizeof(T) * Elem<T>::R) * (double)nc * (oh * ow + nh * nw) * b.mid, s);
-          launch_dwconv<T>(M, nc, oh, ow, nh, nw, b.stride, qt, ql, b.mid, cs,
-                           static_cast<const float*>(arena_.ptr(b.dw_w)), static_cast<const float*>(arena_.ptr(b.dw_b)),
-                           M2, sums, s);
-        }
-        {
-          ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * dw_pixel_blocks(nh, nw) + (sizeof(T) * Elem<T>::R) * (double)nc * cs, s);
-          launch_se_mean<T>(sums, nc, dw_pixel_blocks(nh, nw), cs, 1.0f / (float)(nh * nw), se_mean, s);
-        }
-        }
-        if (FUSABLE && se_fused_ && se_excite_supported(b.rd, b.se2.kp, cs)) {
-          launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
-                           SPL, s);
-        } else {
-        ConvArgs r1 = conv_args(b.se1);  // conv_reduce + SiLU, all images of the chunk at once
-        r1.x = se_mean;
-        r1.y = se_hid;
-        r1.M = nc;
-        r1.act = ACT_SILU;
-        run_conv<T>(r1, b.se1, s);
-        ConvArgs r2 = conv_args(b.se2);  // conv_expand + sigmoid -> per-(image, channel) gates
-        r2.x = se_hid;
-        r2.y = scale;
-        r2.M = nc;
-        r2.act = ACT_SIGMOID;
-        run_conv<T>(r2, b.se2, s);
-        }
-        // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
-        const int ld8 = want8 ? blocks_[k + 1].f8x_kp : 0;
-        if (f8 && want8 && se_y8_) next8 = cur8 == X8[0] ? X8[1] : X8[0];
-        if (f8 && se_ws_ && se_ws_f8_supported(nh * nw, cs, chan_stride(b.cout))) {
-          const double rows = (double)nc * nh * nw;
-          launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad,
-                          static_cast<const float*>(arena_.ptr(b.f8_s)), static_cast<const float*>(arena_.ptr(b.f8_b)),
-                          scale, b.skip ? cur : nullptr, nxt, chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
-                          rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
-                              (next8 ? rows * b.cout : 0.0),
-                          next8, ld8, ws_report());
-        } else if (f8) {
-          const double rows = (double)nc * nh * nw, co = chan_stride(b.cout);
-          launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad,
-                            static_cast<const float*>(arena_.ptr(b.f8_s)), static_cast<const float*>(arena_.ptr(b.f8_b)),
-                            scale, b.skip ? cur : nullptr, nxt, chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
-                            rows * cs + 2.0 * rows * co * (b.skip ? 2.0 : 1.0) + (double)b.f8_npad * b.f8_kp +
-                                2.0 * nc * cs + (next8 ? rows * ld8 : 0.0),
-                            next8, ld8);
-        } else if (sews) {
-          const double rows = (double)nc * nh * nw;
-          launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,
-                       chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
-                       4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
-                       ws_report(), mid_f32);
-        } else if (SPL && se_sp_ && se_gemm_sp_supported(nh * nw, cs, chan_stride(b.cout))) {
-          const double rows = (double)nc * nh * nw, co = chan_stride(b.cout);
-          launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,
-                            chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
-                            4.0 * rows * cs + 4.0 * rows * co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
-                                4.0 * nc * cs);
-        } else {
-        ConvArgs p = conv_args(b.c2);
-        p.x = M2;
-        p.y = nxt;
-        p.M = nc * nh * nw;
-        p.OH = nh * nw;
-        p.in_xform = IN_SE_SCALE;
-        p.in_scale = scale;
-        p.res = b.skip ? cur : nullptr;
-        run_conv<T>(p, b.c2, s);
-        }
+        effnet_ir_front(p, k);
+        effnet_ir_se(p, k);
+        effnet_ir_pwl(p, k);
       }
-      std::swap(cur, nxt);
-      cur8 = next8;
-      oh = nh;
-      ow = nw;
+      std::swap(cur, p.nxt);
+      p.cur8 = p.next8;
+      oh = p.nh;
+      ow = p.nw;
       cc = b.cout;
       ++bi;
       if (tap(bi)) {
@@ -985,17 +1023,26 @@ void Acoustic::lstm_recurrence(const float* pre, float* hs, float* cst, void* sy
   }
 }
 
+Acoustic::LstmBufs Acoustic::lstm_bufs(Workspace& ws, int B, int T) const {
+  const size_t BT = (size_t)B * T, H = (size_t)hidden_;
+  LstmBufs b{};
+  b.pre = ws.take<float>(BT * 8 * H);
+  b.hs = ws.take<float>(2 * BT * H);
+  b.cst = ws.take<float>((size_t)2 * B * H);
+  b.sync = ws.take<char>(lstm_sync_bytes());
+  return b;
+}
+
 void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_norm, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "bilstm: empty input");
   const int H = hidden_;
   const size_t BT = (size_t)B * T;
-  float* pre = ws.take<float>(BT * 8 * H);
-  float* hs = ws.take<float>(2 * BT * H);
-  float* cst = ws.take<float>((size_t)2 * B * H);
+  const LstmBufs b = lstm_bufs(ws, B, T);
+  float* const hs = b.hs;
   StageTag tag("bilstm");
   ConvArgs a = conv_args(lstm_ih_);
   a.x = feats;
-  a.y = pre;
+  a.y = b.pre;
   a.M = (int)BT;
   // small passes (<= 64 frames): the four waves of a row tile split K (one 30-frame clip: 20 -> 12 us); larger passes
   // keep four row groups a workgroup sharing the weight tile (K split there: the 1920-frame step's projection
@@ -1003,8 +1050,7 @@ void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_nor
   // (keyed on the projection's row count M: a ragged call of N packed rows switches where a dense one of N does)
   a.kwave = BT <= 64 ? 1 : 0;
   run_conv<float>(a, lstm_ih_, s);
-  void* sync = ws.take<char>(lstm_sync_bytes());
-  lstm_recurrence(pre, hs, cst, sync, B, T, (double)B * (T - 1), (double)BT, s);
+  lstm_recurrence(b.pre, hs, b.cst, b.sync, B, T, (double)B * (T - 1), (double)BT, s);
   if (mel_norm) {
     StageTag head("head");
     ProfScope ps("mel_head_kernel", 2.0 * BT * H * n_mels_, 4.0 * BT * (2 * H + n_mels_), s);
@@ -1014,11 +1060,9 @@ void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_nor
   if (y) launch_add2(hs, hs + BT * H, y, (long)(BT * H), s);
 }
 
-void Acoustic::forward(const float* frames, int B, int T, int H, int W, float* mel_norm, void* wsp, size_t wsb,
-                       hipStream_t s) {
+void Acoustic::forward(const float* frames, int B, int T, int H, int W, float* mel_norm, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "acoustic: empty input");
-  Workspace ws(wsp, wsb);
-  float* feats = ws.take<float>((size_t)B * T * EFF_OUT);
+  float* feats = feats_buf(ws, (size_t)B * T);
   effnet(frames, B * T, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm(feats, B, T, nullptr, mel_norm, ws, s);
 }
@@ -1057,24 +1101,14 @@ void ragged_check_stream(hipStream_t s) {
 }
 
 void RaggedTable::upload(const int* lengths, int B, int* dev, hipStream_t s) {
-  ragged_check_stream(s);
-  if (!done_) M2S_HIP(hipEventCreateWithFlags(&done_, hipEventDisableTiming));
-  M2S_HIP(hipEventSynchronize(done_));  // the previous call's copy has read the staging buffer
-  if (cap_ < (size_t)2 * B) {
-    if (host_) M2S_HIP(hipHostFree(host_));
-    host_ = nullptr;
-    cap_ = 0;
-    M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&host_), (size_t)2 * B * sizeof(int), hipHostMallocDefault));
-    cap_ = (size_t)2 * B;
-  }
+  std::vector<int> tab((size_t)2 * B);
   int off = 0;
   for (int b = 0; b < B; ++b) {
-    host_[b] = off;
-    host_[B + b] = lengths[b];
+    tab[b] = off;
+    tab[B + b] = lengths[b];
     off += lengths[b];
   }
-  M2S_HIP(hipMemcpyAsync(dev, host_, (size_t)2 * B * sizeof(int), hipMemcpyHostToDevice, s));
-  M2S_HIP(hipEventRecord(done_, s));
+  upload_ints(tab.data(), tab.size(), dev, s);
 }
 
 void RaggedTable::upload_ints(const int* src, size_t n, int* dev, hipStream_t s) {
@@ -1097,30 +1131,28 @@ size_t Acoustic::ragged_workspace_bytes(const int* lengths, int B, int H, int W)
   long n = 0;
   for (int b = 0; lengths && b < B; ++b) n += lengths[b];
   const RaggedDims d = ragged_dims(lengths, B, n);
-  const size_t BT = (size_t)B * d.Tmax;
-  Workspace ws(nullptr, 0);
-  ws.take<float>((size_t)d.N * EFF_OUT);
-  ws.take<char>(effnet_ws((int)d.N, H, W));
-  ws.take<int>((size_t)2 * B);
-  ws.take<float>((size_t)d.N * 8 * hidden_);
-  ws.take<float>(BT * 8 * hidden_);
-  ws.take<float>(2 * BT * hidden_);
-  ws.take<float>((size_t)2 * B * hidden_);
-  ws.take<char>(lstm_sync_bytes());
-  return ws.used();
+  return Workspace::bytes([&](Workspace& ws) {
+    feats_buf(ws, (size_t)d.N);
+    effnet_ws(ws, (int)d.N, H, W);
+    ragged_lstm_bufs(ws, d);
+  });
+}
+
+Acoustic::RaggedLstmBufs Acoustic::ragged_lstm_bufs(Workspace& ws, const RaggedDims& d) const {
+  RaggedLstmBufs b{};
+  b.tab = ws.take<int>((size_t)2 * d.B);
+  b.pre_packed = ws.take<float>((size_t)d.N * 8 * hidden_);
+  b.d = lstm_bufs(ws, d.B, d.Tmax);
+  return b;
 }
 
 void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long N, float* y, float* mel_norm,
                              Workspace& ws, hipStream_t s) {
   const RaggedDims d = ragged_dims(lengths, B, N);
   const int H = hidden_, T = d.Tmax;
-  const size_t BT = (size_t)B * T;
-  int* tab = ws.take<int>((size_t)2 * B);
-  float* pre_packed = ws.take<float>((size_t)N * 8 * H);
-  float* pre = ws.take<float>(BT * 8 * H);
-  float* hs = ws.take<float>(2 * BT * H);
-  float* cst = ws.take<float>((size_t)2 * B * H);
-  void* sync = ws.take<char>(lstm_sync_bytes());
+  const RaggedLstmBufs rb = ragged_lstm_bufs(ws, d);
+  int* const tab = rb.tab;
+  float *const pre_packed = rb.pre_packed, *const pre = rb.d.pre, *const hs = rb.d.hs;
   rtab_.upload(lengths, B, tab, s);
   StageTag tag("bilstm");
   ConvArgs a = conv_args(lstm_ih_);
@@ -1135,7 +1167,7 @@ void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long
   }
   // the dense kernels, Tmax steps for every clip: zero pre-activation rows keep the reverse direction's state at
   // exactly zero until the clip's last frame, and the forward direction's padded steps are never read
-  lstm_recurrence(pre, hs, cst, sync, B, T, (double)(N - B), (double)N, s);
+  lstm_recurrence(pre, hs, rb.d.cst, rb.d.sync, B, T, (double)(N - B), (double)N, s);
   StageTag head("head");
   ProfScope ps("ragged_head_gather_kernel", mel_norm ? 2.0 * N * H * n_mels_ : 0.0,
                4.0 * N * (2 * H + (mel_norm ? n_mels_ : 0) + (y ? H : 0)), s);
@@ -1144,11 +1176,10 @@ void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long
 }
 
 void Acoustic::forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm,
-                              void* wsp, size_t wsb, hipStream_t s) {
+                              Workspace& ws, hipStream_t s) {
   ragged_dims(lengths, B, N);  // before the CNN launches
   ragged_check_stream(s);
-  Workspace ws(wsp, wsb);
-  float* feats = ws.take<float>((size_t)N * EFF_OUT);
+  float* feats = feats_buf(ws, (size_t)N);
   effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm_ragged(feats, lengths, B, N, nullptr, mel_norm, ws, s);
 }
@@ -1212,13 +1243,13 @@ size_t Acoustic::windowed_workspace_bytes(const int* lengths, const int* context
   for (int b = 0; lengths && b < B; ++b) n += lengths[b];
   M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
   const WindowPlan p = window_plan(lengths, context, B, n, window, merge);
-  Workspace ws(nullptr, 0);
-  if (H != 0 || W != 0) {
-    ws.take<float>((size_t)p.N * EFF_OUT);
-    ws.take<char>(effnet_ws((int)p.N, H, W));
-  }
-  window_bufs(ws, p);
-  return ws.used();
+  return Workspace::bytes([&](Workspace& ws) {
+    if (H != 0 || W != 0) {
+      feats_buf(ws, (size_t)p.N);
+      effnet_ws(ws, (int)p.N, H, W);
+    }
+    window_bufs(ws, p);
+  });
 }
 
 void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window,
@@ -1278,12 +1309,11 @@ void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int
 }
 
 void Acoustic::forward_windowed(const float* frames, const int* lengths, const int* context, int B, long N, int H,
-                                int W, int window, int merge, float* mel_norm, void* wsp, size_t wsb, hipStream_t s) {
+                                int W, int window, int merge, float* mel_norm, Workspace& ws, hipStream_t s) {
   M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
   window_plan(lengths, context, B, N, window, merge);  // before the CNN launches
   ragged_check_stream(s);
-  Workspace ws(wsp, wsb);
-  float* feats = ws.take<float>((size_t)N * EFF_OUT);
+  float* feats = feats_buf(ws, (size_t)N);
   effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm_windowed(feats, lengths, context, B, N, window, merge, nullptr, mel_norm, ws, s);
 }
@@ -1506,100 +1536,100 @@ size_t Vocoder::act_elems(int B, int T) const {
   return m;
 }
 
+void* Vocoder::mel_in(Workspace& ws, int B, int T) const {
+  return ws.take<char>((size_t)B * T * chan_stride(h_.num_mels) * act_bytes(dtype_));
+}
+
+template <typename T>
+Vocoder::GenBufs<T> Vocoder::gen_bufs(Workspace& ws, int B, int T_) const {
+  const size_t n = act_elems(B, T_) * Elem<T>::R;
+  GenBufs<T> g{};
+  g.X = ws.take<T>(n);
+  for (T*& h : g.Hb) h = ws.take<T>(n);
+  g.T1 = ws.take<T>(n);
+  g.S = ws.take<T>(n);
+  if (dtype_ == M2S_DT_FP8) g.E8 = ws.take<T>(n);
+  if (std::is_same<T, sp_t>::value)
+    for (auto& bt : g.Bt)
+      for (T*& q : bt) q = ws.take<T>(n);
+  return g;
+}
+
+void Vocoder::gen_ws(Workspace& ws, int B, int T) const {
+  dispatch_act(dtype_, [&](auto t) { gen_bufs<typename decltype(t)::type>(ws, B, T); });
+}
+
 size_t Vocoder::workspace_bytes(int B, int T) const {
-  const size_t es = act_bytes(dtype_);
-  Workspace ws(nullptr, 0);
-  ws.take<char>((size_t)B * T * chan_stride(h_.num_mels) * es);
-  for (int i = 0; i < act_buffers(); ++i) ws.take<char>(act_elems(B, T) * es);
-  return ws.used();
+  return Workspace::bytes([&](Workspace& ws) {
+    mel_in(ws, B, T);
+    gen_ws(ws, B, T);
+  });
 }
 
 void Vocoder::forward(const float* mel, int layout, int B, int T, float* wav, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "vocoder: empty input");
-  const int cs = chan_stride(h_.num_mels);
-  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8) {
-    bf16_t* mn = ws.take<bf16_t>((size_t)B * T * cs);
-    launch_mel_to_nlc<bf16_t>(mel, B, h_.num_mels, T, layout, mn, cs, s);
-    run_t<bf16_t>(mn, B, T, wav, ws, s);
-  } else if (dtype_ == M2S_DT_BF16X3) {
-    sp_t* mn = ws.take<sp_t>((size_t)B * T * cs * 2);
-    launch_mel_to_nlc<sp_t>(mel, B, h_.num_mels, T, layout, mn, cs, s);
-    run_t<sp_t>(mn, B, T, wav, ws, s);
-  } else {
-    float* mn = ws.take<float>((size_t)B * T * cs);
-    launch_mel_to_nlc<float>(mel, B, h_.num_mels, T, layout, mn, cs, s);
-    run_t<float>(mn, B, T, wav, ws, s);
-  }
+  void* mn = mel_in(ws, B, T);
+  dispatch_act(dtype_, [&](auto t) {
+    using A = typename decltype(t)::type;
+    launch_mel_to_nlc<A>(mel, B, h_.num_mels, T, layout, static_cast<A*>(mn), chan_stride(h_.num_mels), s);
+    run_t<A>(mn, B, T, wav, ws, s);
+  });
 }
 
 void Vocoder::forward_from_norm(const float* mel_norm, const float* mean, const float* std_, int B, int T,
                                 float* mel_db, float* mel_log, void* ln_buf, float* wav, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "vocoder: empty input");
   const int nm = h_.num_mels, cs = chan_stride(nm);
-  ws.take<char>((size_t)B * T * cs * act_bytes(dtype_));  // same carve as forward()
+  mel_in(ws, B, T);  // unused here (the input is ln_buf): the generator's buffers sit where forward() puts them
   StageTag tag("glue");
-  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8) {
-    ProfScope ps("mel_glue_kernel<unsigned short>", 0.0, 4.0 * B * T * nm * 4, s);
-    launch_mel_glue<bf16_t>(mel_norm, B * T, nm, mean, std_, mel_db, mel_log, static_cast<bf16_t*>(ln_buf), cs, s);
-  } else if (dtype_ == M2S_DT_BF16X3) {
-    ProfScope ps("mel_glue_kernel<m2s::sp_t>", 0.0, 4.0 * B * T * nm * 4, s);
-    launch_mel_glue<sp_t>(mel_norm, B * T, nm, mean, std_, mel_db, mel_log, static_cast<sp_t*>(ln_buf), cs, s);
-  } else {
-    ProfScope ps("mel_glue_kernel<float>", 0.0, 4.0 * B * T * nm * 4, s);
-    launch_mel_glue<float>(mel_norm, B * T, nm, mean, std_, mel_db, mel_log, static_cast<float*>(ln_buf), cs, s);
-  }
-  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)
-    run_t<bf16_t>(ln_buf, B, T, wav, ws, s);
-  else if (dtype_ == M2S_DT_BF16X3)
-    run_t<sp_t>(ln_buf, B, T, wav, ws, s);
-  else
-    run_t<float>(ln_buf, B, T, wav, ws, s);
+  dispatch_act(dtype_, [&](auto t) {
+    using A = typename decltype(t)::type;
+    {
+      ProfScope ps(tname<A>("mel_glue_kernel"), 0.0, 4.0 * B * T * nm * 4, s);
+      launch_mel_glue<A>(mel_norm, B * T, nm, mean, std_, mel_db, mel_log, static_cast<A*>(ln_buf), cs, s);
+    }
+    run_t<A>(ln_buf, B, T, wav, ws, s);
+  });
 }
 
-// Ragged batches.  Workspace: clip table, padded ln-mel, padded wav, then run_t's buffers for (B, Tmax).
+// Ragged batches.  Workspace: clip table, padded ln-mel, padded wav, then the generator's buffers for (B, Tmax).
+Vocoder::RaggedBufs Vocoder::ragged_bufs(Workspace& ws, int B, int Tmax) const {
+  RaggedBufs b{};
+  b.tab = ws.take<int>((size_t)2 * B);
+  b.ln_buf = mel_in(ws, B, Tmax);
+  b.wav_pad = ws.take<float>((size_t)B * Tmax * hop_);
+  return b;
+}
+
 size_t Vocoder::ragged_workspace_bytes(const int* lengths, int B) const {
   long n = 0;
   for (int b = 0; lengths && b < B; ++b) n += lengths[b];
   const RaggedDims d = ragged_dims(lengths, B, n);
-  const size_t es = act_bytes(dtype_);
-  Workspace ws(nullptr, 0);
-  ws.take<int>((size_t)2 * B);
-  ws.take<char>((size_t)B * d.Tmax * chan_stride(h_.num_mels) * es);
-  ws.take<float>((size_t)B * d.Tmax * hop_);
-  for (int i = 0; i < act_buffers(); ++i) ws.take<char>(act_elems(B, d.Tmax) * es);
-  return ws.used();
+  return Workspace::bytes([&](Workspace& ws) {
+    ragged_bufs(ws, B, d.Tmax);
+    gen_ws(ws, B, d.Tmax);
+  });
 }
 
 void Vocoder::ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
                          float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s) {
   const RaggedDims d = ragged_dims(lengths, B, N);
   const int nm = h_.num_mels, cs = chan_stride(nm), T = d.Tmax;
-  int* tab = ws.take<int>((size_t)2 * B);
-  void* ln_buf = ws.take<char>((size_t)B * T * cs * act_bytes(dtype_));
-  float* wav_pad = ws.take<float>((size_t)B * T * hop_);
+  const RaggedBufs rb = ragged_bufs(ws, B, T);
+  int* const tab = rb.tab;
+  float* const wav_pad = rb.wav_pad;
   rtab_.upload(lengths, B, tab, s);
   // the masks write only where a clip is shorter than Tmax: with equal lengths the generator runs as the dense call
   const int* mask_tab = d.Tmin < T ? tab : nullptr;
-  {
-    StageTag tag("glue");
-    const double bytes = 4.0 * N * nm * (mean ? 4 : 2);
-    if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8) {
-      ProfScope ps("ragged_glue_kernel<unsigned short>", 0.0, bytes, s);
-      launch_ragged_glue<bf16_t>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<bf16_t*>(ln_buf), cs, s);
-    } else if (dtype_ == M2S_DT_BF16X3) {
-      ProfScope ps("ragged_glue_kernel<m2s::sp_t>", 0.0, bytes, s);
-      launch_ragged_glue<sp_t>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<sp_t*>(ln_buf), cs, s);
-    } else {
-      ProfScope ps("ragged_glue_kernel<float>", 0.0, bytes, s);
-      launch_ragged_glue<float>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<float*>(ln_buf), cs, s);
+  dispatch_act(dtype_, [&](auto t) {
+    using A = typename decltype(t)::type;
+    {
+      StageTag tag("glue");
+      ProfScope ps(tname<A>("ragged_glue_kernel"), 0.0, 4.0 * N * nm * (mean ? 4 : 2), s);
+      launch_ragged_glue<A>(x, tab, B, T, nm, mean, std_, mel_db, mel_log, static_cast<A*>(rb.ln_buf), cs, s);
     }
-  }
-  if (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)
-    run_t<bf16_t>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
-  else if (dtype_ == M2S_DT_BF16X3)
-    run_t<sp_t>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
-  else
-    run_t<float>(ln_buf, B, T, wav_pad, ws, s, mask_tab);
+    run_t<A>(rb.ln_buf, B, T, wav_pad, ws, s, mask_tab);
+  });
   StageTag tag("voc_post");
   ProfScope ps("ragged_wav_pack_kernel", 0.0, 2.0 * 4.0 * N * hop_, s);
   launch_ragged_wav_pack(wav_pad, tab, B, T, hop_, wav, s);
@@ -1618,9 +1648,6 @@ void Vocoder::forward_from_norm_ragged(const float* mel_norm, const float* mean,
 }
 
 constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right pad of 6 (launch_conv_post)
-
-// split: + the batched stages' per-resblock buffers; fp8: + one for the e4m3 pair outputs (run_t)
-int Vocoder::act_buffers() const { return dtype_ == M2S_DT_BF16X3 ? 5 + 3 * CONV_BATCH : dtype_ == M2S_DT_FP8 ? 6 : 5; }
 
 // Split-fp32 ResBlock1 stage with the resblocks batched (conv_gemm batch launches, grid.z = resblock):
 // X holds a0 = lrelu(x) (the upsampler's epilogue applied it), so no conv re-applies LeakyReLU to its
@@ -1716,16 +1743,9 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     ProfScope ps("ragged_tail_mask_kernel", 0.0, (double)B * halo * row_bytes, s);
     launch_ragged_tail_mask(S, tab, B, L, L / Tn, halo, row_bytes, s);
   };
-  const size_t n = act_elems(B, Tn) * Elem<T>::R;
-  T* X = ws.take<T>(n);
-  T* Hb[2] = {ws.take<T>(n), ws.take<T>(n)};
-  T* T1 = ws.take<T>(n);
-  T* S = ws.take<T>(n);
-  T* E8 = dtype_ == M2S_DT_FP8 ? ws.take<T>(n) : nullptr;  // fp8: e4m3 outputs of the C = 128 / 256 MRF pairs
-  T* Bt[CONV_BATCH][3] = {};  // split: per resblock, c1 output and the pair outputs (ping-pong)
-  if (SPL)
-    for (int j = 0; j < CONV_BATCH; ++j)
-      for (int q = 0; q < 3; ++q) Bt[j][q] = ws.take<T>(n);
+  const GenBufs<T> g = gen_bufs<T>(ws, B, Tn);
+  T *const X = g.X, *const *const Hb = g.Hb, *const T1 = g.T1, *const S = g.S, *const E8 = g.E8;
+  T* const(*Bt)[3] = g.Bt;
   int L = Tn;
   const int nk = h_.n_kernels;
   auto is_batched = [&](int i) {  // stage i's MRF runs as batched split launches (mrf_stage_batched)
@@ -1892,6 +1912,29 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
   ProfScope ps(tname<T>(post_c_ <= 64 ? "conv_post_tile_kernel" : "conv_post_kernel"), 2.0 * B * L * post_c_ * 7, (sizeof(T) * Elem<T>::R) * (double)B * L * post_c_ + 4.0 * B * L, s);
   launch_conv_post<T>(S, B, L, post_c_, chan_stride(post_c_), static_cast<const float*>(arena_.ptr(post_w_)), post_b_,
                       wav, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// Pipeline scratch (capi.cpp: the size queries and m2s_pipeline_forward(_ragged))
+PipelineBufs pipeline_bufs(Workspace& ws, const Acoustic& a, const Vocoder& v, int B, int T, int H, int W) {
+  const size_t rows = (size_t)B * T;
+  PipelineBufs b{};
+  b.mn = ws.take<float>(rows * a.n_mels());
+  b.ln_t = ws.take<char>(rows * chan_stride(a.n_mels()) * 4);
+  b.rest_bytes = std::max(a.workspace_bytes(B, T, H, W), v.workspace_bytes(B, T));
+  b.rest = ws.take<char>(b.rest_bytes);
+  return b;
+}
+
+PipelineBufs pipeline_ragged_bufs(Workspace& ws, const Acoustic& a, const Vocoder& v, const int* lengths, int B, int H,
+                                  int W) {
+  PipelineBufs b{};
+  b.rest_bytes = std::max(a.ragged_workspace_bytes(lengths, B, H, W), v.ragged_workspace_bytes(lengths, B));
+  size_t rows = 0;
+  for (int i = 0; i < B; ++i) rows += (size_t)lengths[i];
+  b.mn = ws.take<float>(rows * a.n_mels());
+  b.rest = ws.take<char>(b.rest_bytes);
+  return b;
 }
 
 }  // namespace m2s

@@ -72,12 +72,34 @@ class Workspace {  // bump allocator over a caller-provided device buffer
     return base_ ? reinterpret_cast<T*>(base_ + off) : nullptr;
   }
   size_t used() const { return (used_ + 255) & ~size_t(255); }
+  // what a layout function takes: the answer of a size query (the pointers it returns are null)
+  template <class F>
+  static size_t bytes(F&& layout) {
+    Workspace ws(nullptr, 0);
+    layout(ws);
+    return ws.used();
+  }
 
  private:
   char* base_;
   size_t cap_;
   size_t used_ = 0;
 };
+
+// Scratch layouts: each entry point's scratch is laid out by one `*_bufs(Workspace&, shape)` function that only takes
+// and returns typed pointers; the call runs it on the caller's buffer, the size query through Workspace::bytes.
+
+// f(ActTag<T>{}) with the activation storage type of an engine dtype: bf16_t (bf16, fp8), sp_t (bf16x3) or float
+template <typename T>
+struct ActTag {
+  using type = T;
+};
+template <class F>
+auto dispatch_act(int dtype, F&& f) {
+  if (dtype == M2S_DT_BF16 || dtype == M2S_DT_FP8) return f(ActTag<bf16_t>{});
+  if (dtype == M2S_DT_BF16X3) return f(ActTag<sp_t>{});
+  return f(ActTag<float>{});
+}
 
 // Ragged batches (ragged.hip): `lengths[B]` host integers >= 1, N = sum(lengths) packed rows, Tmax = max.
 struct RaggedDims {
@@ -100,8 +122,8 @@ class RaggedTable {
   RaggedTable(const RaggedTable&) = delete;
   RaggedTable& operator=(const RaggedTable&) = delete;
   ~RaggedTable();
-  void upload(const int* lengths, int B, int* dev, hipStream_t s);
-  // any table of n ints through the same staging buffer (the windowed calls' five-column clip table)
+  void upload(const int* lengths, int B, int* dev, hipStream_t s);  // [off | len] through upload_ints
+  // any table of n ints through the staging buffer (the windowed calls' five-column clip table)
   void upload_ints(const int* src, size_t n, int* dev, hipStream_t s);
 
  private:
@@ -180,7 +202,7 @@ class Acoustic {
   // (the M2S_* switches are read once, when the engine is created: A/B tests of fused vs unfused)
 
   size_t workspace_bytes(int B, int T, int H, int W) const;
-  void forward(const float* frames, int B, int T, int H, int W, float* mel_norm, void* ws, size_t wsb, hipStream_t s);
+  void forward(const float* frames, int B, int T, int H, int W, float* mel_norm, Workspace& ws, hipStream_t s);
   void effnet(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
               Workspace& ws, hipStream_t s);
   void bilstm(const float* feats, int B, int T, float* y, float* mel_norm, Workspace& ws, hipStream_t s);
@@ -189,8 +211,8 @@ class Acoustic {
   size_t ragged_workspace_bytes(const int* lengths, int B, int H, int W) const;
   void bilstm_ragged(const float* feats, const int* lengths, int B, long N, float* y, float* mel_norm, Workspace& ws,
                      hipStream_t s);
-  void forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm, void* ws,
-                      size_t wsb, hipStream_t s);
+  void forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm,
+                      Workspace& ws, hipStream_t s);
   // Sliding windows of `window` frames over packed clips (m2s.h "windowed inference"): packed feats (N, 208) /
   // frames (N, H, W) -> y (R, hidden), mel_norm (R, n_mels), R = N - sum(context).  H = W = 0 in the query: the
   // BiLSTM part alone (bilstm_windowed's exact size).
@@ -199,7 +221,7 @@ class Acoustic {
   void bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window, int merge,
                        float* y, float* mel_norm, Workspace& ws, hipStream_t s);
   void forward_windowed(const float* frames, const int* lengths, const int* context, int B, long N, int H, int W,
-                        int window, int merge, float* mel_norm, void* ws, size_t wsb, hipStream_t s);
+                        int window, int merge, float* mel_norm, Workspace& ws, hipStream_t s);
 
  private:
   struct WindowBufs {
@@ -208,8 +230,44 @@ class Acoustic {
     float *pre = nullptr, *c = nullptr, *hm = nullptr, *hf = nullptr;
     void* hop[2] = {nullptr, nullptr};
   };
-  // the one carve of a windowed call's BiLSTM scratch, shared by the size query and the call
   WindowBufs window_bufs(Workspace& ws, const WindowPlan& p) const;
+  template <typename T>
+  struct EffBufs {  // one CNN pass of pass_frames(N) frames
+    T *A, *B, *M, *M2, *se_mean, *se_hid, *scale;  // ... SE means, hidden (rd <= 64), gates
+    float* sums;
+    // fp8: e4m3 copies of IR block inputs (the e4m3 expand's operand), written by the previous block's SE GEMM
+    // (y8) or converted (the expand reads no byte past cs_in of a row)
+    uint8_t* X8[2];
+  };
+  template <typename T>
+  EffBufs<T> effnet_bufs(Workspace& ws, int N, int H, int W) const;
+  void effnet_ws(Workspace& ws, int N, int H, int W) const;  // effnet_bufs of the engine's dtype
+  float* feats_buf(Workspace& ws, size_t rows) const;         // precedes the CNN in the forward* calls
+  struct LstmBufs {
+    float *pre, *hs, *cst;
+    void* sync;
+  };
+  LstmBufs lstm_bufs(Workspace& ws, int B, int T) const;
+  struct RaggedLstmBufs {
+    int* tab;
+    float* pre_packed;
+    LstmBufs d;  // the dense set at (B, Tmax)
+  };
+  RaggedLstmBufs ragged_lstm_bufs(Workspace& ws, const RaggedDims& d) const;
+  // One CNN pass at one block: frames n0 .. n0 + nc, input (oh x ow) and output (nh x nw, TF-SAME pads qt / ql)
+  // geometry.  A block function reads cur (fp8: and cur8, its e4m3 copy in X8[0] / X8[1] when one was written),
+  // writes nxt and sets next8 if it wrote an e4m3 copy; the loop then advances them.
+  template <typename T>
+  struct EffPass {
+    EffBufs<T> b;
+    hipStream_t s;
+    int nc, n0, oh, ow, nh, nw, qt, ql;
+    T *cur, *nxt;
+    uint8_t *cur8, *next8;
+    // an InvertedResidual block's front half to its gated conv_pwl: e4m3 depthwise output -> the e4m3 SE GEMM; the
+    // conv_pwl runs on se_ws; ... and ir_ws handed it plain fp32 rows
+    bool f8, sews, mid_f32;
+  };
   size_t whh_win_ = 0;  // W_hh in lstm_window.hip's row order (pack_lstm_window_whh)
   // the recurrence kernel for (B, T): the selection ladder shared by bilstm and bilstm_ragged.  seq_steps / rows:
   // the recurrent steps and (b, t) rows that count as algorithmic work (a ragged call: the valid ones)
@@ -248,7 +306,18 @@ class Acoustic {
   template <typename T>
   void effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
                 Workspace& ws, hipStream_t s);
-  size_t effnet_ws(int N, int H, int W) const;
+  // block k of a pass: ConvBnAct, EdgeResidual, and InvertedResidual as front half (expand + depthwise + SE mean),
+  // SE gates and the gated conv_pwl
+  template <typename T>
+  void effnet_cn(EffPass<T>& p, size_t k);
+  template <typename T>
+  void effnet_er(EffPass<T>& p, size_t k);
+  template <typename T>
+  void effnet_ir_front(EffPass<T>& p, size_t k);
+  template <typename T>
+  void effnet_ir_se(EffPass<T>& p, size_t k);
+  template <typename T>
+  void effnet_ir_pwl(EffPass<T>& p, size_t k);
   int pass_frames(int N) const;
   size_t effnet_x8(int H, int W) const;  // fp8 engines: bytes per image of an e4m3 expand-operand buffer
   void effnet_dims(int H, int W, size_t* io_elems, size_t* mid_elems, size_t* se_elems) const;
@@ -302,11 +371,27 @@ class Vocoder {
   // conv_post then gets the rows its consumer reads past a clip's end zeroed (launch_ragged_tail_mask)
   template <typename T>
   void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab = nullptr);
+  template <typename T>
+  struct GenBufs {  // the generator's activation buffers, act_elems(B, T) each
+    T *X, *Hb[2], *T1, *S;
+    T* E8;                 // fp8: e4m3 outputs of the C = 128 / 256 MRF pairs
+    T* Bt[CONV_BATCH][3];  // split: per resblock, c1 output and the pair outputs (ping-pong)
+  };
+  template <typename T>
+  GenBufs<T> gen_bufs(Workspace& ws, int B, int T_) const;
+  void gen_ws(Workspace& ws, int B, int T) const;  // gen_bufs of the engine's dtype
+  // the channel-last generator input, rows x cs(num_mels) activation elements
+  void* mel_in(Workspace& ws, int B, int T) const;
+  struct RaggedBufs {  // a ragged call's prefix: clip table, padded ln-mel, padded wav; then gen_bufs at (B, Tmax)
+    int* tab;
+    void* ln_buf;
+    float* wav_pad;
+  };
+  RaggedBufs ragged_bufs(Workspace& ws, int B, int Tmax) const;
   void ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
                   float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
   template <typename T>
   void mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out, hipStream_t s);
-  int act_buffers() const;  // activation buffers of act_elems() each in the workspace
   struct RB {
     int k = 3;
     std::vector<int> dil;
@@ -337,5 +422,17 @@ class Vocoder {
   float post_b_ = 0.f;
   int post_c_ = 0;
 };
+
+// The pipeline calls' scratch: mel_norm (rows, n_mels), the dense call's channel-last vocoder input (4 bytes an
+// element in every dtype), then `rest` (the larger of the two engines' queries): the acoustic model's, then the vocoder's
+struct PipelineBufs {
+  float* mn;
+  void* ln_t;
+  char* rest;
+  size_t rest_bytes;
+};
+PipelineBufs pipeline_bufs(Workspace& ws, const Acoustic& a, const Vocoder& v, int B, int T, int H, int W);
+PipelineBufs pipeline_ragged_bufs(Workspace& ws, const Acoustic& a, const Vocoder& v, const int* lengths, int B, int H,
+                                  int W);
 
 }  // namespace m2s

@@ -416,8 +416,9 @@ def test_bilstm_summerge_ragged(shared, ac_sd, dtype):
     _per_clip(f"{what} mel_norm", rep.outs["nan"]["mel_norm"].cpu().numpy(), lens, 64, [d[1] for d in dense], 1e-4)
 
 
-@pytest.mark.parametrize("dtype", EXACT)
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_vocoder_forward_ragged(shared, gen_sd, dtype):
+    """Every dtype: the ragged query counts the fp8 engine's sixth buffer and the split engine's per-resblock ones."""
     lens = [17, 1, 9]
     key, voc = _vocoder(shared, gen_sd, dtype)
     mels = [np.ascontiguousarray(synth.synth_mel_log(1, 64, n, seed=40 + 11 * b)[0].T) for b, n in enumerate(lens)]
@@ -430,12 +431,13 @@ def test_vocoder_forward_ragged(shared, gen_sd, dtype):
                                             _stream())
 
     what = f"vocoder_forward_ragged {dtype} {lens}"
-    rep = _run(shared, key, what, arena, call, tol={"wav": 1e-4})
-    dense = [voc.forward(torch.from_numpy(m[None]).to(DEV), layout=1) for m in mels]
-    _per_clip(what, rep.outs["nan"]["wav"].cpu().numpy(), lens, voc.hop, dense, 1e-4)
+    rep = _run(shared, key, what, arena, call, tol={"wav": 1e-4} if dtype in EXACT else LOOSE_TOL)
+    if dtype in EXACT:
+        dense = [voc.forward(torch.from_numpy(m[None]).to(DEV), layout=1) for m in mels]
+        _per_clip(what, rep.outs["nan"]["wav"].cpu().numpy(), lens, voc.hop, dense, 1e-4)
 
 
-@pytest.mark.parametrize("dtype", EXACT)
+@pytest.mark.parametrize("dtype", DTYPES)
 def test_pipeline_forward_ragged(shared, ac_sd, gen_sd, dtype):
     from m2s import runtime
     lens, (H_, W_) = [5, 1, 3], (96, 80)
@@ -455,12 +457,22 @@ def test_pipeline_forward_ragged(shared, ac_sd, gen_sd, dtype):
                                              a.ptr("wav"), a.ptr("ws"), n, _stream())
 
     what = f"pipeline_forward_ragged {dtype} {lens}"
-    rep = _run(shared, ("pipe", dtype), what, arena, call, _ac_status(ac), E2E_TOL)
+    rep = _run(shared, ("pipe", dtype), what, arena, call, _ac_status(ac), E2E_TOL if dtype in EXACT else LOOSE_TOL)
+    if dtype not in EXACT:
+        return
     pipe = runtime.Pipeline(ac, voc, mean, std)
     dense = [pipe.forward(torch.from_numpy(c[None]).to(DEV)) for c in clips]
     for n, atol in E2E_TOL.items():
         _per_clip(f"{what} {n}", rep.outs["nan"][n].cpu().numpy(), lens, voc.hop if n == "wav" else 64,
                   [d[n] for d in dense], atol)
+
+
+def test_size_queries_return_zero_for_null_handles():
+    """The dense size queries, like every other one (include/m2s.h): 0 for a null handle, and no engine is needed."""
+    L = _lib()
+    assert L.m2s_acoustic_workspace_bytes(None, 2, 3, 64, 64) == 0
+    assert L.m2s_vocoder_workspace_bytes(None, 2, 3) == 0
+    assert L.m2s_pipeline_workspace_bytes(None, None, 2, 3, 64, 64) == 0
 
 
 # ------------------------------------------------------------------------------------------ Grad-CAM path
