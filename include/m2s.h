@@ -253,6 +253,37 @@ int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const in
                                   int rows, int H, int W, int window, int merge, float* mel_norm, void* ws,
                                   size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------ streaming vocoder ---- */
+/* The generator of this reference has causal resblocks; it looks ahead only through conv_pre's and conv_post's right
+ * pad of 6 and through the transposed convs.  So output frame o (hop samples) depends on mel rows o - back ..
+ * o + ahead only: the generator's REACH, a property of the config alone (interval propagation over rates, kernels
+ * and dilations; m2s.config.generator_reach is the same rule).  The shipped config has reach (16, 7), resblock "2"
+ * with dilations [1, 3] has (6, 7).  `ahead` rows is the algorithmic latency of streaming this model: 7 rows of 420
+ * samples at 11413 Hz = 258 ms for the shipped config, whatever the hardware. */
+int m2s_vocoder_reach(const m2s_vocoder* v, int* back, int* ahead);
+/* One stateless chunk call, ADDITIVE (DESIGN.md "Streaming vocoder").  mel (rows, num_mels) ln-mel, packed as in the
+ * ragged calls; `lengths`, `context`, `hold` are HOST arrays of B ints.  With G(x_b) = the generator on clip b's
+ * lengths[b] rows as a whole clip (what m2s_vocoder_forward_ragged computes: both ends of the span are clip ends),
+ * the call writes, packed in clip order,
+ *     G(x_b)[context[b] * hop : (lengths[b] - hold[b]) * hop]
+ * so wav has out_rows * hop samples, out_rows = sum(lengths[b] - context[b] - hold[b]).  Rows in context and hold
+ * are read but get no output.  No state crosses a call.  The emitted rows are the rows of the WHOLE clip the span
+ * was cut from if (context[b] >= back or the span starts at the clip's first row) and (hold[b] >= ahead or the span
+ * ends at the clip's last row): keep the last back + ahead mel rows of a stream and every chunking of a clip gives
+ * the whole clip's waveform (to rounding: a kernel's summation plan may depend on the row count).
+ * Between stages the call drops the rows no emitted sample depends on (the cone; whole mel rows of every clip, on
+ * the left only if every clip has context >= back, on the right only if every clip has hold >= ahead).  That
+ * changes the work, never the contract; m2s_vocoder_set_chunk_cone(v, 0) turns it off, for tests and timing.
+ * M2S_E_ARG, before any launch: B < 1, a length < 1, context[b] < 0, hold[b] < 0, context[b] + hold[b] >=
+ * lengths[b], sum(lengths) != rows, null context or hold.  M2S_E_STATE if `stream` is capturing (the clip table is
+ * staged per call, as in the ragged calls).  The workspace contract above applies as written; the query is exact to
+ * the granule, and returns 0 for arguments the call would reject. */
+int m2s_vocoder_set_chunk_cone(m2s_vocoder* v, int on);
+size_t m2s_vocoder_chunk_workspace_bytes(const m2s_vocoder* v, const int* lengths, const int* context, const int* hold,
+                                         int B);
+int m2s_vocoder_forward_chunk(m2s_vocoder* v, const float* mel, const int* lengths, const int* context, const int* hold,
+                              int B, int rows, float* wav, void* ws, size_t ws_bytes, void* stream);
+
 /* ------------------------------------------------------- Grad-CAM (autograd) path ---- */
 /* compute_gradcam (scripts/mri_gradcam_formant.py:203-279) runs the model in train() and back-
  * propagates a mel-band power to the last feature map.  These entry points are that path, exact

@@ -332,6 +332,35 @@ int m2s_vocoder_forward_ragged(m2s_vocoder* v, const float* mel, const int* leng
   });
 }
 
+int m2s_vocoder_reach(const m2s_vocoder* v, int* back, int* ahead) {
+  return guarded([&] {
+    M2S_CHECK(v && back && ahead, "null argument");
+    v->impl.reach(back, ahead);
+  });
+}
+
+int m2s_vocoder_set_chunk_cone(m2s_vocoder* v, int on) {
+  return guarded([&] {
+    M2S_CHECK(v, "null argument");
+    v->impl.chunk_cone_ = on != 0;
+  });
+}
+
+size_t m2s_vocoder_chunk_workspace_bytes(const m2s_vocoder* v, const int* lengths, const int* context, const int* hold,
+                                         int B) {
+  return size_query(v, [&] { return v->impl.chunk_workspace_bytes(lengths, context, hold, B); });
+}
+
+int m2s_vocoder_forward_chunk(m2s_vocoder* v, const float* mel, const int* lengths, const int* context, const int* hold,
+                              int B, int rows, float* wav, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(v && mel && wav && ws, "null argument");
+    DeviceGuard g(v->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    v->impl.forward_chunk(mel, lengths, context, hold, B, rows, wav, w, S(stream));
+  });
+}
+
 size_t m2s_pipeline_ragged_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, const int* lengths, int B,
                                            int H, int W) {
   return size_query(m && v, [&] {

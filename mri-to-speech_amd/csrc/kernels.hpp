@@ -340,6 +340,16 @@ void launch_ragged_tail_mask(void* x, const int* tab, int B, int rows, int scale
 void launch_ragged_wav_pack(const float* wav_padded, const int* tab, int B, int Tmax, int hop, float* wav,
                             hipStream_t s);
 
+// Streaming vocoder (vocoder_chunk.hip): the chunk call's glue between the dense generator kernels.
+// x (B, rows_in, row_bytes) -> y (B, rows_out, row_bytes), y[b][r] = x[b][drop + r]; a row = row_bytes contiguous
+// bytes in any activation storage (a multiple of 16, as in launch_ragged_tail_mask); drop + rows_out <= rows_in
+void launch_crop_rows(const void* x, int B, long rows_in, long drop, long rows_out, size_t row_bytes, void* y,
+                      hipStream_t s);
+// padded wav (B, T * hop) -> the packed emitted rows: clip b's rows src[b] .. src[b] + n[b] - 1 go to packed rows
+// dst[b] ..., hop samples a row; src / dst / n = device arrays of B ints
+void launch_chunk_wav_pack(const float* wav_padded, const int* src, const int* dst, const int* n, int B, int T, int hop,
+                           float* wav, hipStream_t s);
+
 // (rows, cs) T -> (rows, C) fp32 dense (debug taps)
 template <typename T>
 void launch_unpad(const T* x, long rows, int C, int cs, float* y, hipStream_t s);

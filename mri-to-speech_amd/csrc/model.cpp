@@ -1524,6 +1524,30 @@ Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int dev
         f.bp = static_cast<const float*>(arena_.ptr(f.b));
       }
   }
+  // Reach (m2s.config.generator_reach is the same rule): the interval of input positions that output frame 0, the
+  // samples 0 .. hop - 1, depends on, carried from the waveform back to the mel.  conv_post and conv_pre read 6
+  // positions ahead; a causal MRF stage reads sum((k - 1) d [+ (k - 1) for ResBlock1's second conv]) positions
+  // back, the largest over its kernel sizes; a transposed conv of rate u, kernel k, padding p reads inputs
+  // ceil((n + p - k + 1) / u) .. floor((n + p) / u) for output n.  Level l is the input of upsampler l.
+  auto fdiv = [](long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+  long lo = 0, hi = hop_ - 1 + 6, scale = hop_;
+  for (int i = h.n_up - 1; i >= 0; --i) {
+    long mrf = 0;
+    for (int j = 0; j < h.n_kernels; ++j) {
+      long r = 0;
+      for (int d = 0; d < h.n_dilations[j]; ++d)
+        r += (long)(h.resblock_kernel_sizes[j] - 1) * (h.resblock_dilation_sizes[j][d] + (h.resblock == 1 ? 1 : 0));
+      mrf = std::max(mrf, r);
+    }
+    const long u = h.upsample_rates[i], k = h.upsample_kernel_sizes[i], p = (k - u) / 2;
+    lo = -fdiv(-(lo - mrf + p - k + 1), u);
+    hi = fdiv(hi + p, u);
+    scale /= u;
+    lvl_back_[i] = (int)-fdiv(lo, scale);
+    lvl_ahead_[i] = (int)fdiv(hi, scale);
+  }
+  back_ = (int)-lo;
+  ahead_ = (int)hi + 6;
 }
 
 size_t Vocoder::act_elems(int B, int T) const {
@@ -1647,6 +1671,108 @@ void Vocoder::forward_from_norm_ragged(const float* mel_norm, const float* mean,
   ragged_run(mel_norm, mean, std_, lengths, B, N, mel_db, mel_log, wav, ws, s);
 }
 
+// Streaming: the stateless chunk call (vocoder_chunk.hip, DESIGN.md "Streaming vocoder").
+Vocoder::ChunkPlan Vocoder::chunk_plan(const int* lengths, const int* context, const int* hold, int B,
+                                       long rows) const {
+  ChunkPlan p;
+  p.d = ragged_dims(lengths, B, rows);
+  M2S_CHECK(context && hold, "chunk: context and hold must not be null");
+  const int nl = h_.n_up, T = p.d.Tmax;
+  // A cropped block's edge is a fake clip end: what it contaminates must lie in rows no emitted sample depends on.
+  // That holds on the left when every clip brings the full history, on the right when every clip holds the full
+  // look-ahead back; otherwise that side keeps its rows, and its ends are clip ends (tail masks as in ragged calls)
+  bool left = chunk_cone_, right = chunk_cone_;
+  int cmin = T;
+  for (int b = 0; b < B; ++b) {
+    const std::string c = "chunk: clip " + std::to_string(b);
+    M2S_CHECK(context[b] >= 0 && hold[b] >= 0, c + ": context and hold must be >= 0");
+    M2S_CHECK((long)context[b] + hold[b] < lengths[b],
+              c + ": context " + std::to_string(context[b]) + " + hold " + std::to_string(hold[b]) +
+                  " leaves no row of its " + std::to_string(lengths[b]) + " to emit");
+    left = left && context[b] >= back_;
+    right = right && hold[b] >= ahead_;
+    cmin = std::min(cmin, context[b]);
+  }
+  p.mask = !right && p.d.Tmin < T;
+  p.tab.assign((size_t)(5 + nl) * B, 0);
+  int start = 0, rows_now = T;  // the block as it stands: rows start .. start + rows_now - 1 of every span
+  for (int l = 0; l < nl; ++l) {
+    int s0 = left ? cmin - lvl_back_[l] : 0, e0 = start + rows_now;
+    if (right) {
+      int need = 0;
+      for (int b = 0; b < B; ++b) need = std::max(need, lengths[b] - hold[b] + lvl_ahead_[l]);
+      e0 = std::min(e0, need);
+    }
+    s0 = std::max(s0, start);
+    p.drop[l] = s0 - start;
+    p.keep[l] = e0 - s0;
+    p.crop = p.crop || p.drop[l] != 0 || p.keep[l] != rows_now;
+    start = s0;
+    rows_now = e0 - s0;
+    for (int b = 0; b < B; ++b) p.tab[(size_t)(5 + l) * B + b] = lengths[b] - start;
+  }
+  p.t_final = rows_now;
+  int off = 0;
+  for (int b = 0; b < B; ++b) {
+    const int n = lengths[b] - context[b] - hold[b];
+    p.tab[b] = off;
+    p.tab[(size_t)B + b] = lengths[b];
+    p.tab[(size_t)2 * B + b] = context[b] - start;
+    p.tab[(size_t)3 * B + b] = (int)p.out_rows;
+    p.tab[(size_t)4 * B + b] = n;
+    off += lengths[b];
+    p.out_rows += n;
+  }
+  return p;
+}
+
+Vocoder::ChunkBufs Vocoder::chunk_bufs(Workspace& ws, int B, int Tmax) const {
+  ChunkBufs b{};
+  b.tab = ws.take<int>((size_t)(5 + h_.n_up) * B);
+  b.ln_buf = mel_in(ws, B, Tmax);
+  b.wav_pad = ws.take<float>((size_t)B * Tmax * hop_);
+  return b;
+}
+
+size_t Vocoder::chunk_workspace_bytes(const int* lengths, const int* context, const int* hold, int B) const {
+  long n = 0;
+  for (int b = 0; lengths && b < B; ++b) n += lengths[b];
+  const ChunkPlan p = chunk_plan(lengths, context, hold, B, n);
+  return Workspace::bytes([&](Workspace& ws) {
+    chunk_bufs(ws, B, p.d.Tmax);
+    gen_ws(ws, B, p.d.Tmax);
+  });
+}
+
+void Vocoder::forward_chunk(const float* mel, const int* lengths, const int* context, const int* hold, int B, long N,
+                            float* wav, Workspace& ws, hipStream_t s) {
+  const ChunkPlan p = chunk_plan(lengths, context, hold, B, N);
+  const int nm = h_.num_mels, cs = chan_stride(nm), T = p.d.Tmax;
+  const ChunkBufs cb = chunk_bufs(ws, B, T);
+  rtab_.upload_ints(p.tab.data(), p.tab.size(), cb.tab, s);
+  Cone cone{};
+  for (int l = 0; l < h_.n_up; ++l) {
+    cone.drop[l] = p.drop[l];
+    cone.keep[l] = p.keep[l];
+    // launch_ragged_tail_mask reads clip b's length at tab[B + b]: column 5 + l through a table that starts at 4 + l
+    cone.mask[l] = p.mask ? cb.tab + (size_t)(4 + l) * B : nullptr;
+  }
+  dispatch_act(dtype_, [&](auto t) {
+    using A = typename decltype(t)::type;
+    {
+      StageTag tag("glue");
+      ProfScope ps(tname<A>("ragged_glue_kernel"), 0.0, 4.0 * N * nm * 2, s);
+      launch_ragged_glue<A>(mel, cb.tab, B, T, nm, nullptr, nullptr, nullptr, nullptr, static_cast<A*>(cb.ln_buf), cs,
+                            s);
+    }
+    run_t<A>(cb.ln_buf, B, T, cb.wav_pad, ws, s, p.mask ? cb.tab : nullptr, p.crop ? &cone : nullptr);
+  });
+  StageTag tag("voc_post");
+  ProfScope ps("chunk_wav_pack_kernel", 0.0, 2.0 * 4.0 * p.out_rows * hop_, s);
+  const int* const emit = cb.tab + (size_t)2 * B;  // [src | dst | n]
+  launch_chunk_wav_pack(cb.wav_pad, emit, emit + B, emit + (size_t)2 * B, B, p.t_final, hop_, wav, s);
+}
+
 constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right pad of 6 (launch_conv_post)
 
 // Split-fp32 ResBlock1 stage with the resblocks batched (conv_gemm batch launches, grid.z = resblock):
@@ -1733,21 +1859,41 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
 }
 
 template <typename T>
-void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab) {
+void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab,
+                    const Cone* cone) {
   constexpr bool SPL = std::is_same<T, sp_t>::value;
+  int Tc = Tn;              // rows per clip of the block as it stands (a cone shortens it between stages)
+  const int* mtab = tab;    // ... and the clip table its tail masks read
   // ragged calls: zero the `halo` rows of S that the next consumer reads past the end of a short clip (they hold
   // biases and resblock outputs of the padding; lrelu(0) = 0, so masking before the activation is equivalent)
   auto mask_tail = [&](T* S, int L, int halo, int cs) {
-    if (!tab || halo <= 0) return;
+    if (!mtab || halo <= 0) return;
     const size_t row_bytes = sizeof(T) * Elem<T>::R * (size_t)cs;
     ProfScope ps("ragged_tail_mask_kernel", 0.0, (double)B * halo * row_bytes, s);
-    launch_ragged_tail_mask(S, tab, B, L, L / Tn, halo, row_bytes, s);
+    launch_ragged_tail_mask(S, mtab, B, L, L / Tc, halo, row_bytes, s);
   };
   const GenBufs<T> g = gen_bufs<T>(ws, B, Tn);
   T *const X = g.X, *const *const Hb = g.Hb, *const T1 = g.T1, *const S = g.S, *const E8 = g.E8;
   T* const(*Bt)[3] = g.Bt;
   int L = Tn;
   const int nk = h_.n_kernels;
+  // chunk calls: level l of the cone, on S as conv_pre (l = 0) or the MRF of stage l - 1 left it.  The kept rows go
+  // to Hb[0], which nothing holds between an MRF stage and the next upsampler
+  T* Sin = S;
+  auto crop = [&](int l) {
+    Sin = S;
+    if (!cone) return;
+    mtab = cone->mask[l];
+    if (cone->drop[l] == 0 && cone->keep[l] == Tc) return;
+    const long scale = L / Tc, keep = cone->keep[l] * scale;
+    const size_t row_bytes = sizeof(T) * Elem<T>::R * (size_t)ups_[l].cs_in;
+    StageTag tag("glue");
+    ProfScope ps("crop_rows_kernel", 0.0, 2.0 * B * keep * row_bytes, s);
+    launch_crop_rows(S, B, L, cone->drop[l] * scale, keep, row_bytes, Hb[0], s);
+    Sin = Hb[0];
+    Tc = cone->keep[l];
+    L = (int)keep;
+  };
   auto is_batched = [&](int i) {  // stage i's MRF runs as batched split launches (mrf_stage_batched)
     const PConv& up = ups_[i];
     const bool fused = (std::is_same<T, bf16_t>::value || SPL) && mrf_fused_ && !rbs_[i * nk].f1.empty();
@@ -1776,11 +1922,12 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
   for (int i = 0; i < h_.n_up; ++i) {
     const PConv& up = ups_[i];
     const bool batched = is_batched(i);
+    crop(i);
     StageTag tag("ups_c" + std::to_string(up.cout));
     // a transposed conv of rate u and padding p reads floor((u - 1 + p) / u) input rows ahead of its output
-    mask_tail(S, L, (up.ct_u - 1 + up.ct_pad) / up.ct_u, up.cs_in);
+    mask_tail(Sin, L, (up.ct_u - 1 + up.ct_pad) / up.ct_u, up.cs_in);
     ConvArgs a = conv_args(up);
-    a.x = S;
+    a.x = Sin;
     a.y = X;
     a.L_in = L;
     a.L_out = L * up.ct_u;

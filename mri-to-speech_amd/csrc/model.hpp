@@ -356,6 +356,19 @@ class Vocoder {
   // ... from packed mel_norm through the glue (packed mel_db / mel_log, may be null)
   void forward_from_norm_ragged(const float* mel_norm, const float* mean, const float* std_, const int* lengths, int B,
                                 long N, float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
+  // Streaming (vocoder_chunk.hip, DESIGN.md "Streaming vocoder"): the generator over packed spans of B clips, of
+  // which clip b's rows context[b] .. lengths[b] - hold[b] - 1 are emitted: packed wav (out_rows * hop).  Stateless;
+  // the rows equal the whole clip's where context >= back or the span starts the clip, and hold >= ahead or it ends it.
+  void reach(int* back, int* ahead) const {
+    *back = back_;
+    *ahead = ahead_;
+  }
+  size_t chunk_workspace_bytes(const int* lengths, const int* context, const int* hold, int B) const;
+  void forward_chunk(const float* mel, const int* lengths, const int* context, const int* hold, int B, long N,
+                     float* wav, Workspace& ws, hipStream_t s);
+  // the cone: between stages the chunk call drops the rows no emitted sample depends on
+  // (m2s_vocoder_set_chunk_cone, for tests and timing); off: every stage runs on the full spans.  Same contract
+  bool chunk_cone_ = true;
   size_t act_elems(int B, int T) const;
   bool mrf_fused_ = true;
   bool mrf_halo_ = true;   // split: C = 64 MRF convs with once-staged input rows (env M2S_MRF_HALO=0: conv_gemm)
@@ -369,8 +382,16 @@ class Vocoder {
  private:
   // tab (ragged calls, with a clip shorter than Tn): the device clip table; the input S of every upsampler and of
   // conv_post then gets the rows its consumer reads past a clip's end zeroed (launch_ragged_tail_mask)
+  // cone (chunk calls): after conv_pre (level 0) and after the MRF of stage l - 1 (level l < n_up) the block keeps
+  // rows drop[l] .. drop[l] + keep[l] - 1 of every clip (crop_rows_kernel), and the tail masks of that block read
+  // the clip lengths at mask[l] + B (null: no clip of the block ends early)
+  struct Cone {
+    int drop[8], keep[8];
+    const int* mask[8];
+  };
   template <typename T>
-  void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab = nullptr);
+  void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab = nullptr,
+             const Cone* cone = nullptr);
   template <typename T>
   struct GenBufs {  // the generator's activation buffers, act_elems(B, T) each
     T *X, *Hb[2], *T1, *S;
@@ -388,6 +409,24 @@ class Vocoder {
     float* wav_pad;
   };
   RaggedBufs ragged_bufs(Workspace& ws, int B, int Tmax) const;
+  // A chunk call, validated (M2S_E_ARG before any launch): the padded block, the rows each level keeps, and the
+  // device table [off | len | src | dst | n | len at level 0 | ... | len at level n_up - 1], B ints a column:
+  // clip b's emitted rows are rows src[b] .. src[b] + n[b] - 1 of the final block and packed rows dst[b] ...
+  struct ChunkPlan {
+    RaggedDims d;
+    long out_rows = 0;
+    bool crop = false, mask = false;  // any level drops rows; a clip ends before its block does
+    int drop[8] = {}, keep[8] = {};
+    int t_final = 0;  // rows per clip of the block conv_post runs on
+    std::vector<int> tab;
+  };
+  ChunkPlan chunk_plan(const int* lengths, const int* context, const int* hold, int B, long rows) const;
+  struct ChunkBufs {  // clip table, padded ln-mel, padded wav; then gen_bufs at (B, Tmax)
+    int* tab;
+    void* ln_buf;
+    float* wav_pad;
+  };
+  ChunkBufs chunk_bufs(Workspace& ws, int B, int Tmax) const;
   void ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
                   float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
   template <typename T>
@@ -413,6 +452,8 @@ class Vocoder {
   };
   m2s_hifigan_h h_;
   int dtype_, device_, hop_ = 1;
+  // reach in mel rows (interval propagation over h_): of the whole generator, and of what follows level l
+  int back_ = 0, ahead_ = 0, lvl_back_[8] = {}, lvl_ahead_[8] = {};
   Arena arena_;
   PConv pre_;
   std::vector<PConv> ups_;

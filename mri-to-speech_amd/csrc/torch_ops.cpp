@@ -16,6 +16,7 @@
 //   pipeline_forward   the no_grad section of main()                   run_mri_video_inference.py:222-242
 //   preprocess_frames  _preprocess_frame after the host decode         run_mri_video_inference.py:34-54
 //   *_ragged           the same forward passes over clips of different lengths, packed (include/m2s.h)
+//   hifigan_forward_chunk  Generator.forward on spans of a stream, emitting the rows that are final (include/m2s.h)
 //   cam_backbone       backbone(x) in train() (batch-statistics BN)    mri_gradcam_formant.py:153-160,221-225
 //   bilstm_train_*     model.rnn(seq) forward / autograd backward      mri_gradcam_formant.py:162-164,247-248
 //   linear_*           model.head(...) forward / autograd backward     mri_gradcam_formant.py:165
@@ -275,6 +276,27 @@ at::Tensor hifigan_forward_ragged(int64_t v, const at::Tensor& mel, at::IntArray
   return wav;
 }
 
+// Streaming vocoder (include/m2s.h): mel (N,num_mels) packed spans -> wav (R*hop), R = N - sum(context) - sum(hold):
+// of clip b, the rows context[b] .. lengths[b] - hold[b] - 1
+at::Tensor hifigan_forward_chunk(int64_t v, const at::Tensor& mel, at::IntArrayRef lengths, at::IntArrayRef context,
+                                 at::IntArrayRef hold, int64_t hop) {
+  TORCH_CHECK(mel.dim() == 2, "hifigan_forward_chunk: mel must be packed (N,num_mels)");
+  TORCH_CHECK(context.size() == lengths.size() && hold.size() == lengths.size(),
+              "hifigan_forward_chunk: one context and one hold entry per clip");
+  const Guard g(mel.device());
+  const at::Tensor x = f32_on_device(mel, "mel");
+  const std::vector<int> l = host_lengths(lengths, "hifigan_forward_chunk"),
+                         c = host_lengths(context, "hifigan_forward_chunk"),
+                         hd = host_lengths(hold, "hifigan_forward_chunk");
+  const int N = x.size(0), B = (int)l.size();
+  at::Tensor wav = at::empty({windowed_out_rows(windowed_out_rows(N, c), hd) * hop}, x.options());
+  at::Tensor ws = workspace(m2s_vocoder_chunk_workspace_bytes(V(v), l.data(), c.data(), hd.data(), B), x);
+  ok(m2s_vocoder_forward_chunk(V(v), x.data_ptr<float>(), l.data(), c.data(), hd.data(), B, N, wav.data_ptr<float>(),
+                               ws.data_ptr(), ws.numel(), S()),
+     "hifigan_forward_chunk");
+  return wav;
+}
+
 // frames (N,H,W) -> (mel_norm, mel_db, mel_log (N,n_mels), wav (N*hop))
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pipeline_forward_ragged(
     int64_t h, int64_t v, const at::Tensor& frames, at::IntArrayRef lengths, const at::Tensor& mean,
@@ -495,6 +517,7 @@ TORCH_LIBRARY(m2s, m) {
         " int n_mels) -> (Tensor, Tensor)");
   m.def("acoustic_forward_windowed(int handle, Tensor frames, int[] lengths, int[] context, int window, int merge,"
         " int n_mels) -> Tensor");
+  m.def("hifigan_forward_chunk(int handle, Tensor mel, int[] lengths, int[] context, int[] hold, int hop) -> Tensor");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
   m.def("cam_backbone(int handle, Tensor frames) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
@@ -520,6 +543,7 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("pipeline_forward_ragged", &pipeline_forward_ragged);
   m.impl("bilstm_windowed", &bilstm_windowed);
   m.impl("acoustic_forward_windowed", &acoustic_forward_windowed);
+  m.impl("hifigan_forward_chunk", &hifigan_forward_chunk);
   m.impl("preprocess_frames", &preprocess_frames);
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);

@@ -96,6 +96,11 @@ def lib():
         "m2s_acoustic_forward_ragged": (i, [vp, fp, C.POINTER(i), i, i, i, i, fp, vp, sz, vp]),
         "m2s_vocoder_ragged_workspace_bytes": (sz, [vp, C.POINTER(i), i]),
         "m2s_vocoder_forward_ragged": (i, [vp, fp, C.POINTER(i), i, i, fp, vp, sz, vp]),
+        # streaming vocoder: `context` / `hold` are host int arrays like `lengths`
+        "m2s_vocoder_reach": (i, [vp, C.POINTER(i), C.POINTER(i)]),
+        "m2s_vocoder_set_chunk_cone": (i, [vp, i]),
+        "m2s_vocoder_chunk_workspace_bytes": (sz, [vp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i]),
+        "m2s_vocoder_forward_chunk": (i, [vp, fp, C.POINTER(i), C.POINTER(i), C.POINTER(i), i, i, fp, vp, sz, vp]),
         "m2s_pipeline_ragged_workspace_bytes": (sz, [vp, vp, C.POINTER(i), i, i, i]),
         "m2s_pipeline_forward_ragged": (i, [vp, vp, fp, C.POINTER(i), i, i, i, i, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
         # windowed inference: `context` is a host int array like `lengths`, or NULL
@@ -152,7 +157,9 @@ def exported_symbols() -> List[str]:
                         "m2s_acoustic_forward_ragged", "m2s_vocoder_ragged_workspace_bytes",
                         "m2s_vocoder_forward_ragged", "m2s_pipeline_ragged_workspace_bytes",
                         "m2s_pipeline_forward_ragged", "m2s_acoustic_windowed_workspace_bytes", "m2s_bilstm_windowed",
-                        "m2s_acoustic_forward_windowed", "m2s_cam_create", "m2s_cam_destroy", "m2s_cam_bn_layers",
+                        "m2s_acoustic_forward_windowed", "m2s_vocoder_reach", "m2s_vocoder_set_chunk_cone",
+                        "m2s_vocoder_chunk_workspace_bytes", "m2s_vocoder_forward_chunk", "m2s_cam_create",
+                        "m2s_cam_destroy", "m2s_cam_bn_layers",
                         "m2s_cam_bn_channels", "m2s_cam_workspace_bytes", "m2s_cam_backbone",
                         "m2s_bilstm_train_workspace_bytes", "m2s_bilstm_train_forward", "m2s_bilstm_train_backward",
                         "m2s_linear_forward", "m2s_linear_backward", "m2s_gap_forward", "m2s_gap_backward",

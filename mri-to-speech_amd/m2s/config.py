@@ -21,6 +21,36 @@ HIFIGAN_H = {
     "sampling_rate": 11413,
 }
 
+
+def generator_reach(h):
+    """(back, ahead): output frame o of the Generator (hop samples) depends on mel rows o - back .. o + ahead and on
+    no other.  Integer interval propagation from the config alone, from the waveform back to the mel:
+
+    * conv_post and conv_pre are Conv1d(k = 7) behind a right pad of 6: 6 positions ahead, none back;
+    * the resblocks are causal (get_padding = k d - d on both sides, then a truncation): an MRF stage reaches back
+      sum over its dilations of (k - 1) d, plus (k - 1) for the second conv of a ResBlock1 pair, the largest over
+      the kernel sizes; nothing ahead;
+    * ConvTranspose1d(k, u, padding p = (k - u) // 2): output n reads inputs ceil((n + p - k + 1) / u) ..
+      floor((n + p) / u).
+
+    ``HIFIGAN_H`` gives (16, 7); the engine computes the same (``m2s_vocoder_reach``).  ``ahead`` is the
+    algorithmic latency of streaming this generator: ``ahead * hop / sampling_rate`` seconds."""
+    rates, kernels = list(h["upsample_rates"]), list(h["upsample_kernel_sizes"])
+    per_pair = 1 if str(h["resblock"]) == "1" else 0
+    mrf = max(sum((int(k) - 1) * (int(d) + per_pair) for d in dil)
+              for k, dil in zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]))
+    hop = 1
+    for u in rates:
+        hop *= int(u)
+    lo, hi = 0, hop - 1 + 6  # frame 0 = samples 0 .. hop - 1, through conv_post
+    for u, k in zip(reversed(rates), reversed(kernels)):
+        u, k = int(u), int(k)
+        p = (k - u) // 2
+        lo = -((-(lo - mrf + p - k + 1)) // u)  # ceil
+        hi = (hi + p) // u
+    return -lo, hi + 6
+
+
 # The analysis half of the same config (config_custom.json:48-53): what meldataset.mel_spectrogram is called
 # with.  Kept apart from HIFIGAN_H, which holds only what the Generator reads.
 HIFIGAN_MEL = {"n_fft": 2048, "win_size": 2048, "fmin": 0, "fmax": 8000}

@@ -27,6 +27,9 @@ RAGGED_OPS = ("bilstm_summerge_ragged", "acoustic_forward_ragged", "hifigan_forw
 # 1 = mean; `context` = leading history rows per clip that get no output row, [] = none)
 WINDOWED_OPS = ("bilstm_windowed", "acoustic_forward_windowed")
 WINDOW_MERGES = {"latest": 0, "mean": 1}
+# streaming vocoder: the generator on spans of a stream, emitting only the rows that are final (packed like the ragged
+# ops; `context` / `hold` = leading / trailing rows per clip that are read but get no output)
+STREAM_OPS = ("hifigan_forward_chunk",)
 # analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
 ANALYSIS_OPS = ("mel_spectrogram",)
 
@@ -162,6 +165,10 @@ def _register_fakes():
     @f("m2s::acoustic_forward_windowed")
     def _acoustic_windowed(handle, frames, lengths, context, window, merge, n_mels):
         return frames.new_empty((frames.shape[0] - sum(context), n_mels), dtype=torch.float32)
+
+    @f("m2s::hifigan_forward_chunk")
+    def _hifigan_chunk(handle, mel, lengths, context, hold, hop):
+        return mel.new_empty(((mel.shape[0] - sum(context) - sum(hold)) * hop,), dtype=torch.float32)
 
     @f("m2s::mel_spectrogram")
     def _melspec(handle, wav, layout):

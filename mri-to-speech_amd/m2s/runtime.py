@@ -231,6 +231,36 @@ class VocoderEngine:
             raise N.M2SError(f"mel has {x.shape[1]} bins, generator expects {self.h['num_mels']}")
         return self.ops.hifigan_forward_ragged(self.handle, x, lengths, self.hop)
 
+    @property
+    def reach(self):
+        """(back, ahead): output frame o depends on mel rows o - back .. o + ahead (m2s_vocoder_reach; the same
+        numbers as ``config.generator_reach(h)``)."""
+        b, a = C.c_int(0), C.c_int(0)
+        N.check(N.lib().m2s_vocoder_reach(self._h, C.byref(b), C.byref(a)))
+        return int(b.value), int(a.value)
+
+    def set_chunk_cone(self, on: bool) -> None:
+        """Tests and timing: whether ``forward_chunk`` drops, between stages, the rows no emitted sample depends on.
+        The results are the same either way."""
+        N.check(N.lib().m2s_vocoder_set_chunk_cone(self._h, 1 if on else 0))
+
+    def forward_chunk(self, mel, lengths=None, context=None, hold=None) -> torch.Tensor:
+        """Spans of streams in one stateless call: packed (N,num_mels) ln-mel (one span if ``lengths`` is None) or a
+        list of per-span (T_b,num_mels) tensors -> packed waveform of the rows ``context[b] .. T_b - hold[b] - 1`` of
+        every span, ``(N - sum(context) - sum(hold)) * hop`` samples.  They are the whole clip's rows where the span
+        brings ``context >= reach[0]`` rows of history (or starts the clip) and ``hold >= reach[1]`` rows of
+        look-ahead (or ends it)."""
+        if lengths is None and not isinstance(mel, (list, tuple)):
+            lengths = [int(mel.shape[0])]
+        x, lengths = _packed(mel, lengths, self.device, 1)
+        if x.shape[1] != self.h["num_mels"]:
+            raise N.M2SError(f"mel has {x.shape[1]} bins, generator expects {self.h['num_mels']}")
+        context = [0] * len(lengths) if context is None else [int(c) for c in context]
+        hold = [0] * len(lengths) if hold is None else [int(c) for c in hold]
+        if len(context) != len(lengths) or len(hold) != len(lengths):
+            raise N.M2SError("one context and one hold entry per span")
+        return self.ops.hifigan_forward_chunk(self.handle, x, lengths, context, hold, self.hop)
+
 
 def mel_glue(mel_norm: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):
     """(rows..., n_mels) -> (mel_db, mel_log), same shape."""

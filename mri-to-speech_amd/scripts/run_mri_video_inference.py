@@ -178,10 +178,11 @@ def load_hifigan(config_path: Path, checkpoint_path: Path, device: torch.device,
 # ------------------------------------------------------------------------------------------------
 # run
 def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray, window: int = 0,
-        window_merge: str = "latest"):
+        window_merge: str = "latest", stream: int = 0):
     """(T,H,W) device frames -> dict mel_db (T,n_mels), mel_log (T,n_mels), audio (T*hop,) on the host.
     ``window`` > 0: the BiLSTM on sliding windows of that many frames (runtime.Pipeline.forward_windowed) instead of
-    the reference's whole-clip recurrence.
+    the reference's whole-clip recurrence.  ``stream`` > 0 (with a window, merge "latest"): the same clip pushed
+    through m2s.stream.SpeechStream that many frames at a time, mel rows and audio as they become final.
 
     On the m2s path the acoustic engine's asynchronous failure report (a BiLSTM barrier timeout
     poisons the outputs with NaN, include/m2s.h m2s_acoustic_status) is read after the results reach
@@ -190,7 +191,14 @@ def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray, win
     if hasattr(model, "_engine") and hasattr(gen, "_engine"):  # both are m2s plug-ins: one device call
         eng = model._engine(dev)
         pipe = runtime.Pipeline(eng, gen._engine(dev), mean, std)
-        if window:
+        if stream:
+            from m2s.stream import SpeechStream
+            st = SpeechStream(pipe, window)
+            parts = [st.push(frames[i:i + stream]) for i in range(0, frames.shape[0], stream)]
+            res = {"mel_db": torch.cat([p["mel_db"] for p in parts]),
+                   "mel_log": torch.cat([p["mel_log"] for p in parts]),
+                   "audio": torch.cat([p["wav"] for p in parts] + [st.flush()])}
+        elif window:
             out = pipe.forward_windowed(frames, None, window, window_merge)
             res = {"mel_db": out["mel_db"], "mel_log": out["mel_log"], "audio": out["wav"]}
         else:
@@ -199,8 +207,9 @@ def run(model, gen, frames: torch.Tensor, mean: np.ndarray, std: np.ndarray, win
         res = {k: v.float().cpu().numpy() for k, v in res.items()}
         eng.check()
         return res
-    if window:
-        raise RuntimeError("--window needs the m2s acoustic and vocoder plug-ins (a foreign plug-in has no windowed mode)")
+    if window or stream:
+        raise RuntimeError("--window / --stream need the m2s acoustic and vocoder plug-ins (a foreign plug-in has no "
+                           "windowed mode)")
     with torch.no_grad():  # a foreign plug-in: its forward, then the device glue and the generator
         mn = model(frames_to_tensor(frames))[0]
         db, ln = runtime.mel_glue(mn, torch.from_numpy(mean), torch.from_numpy(std))
@@ -259,7 +268,17 @@ def parse_args(argv=None):
     p.add_argument("--window-merge", choices=["latest", "mean"], default="latest",
                    help="--window: frame t from the window ending at t (latest) or averaged over the full windows "
                         "containing t (mean)")
+    p.add_argument("--stream", type=int, default=0, metavar="N",
+                   help="push the clip through the streaming path N frames at a time (m2s.stream.SpeechStream: mel "
+                        "rows per push, audio once a row's 7 successors exist); implies --window (default 4), since the "
+                        "whole-clip BiLSTM cannot stream; same output files; default 0: one call over the clip")
     args = p.parse_args(argv)
+    if args.stream < 0:
+        p.error("--stream must be >= 1 frames per push")
+    if args.stream and not args.window:
+        args.window = 4
+    if args.stream and args.window_merge != "latest":
+        p.error("--stream needs --window-merge latest (mean looks at later windows)")
     if args.window and not 1 <= args.window <= 16:
         p.error("--window must be 1..16")
     return args
@@ -280,7 +299,7 @@ def main(argv=None):
     model = build_mri_model(args, device)
     gen, h = load_hifigan(Path(args.hifigan_config), Path(args.hifigan_checkpoint), device, args.dtype)
     frames = FrameStream(video, device, args.max_frames, chunk=args.decode_chunk).read()
-    res = run(model, gen, frames, mean, std, args.window, args.window_merge)
+    res = run(model, gen, frames, mean, std, args.window, args.window_merge, args.stream)
     paths = write_outputs(res, Path(args.output_dir), video.stem, int(h.sampling_rate))
     print(f"[m2s] {frames.shape[0]} frames -> mel {res['mel_db'].shape} -> {res['audio'].shape[0]} samples "
           f"@ {int(h.sampling_rate)} Hz ({model.m2s_dtype if hasattr(model, 'm2s_dtype') else 'plug-in'})")
