@@ -28,6 +28,10 @@
  *                          scripts/mri_gradcam_formant.py:165
  *   m2s_gap_*              GlobalAvgPool / feats.mean((2,3)) forward + backward
  *                          mri_acoustic_model.py:15-18, scripts/mri_gradcam_formant.py:162
+ *   m2s_gradcam_*          compute_gradcam for all bands and target frames of a clip, heat maps included
+ *                          scripts/mri_gradcam_formant.py:128-279,407-426
+ *   m2s_bilstm_train_backward_multi   the LSTM part of the backward() calls, all targets at once   :247-248,262-266
+ *   m2s_cam_heatmap        _compute_cam_from_grads   scripts/mri_gradcam_formant.py:169-200
  *   m2s_melspec_*          mel_spectrogram (reflect pad, periodic-Hann STFT, magnitude, mel, ln)
  *                          meldataset.py:57-93, as inference.py:25-26 and train.py:228-252 call it; and
  *                          pre_emphasis + compute_mel_db up to the dB map (the caller supplies the mel basis)
@@ -119,7 +123,7 @@ int m2s_acoustic_set_ws_spin_limit(m2s_acoustic* m, unsigned polls);
  *     passed the call.  What an engine keeps across calls (the BiLSTM hand-off tags) it owns itself.
  *   - The size a query reports is sufficient, and it is exact to its 256-byte granule for the call the query is named
  *     after (m2s_acoustic_forward, m2s_vocoder_forward, m2s_pipeline_forward, their *_ragged forms,
- *     m2s_cam_backbone, m2s_bilstm_train_backward): 256 bytes less is refused with M2S_E_ARG, nothing outside the
+ *     m2s_cam_backbone, m2s_bilstm_train_backward, m2s_gradcam_forward, m2s_bilstm_train_backward_multi): 256 bytes less is refused with M2S_E_ARG, nothing outside the
  *     caller's buffers is written, and the engine stays usable.  The calls without a query of their own take the
  *     enclosing call's and use a part of it: m2s_effnet_forward / m2s_effnet_probe on N frames that of
  *     m2s_acoustic_workspace_bytes(m, N, 1, H, W); m2s_bilstm_summerge that of (m, B, T, H, W) for any valid frame
@@ -322,6 +326,62 @@ int m2s_linear_backward(const float* dy, const float* x, int rows, int in, int o
 /* mean over the last P elements of nc rows (NCHW maps: nc = N*C, P = H*W) and its backward. */
 int m2s_gap_forward(const float* x, int64_t nc, int p, float* y, void* stream);
 int m2s_gap_backward(const float* dy, int64_t nc, int p, float* dx, void* stream);
+
+/* ------------------------------------------------------------- Grad-CAM engine ---- */
+/* compute_gradcam for every formant band and every target frame of one clip in one call:
+ * what main() of scripts/mri_gradcam_formant.py does per band (:407-426), compute_gradcam (:203-279) with
+ * _forward_with_features (:128-166) and _compute_cam_from_grads (:169-200).  Exact fp32.  The K = n_bands *
+ * (1 + n_frames) targets share one train-mode forward; target k = band * (1 + n_frames) + j is the whole-clip
+ * band power for j = 0 and the band power of frame frame_idx[j - 1] for j >= 1.  Their cotangents go through
+ * the backward together, m2s_gradcam_chunk() at a time.  One clip per call, as the reference's helper. */
+typedef struct m2s_gradcam m2s_gradcam;
+/* Packs cnn.backbone.* like m2s_cam_create and keeps rnn.lstm.* and head.* as fp32.  Synchronous. */
+int m2s_gradcam_create(const m2s_tensor* sd, int n, int device, m2s_gradcam** out);
+void m2s_gradcam_destroy(m2s_gradcam* g);
+/* rows of head.weight */
+int m2s_gradcam_n_mels(const m2s_gradcam* g);
+/* floats of bn_stats: [mean C | biased var C] per BatchNorm layer, the layers of m2s_cam_bn_layers */
+int m2s_gradcam_bn_stats_floats(const m2s_gradcam* g);
+/* cotangents per backward pass (a compile-time constant): a call runs T * ceil(K / chunk) step launches */
+int m2s_gradcam_chunk(void);
+/* 0 for arguments the call would reject.  Proportional to min(K, chunk) * T: past K = chunk only the staged
+ * frame-index table (n_frames ints) grows. */
+size_t m2s_gradcam_workspace_bytes(const m2s_gradcam* g, int T, int H, int W, int n_bands, int n_frames);
+/* frames (T,H,W) fp32 in [0,1], mean / std (n_mels) the scaler, all device memory.  band_mask (n_bands,n_mels)
+ * of 0 / 1 and frame_idx (n_frames; may repeat, any order) are HOST arrays.  reduction 0 = mean, 1 = sum (:243-247).
+ * Outputs: heat_seq (n_bands,T,H,W): frame t under the whole-clip target; heat_frame (n_bands,n_frames,H,W):
+ * frame frame_idx[j] under its own target (NULL allowed when n_frames = 0); optional (NULL to skip) pred_norm
+ * (T,n_mels), dpooled (K,T,C = 208) = d target_k / d pooled features (feats.grad = dpooled / (h w), constant
+ * over a channel's positions), bn_stats as m2s_cam_backbone writes them.
+ * M2S_E_ARG, before any launch: T < 1, a frame smaller than 32 x 32, n_bands < 1, an index outside [0, T), a mask
+ * entry other than 0 / 1, a band with no bin set, an undersized workspace.  M2S_E_STATE on a capturing stream
+ * (the tables are staged per call). */
+int m2s_gradcam_forward(m2s_gradcam* g, const float* frames, int T, int H, int W, const float* mean, const float* std_,
+                        const float* band_mask, int n_bands, const int* frame_idx, int n_frames, int reduction,
+                        float* heat_seq, float* heat_frame, float* pred_norm, float* dpooled, float* bn_stats,
+                        void* ws, size_t ws_bytes, void* stream);
+/* Stage: the targets' gradients with respect to pred_norm (:230-247, :254-266 differentiated), every pointer
+ * device memory (band_mask, frame_idx too): dpred (K,T,n_mels),
+ *   dpred[k,t,m] = s_k(t) ln10/10 std[m] 10^((pred std + mean)[t,m] / 10) mask[band,m],
+ * s_k(t) = 1/T (mean) or 1 (sum) for j = 0, [t == frame_idx[j-1]] for j >= 1. */
+int m2s_gradcam_cotangents(const float* pred_norm, int T, int n_mels, const float* mean, const float* std_,
+                           const float* band_mask, int n_bands, const int* frame_idx, int n_frames, int reduction,
+                           float* dpred, void* stream);
+/* Stage: K cotangents dy (K,T,H) through the backward of one saved sequence (gates (2,1,T,4H), cells (2,1,T,H)
+ * from m2s_bilstm_train_forward with B = 1; w[8] as there) -> dx (K,T,C); what K loss.backward() calls leave
+ * in the LSTM input's .grad (:247-248, :262-266), without the weight gradients.  H % 16 == 0.  dx[k] is
+ * bit-identical whatever K and k's position; an all-zero cotangent gives exactly zero.  The query returns 0 for
+ * arguments the call would reject and stops growing at K = m2s_gradcam_chunk(). */
+size_t m2s_bilstm_train_backward_multi_workspace_bytes(int K, int T, int C, int H);
+int m2s_bilstm_train_backward_multi(const float* dy, int K, int T, int C, int H, const float* const* w,
+                                    const float* gates, const float* cells, float* dx, void* ws, size_t ws_bytes,
+                                    void* stream);
+/* Stage: _compute_cam_from_grads (:169-200) for M maps.  feats (N,C,h,w), weights (M,C) (the spatial mean of the
+ * gradient), frame (M) device ints into N -> out (M,H,W): relu(sum_c weights[m,c] feats[frame[m],c]), bilinear
+ * resize (align_corners=False), (v - min) / ((max - min) + 1e-6) over the resized map.  Any h, w, H, W whose
+ * source map, weights and sample tables fit 64 KB of LDS; a frame outside [0, N) gives an all-zero map. */
+int m2s_cam_heatmap(const float* feats, int N, int C, int h, int w, const float* weights, const int* frame, int M,
+                    int H, int W, float* out, void* stream);
 
 /* ------------------------------------------------ analysis: waveform -> mel ---- */
 /* The opposite direction of the vocoder: wav (B,L) -> mel, exact fp32 (an f32-MFMA DFT with float64-built

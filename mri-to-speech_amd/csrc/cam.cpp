@@ -14,6 +14,7 @@
 #include <cstring>
 
 #include "pack.hpp"
+#include "prof.hpp"
 
 namespace m2s {
 
@@ -343,6 +344,216 @@ void bilstm_train_backward(const float* x, const float* dy, int B, int T, int C,
     if (dw_hh && dw_hh[d])  // dW_hh[n][k] = sum_bt dG[bt][n] h_prev[bt][k]
       launch_gemm_f32(G, H, (int)BT, g, 1, G, hp + (size_t)d * BT * H, H, 1, dw_hh[d], H, nullptr, nullptr, false, s);
     if (db && db[d]) launch_colsum(g, (int)BT, G, G, db[d], false, s);
+  }
+}
+
+// ---- many cotangents through one saved sequence ----------------------------------------------------
+namespace {
+struct BpttMultiBufs {
+  float* dg;  // (2, kc, T, 4H) gate gradients of one chunk
+  float* wt;  // W_hh^T of both directions (2, H, 4H)
+  float* dc;  // (2, kc, H) carried cell gradient
+};
+}  // namespace
+
+static void bptt_multi_check(int K, int T, int C, int H) {
+  M2S_CHECK(K > 0 && T > 0 && C > 0 && H > 0 && H % 16 == 0, "bilstm_train_backward_multi: shape (H % 16 == 0)");
+  M2S_CHECK((long)std::min(K, kGradcamKC) * T <= 4000000L, "bilstm_train_backward_multi: sequence too long");
+}
+
+static BpttMultiBufs bptt_multi_bufs(Workspace& w, int K, int T, int H) {
+  const size_t kc = (size_t)std::min(K, kGradcamKC);
+  BpttMultiBufs b;
+  b.dg = w.take<float>(2 * kc * T * 4 * H);
+  b.wt = w.take<float>((size_t)2 * 4 * H * H);
+  b.dc = w.take<float>(2 * kc * H);
+  return b;
+}
+
+// one chunk: dy (kc,T,H) -> dx (kc,T,C); b.wt already holds W_hh^T
+static void bptt_multi_chunk(const BpttMultiBufs& b, const float* dy, int kc, int T, int C, int H,
+                             const float* const w_ih[2], const float* gates, const float* cells, float* dx,
+                             hipStream_t s) {
+  const int G = 4 * H;
+  for (int st = 0; st < T; ++st) launch_lstm_bptt_multi_step(b.wt, dy, gates, cells, b.dc, b.dg, kc, T, H, st, s);
+  for (int d = 0; d < 2; ++d)  // dx[kt][c] (+)= sum_n dG[d][kt][n] W_ih[d][n][c]
+    launch_gemm_f32(kc * T, C, G, b.dg + (size_t)d * kc * T * G, G, 1, w_ih[d], C, 1, dx, C, nullptr, nullptr, d == 1, s);
+}
+
+size_t bilstm_train_backward_multi_workspace_bytes(int K, int T, int C, int H) {
+  bptt_multi_check(K, T, C, H);
+  return Workspace::bytes([&](Workspace& w) { bptt_multi_bufs(w, K, T, H); });
+}
+
+void bilstm_train_backward_multi(const float* dy, int K, int T, int C, int H, const float* const w_ih[2],
+                                 const float* const w_hh[2], const float* gates, const float* cells, float* dx,
+                                 void* ws, size_t wsb, hipStream_t s) {
+  bptt_multi_check(K, T, C, H);
+  Workspace w(ws, wsb);
+  const BpttMultiBufs b = bptt_multi_bufs(w, K, T, H);
+  for (int d = 0; d < 2; ++d) launch_transpose(w_hh[d], 1, 4 * H, H, b.wt + (size_t)d * 4 * H * H, s);
+  for (int k0 = 0; k0 < K; k0 += kGradcamKC) {
+    const int kc = std::min(kGradcamKC, K - k0);
+    bptt_multi_chunk(b, dy + (size_t)k0 * T * H, kc, T, C, H, w_ih, gates, cells, dx + (size_t)k0 * T * C, s);
+  }
+}
+
+// ---- the Grad-CAM engine ---------------------------------------------------------------------------
+GradCam::GradCam(const StateDict& sd, int device) : bb_(sd, device) {
+  auto hw = sd.find("head.weight");
+  M2S_CHECK(hw != sd.end() && hw->second.shape.size() == 2, "missing state-dict key: head.weight (n_mels, hidden)");
+  nm_ = (int)hw->second.shape[0];
+  hid_ = (int)hw->second.shape[1];
+  M2S_CHECK(nm_ >= 1 && hid_ >= 16 && hid_ % 16 == 0, "gradcam: head.weight shape");
+  const int C = kStages[5].cout;
+  for (int d = 0; d < 2; ++d) {
+    const std::string sfx = d ? "_l0_reverse" : "_l0";
+    w_ih_[d] = arena_.add(need(sd, "rnn.lstm.weight_ih" + sfx, {4 * hid_, C}).data, sizeof(float) * 4 * hid_ * C);
+    w_hh_[d] = arena_.add(need(sd, "rnn.lstm.weight_hh" + sfx, {4 * hid_, hid_}).data, sizeof(float) * 4 * hid_ * hid_);
+    b_ih_[d] = arena_.add(need(sd, "rnn.lstm.bias_ih" + sfx, {4 * hid_}).data, sizeof(float) * 4 * hid_);
+    b_hh_[d] = arena_.add(need(sd, "rnn.lstm.bias_hh" + sfx, {4 * hid_}).data, sizeof(float) * 4 * hid_);
+  }
+  head_w_ = arena_.add(hw->second.data, sizeof(float) * nm_ * hid_);
+  head_b_ = arena_.add(need(sd, "head.bias", {nm_}).data, sizeof(float) * nm_);
+  arena_.upload(device);
+}
+
+namespace {
+struct GradCamDims {
+  int T, C, h, w, P, K, kc, nm, hid;
+  size_t bb_bytes, lstm_bytes;
+};
+struct GradCamBufs {
+  float *feats, *bn, *pooled, *y, *gates, *cells, *hid, *pred, *dpred, *dy, *dx, *mask;
+  int* fidx;
+  void *bbws, *lstmws;
+  BpttMultiBufs bp;
+};
+}  // namespace
+
+static size_t gradcam_fpad(int n_frames) { return ((size_t)std::max(n_frames, 1) + 3) & ~size_t(3); }
+
+// the engine's scratch: the size query and the call both run this.  The optional outputs (pred_norm, dpooled,
+// bn_stats) always have their stand-ins here, so the size does not depend on which of them the caller wants.  Only the frame-index table (n_frames ints)
+// grows with the number of targets past kGradcamKC.
+static GradCamBufs gradcam_bufs(Workspace& w, const GradCamDims& d, int n_bands, int n_frames, size_t bn_floats) {
+  GradCamBufs b;
+  const size_t T = (size_t)d.T, fpad = gradcam_fpad(n_frames);
+  b.fidx = w.take<int>(fpad + (size_t)n_bands * d.nm);  // [frame_idx, padded | band_mask]: one staged copy
+  b.mask = b.fidx ? reinterpret_cast<float*>(b.fidx + fpad) : nullptr;
+  b.feats = w.take<float>(T * d.C * d.P);
+  b.bn = w.take<float>(bn_floats);
+  b.bbws = w.take<char>(d.bb_bytes);
+  b.pooled = w.take<float>(T * d.C);
+  b.y = w.take<float>(T * d.hid);
+  b.gates = w.take<float>(2 * T * 4 * d.hid);
+  b.cells = w.take<float>(2 * T * d.hid);
+  b.hid = w.take<float>(2 * T * d.hid);
+  b.lstmws = w.take<char>(d.lstm_bytes);
+  b.pred = w.take<float>(T * d.nm);
+  b.dpred = w.take<float>((size_t)d.kc * T * d.nm);
+  b.dy = w.take<float>((size_t)d.kc * T * d.hid);
+  b.dx = w.take<float>((size_t)d.kc * T * d.C);
+  b.bp = bptt_multi_bufs(w, d.K, d.T, d.hid);
+  return b;
+}
+
+static GradCamDims gradcam_dims(const CamBackbone& bb, int nm, int hid, int T, int H, int W, int n_bands, int n_frames) {
+  M2S_CHECK(T >= 1 && H >= 32 && W >= 32, "gradcam: bad clip size");
+  M2S_CHECK(n_bands >= 1 && n_bands <= 4096, "gradcam: n_bands must be at least 1");
+  M2S_CHECK(n_frames >= 0, "gradcam: negative n_frames");
+  const long K = (long)n_bands * (1 + (long)n_frames);
+  M2S_CHECK(K <= 2147483647L / 4, "gradcam: too many targets");
+  GradCamDims d;
+  d.T = T;
+  d.C = kStages[5].cout;
+  d.h = H;
+  d.w = W;
+  for (int i = 0; i < 5; ++i) d.h = (d.h + 1) / 2, d.w = (d.w + 1) / 2;
+  d.P = d.h * d.w;
+  M2S_CHECK(cam_heatmap_shape_ok(d.C, d.h, d.w, H, W), "gradcam: frame size too large for the heat-map kernel");
+  d.K = (int)K;
+  d.kc = (int)std::min<long>(K, kGradcamKC);
+  d.nm = nm;
+  d.hid = hid;
+  bptt_multi_check(d.K, T, d.C, hid);
+  d.bb_bytes = bb.workspace_bytes(T, H, W);
+  d.lstm_bytes = bilstm_train_workspace_bytes(1, T, d.C, hid);
+  return d;
+}
+
+size_t GradCam::workspace_bytes(int T, int H, int W, int n_bands, int n_frames) const {
+  const GradCamDims d = gradcam_dims(bb_, nm_, hid_, T, H, W, n_bands, n_frames);
+  return Workspace::bytes([&](Workspace& w) { gradcam_bufs(w, d, n_bands, n_frames, (size_t)bb_.bn_stats_floats()); });
+}
+
+void GradCam::forward(const float* frames, int T, int H, int W, const float* mean, const float* sd,
+                      const float* band_mask, int n_bands, const int* frame_idx, int n_frames, int reduction,
+                      float* heat_seq, float* heat_frame, float* pred_norm, float* dpooled, float* bn_stats, void* ws,
+                      size_t wsb, hipStream_t s) {
+  const GradCamDims d = gradcam_dims(bb_, nm_, hid_, T, H, W, n_bands, n_frames);
+  M2S_CHECK(reduction == 0 || reduction == 1, "gradcam: reduction must be 0 (mean) or 1 (sum)");
+  M2S_CHECK(n_frames == 0 || (frame_idx && heat_frame), "gradcam: null frame_idx / heat_frame");
+  for (int j = 0; j < n_frames; ++j)
+    M2S_CHECK(frame_idx[j] >= 0 && frame_idx[j] < T, "gradcam: target frame index outside [0, T)");
+  for (int b = 0; b < n_bands; ++b) {
+    bool any = false;
+    for (int m = 0; m < nm_; ++m) {
+      const float v = band_mask[(size_t)b * nm_ + m];
+      M2S_CHECK(v == 0.f || v == 1.f, "gradcam: band_mask entries must be 0 or 1");
+      any = any || v != 0.f;
+    }
+    M2S_CHECK(any, "gradcam: a band selects no mel bin");
+  }
+  Workspace w(ws, wsb);
+  const GradCamBufs b = gradcam_bufs(w, d, n_bands, n_frames, (size_t)bb_.bn_stats_floats());
+  const int F = n_frames, C = d.C, Hd = hid_;
+  {
+    const size_t fpad = gradcam_fpad(F);
+    std::vector<int> tab(fpad + (size_t)n_bands * nm_, 0);
+    for (int j = 0; j < F; ++j) tab[j] = frame_idx[j];
+    std::memcpy(tab.data() + fpad, band_mask, sizeof(float) * (size_t)n_bands * nm_);
+    tab_.upload_ints(tab.data(), tab.size(), b.fidx, s);  // M2S_E_STATE on a capturing stream
+  }
+  auto A = [&](size_t off) { return static_cast<const float*>(arena_.ptr(off)); };
+  const float* wih[2] = {A(w_ih_[0]), A(w_ih_[1])};
+  const float* whh[2] = {A(w_hh_[0]), A(w_hh_[1])};
+  const float* bih[2] = {A(b_ih_[0]), A(b_ih_[1])};
+  const float* bhh[2] = {A(b_hh_[0]), A(b_hh_[1])};
+  float* pred = pred_norm ? pred_norm : b.pred;
+  {
+    StageTag tag("gradcam_fwd");
+    float* taps[5] = {nullptr, nullptr, nullptr, nullptr, b.feats};
+    bb_.forward(frames, T, H, W, taps, bn_stats ? bn_stats : b.bn, b.bbws, d.bb_bytes, s);
+    launch_gap_nchw(b.feats, (long)T * C, d.P, b.pooled, s);
+    bilstm_train_forward(b.pooled, 1, T, C, Hd, wih, whh, bih, bhh, b.y, b.gates, b.cells, b.hid, b.lstmws,
+                         d.lstm_bytes, s);
+    linear_forward(b.y, T, Hd, nm_, A(head_w_), A(head_b_), pred, s);
+  }
+  StageTag tag("gradcam_bwd");
+  for (int dd = 0; dd < 2; ++dd) launch_transpose(whh[dd], 1, 4 * Hd, Hd, b.bp.wt + (size_t)dd * 4 * Hd * Hd, s);
+  const float inv_p = 1.f / (float)d.P;
+  const size_t map = (size_t)H * W;
+  for (int k0 = 0; k0 < d.K; k0 += kGradcamKC) {
+    const int kc = std::min(kGradcamKC, d.K - k0);
+    launch_gradcam_cotangents(pred, mean, sd, b.mask, b.fidx, F, T, nm_, k0, kc, reduction == 1, b.dpred, s);
+    // the head's backward: dy (kc T, hidden) = dpred (kc T, n_mels) W_head
+    launch_gemm_f32(kc * T, Hd, nm_, b.dpred, nm_, 1, A(head_w_), Hd, 1, b.dy, Hd, nullptr, nullptr, false, s);
+    float* dx = dpooled ? dpooled + (size_t)k0 * T * C : b.dx;
+    bptt_multi_chunk(b.bp, b.dy, kc, T, C, Hd, wih, b.gates, b.cells, dx, s);
+    // the map of target k at its own frame(s), under its own cotangent; grads.mean((2,3)) = dpooled / P
+    bool frame_targets = false;
+    for (int kl = 0; kl < kc; ++kl) {
+      const int k = k0 + kl, band = k / (1 + F), j = k % (1 + F);
+      if (j != 0) {
+        frame_targets = true;
+        continue;
+      }
+      launch_cam_heatmap(b.feats, T, C, d.h, d.w, dx + (size_t)kl * T * C, inv_p, nullptr, 0, 0, 0, T, T, H, W,
+                         heat_seq + (size_t)band * T * map, s);
+    }
+    if (frame_targets)
+      launch_cam_heatmap(b.feats, T, C, d.h, d.w, dx, inv_p, b.fidx, 1, k0, F, T, kc, H, W, heat_frame, s);
   }
 }
 

@@ -49,6 +49,28 @@ void launch_lstm_hprev(const float* hid, float* hp, int B, int T, int H, hipStre
 // (rows, cols) -> (cols, rows), for `planes` consecutive matrices
 void launch_transpose(const float* x, int planes, int rows, int cols, float* y, hipStream_t s);
 
+// ---- kernels of the Grad-CAM engine (gradcam.hip) ----------------------------------------------------
+// cotangents per backward-through-time pass: the N tile of v_mfma_f32_16x16x4_f32
+constexpr int kGradcamKC = 16;
+// dpred (kc,T,nm) = d target_k / d pred_norm for cotangents k0 .. k0 + kc - 1, k = band * (1 + F) + j: j = 0 the
+// whole-clip target (mean: 1/T per frame, sum: 1), j >= 1 the band power of frame fidx[j-1].
+// dpred[k,t,m] = s_k(t) * ln10/10 * std[m] * 10^((pred std + mean)[t,m] / 10) * mask[band,m]
+void launch_gradcam_cotangents(const float* pred, const float* mean, const float* sd, const float* mask,
+                               const int* fidx, int F, int T, int nm, int k0, int kc, bool sum, float* dpred,
+                               hipStream_t s);
+// one step of the backward through time for kc <= kGradcamKC cotangents over one saved sequence, both
+// directions (grid: H/16 unit groups x 2): whh_t (2,H,4H), dy (kc,T,H), gates (2,1,T,4H), cells (2,1,T,H),
+// dc (2,kc,H) carried cell gradient, dg (2,kc,T,4H) out.  H % 16 == 0.
+void launch_lstm_bptt_multi_step(const float* whh_t, const float* dy, const float* gates, const float* cells, float* dc,
+                                 float* dg, int kc, int T, int H, int step, hipStream_t s);
+// heat maps out (.,H,W) from feats (N,C,h,w) NCHW and channel weights (scaled by wscale); see gradcam.hip for
+// the two addressing modes (0: M plain maps with frame table `tab` or frame = map index; 1: the frame
+// cotangents of a (kc,T,C) chunk starting at cotangent k0, M = kc)
+bool cam_heatmap_shape_ok(int C, int h, int w, int H, int W);
+void launch_cam_heatmap(const float* feats, int N, int C, int h, int w, const float* weights, float wscale,
+                        const int* tab, int mode, int k0, int F, int T, int M, int H, int W, float* out,
+                        hipStream_t s);
+
 // ---- BiLSTM (nn.LSTM 1 layer, bidirectional, batch_first, sum merge) and Linear with autograd ------
 // x (B,T,C); weights in nn.LSTM layout per direction d (0 fwd, 1 reverse): w_ih (4H,C), w_hh (4H,H),
 // b_ih / b_hh (4H).  forward: y (B,T,H) = h_fwd + h_bwd, saved gates (2,B,T,4H), cells / hid (2,B,T,H).
@@ -62,6 +84,14 @@ void bilstm_train_backward(const float* x, const float* dy, int B, int T, int C,
                            const float* const w_hh[2], const float* gates, const float* cells, const float* hid,
                            float* dx, float* const dw_ih[2], float* const dw_hh[2], float* const db[2], void* ws,
                            size_t wsb, hipStream_t s);
+// K cotangents dy (K,T,H) through the backward of ONE saved sequence (gates (2,1,T,4H), cells (2,1,T,H) of
+// bilstm_train_forward with B = 1) -> dx (K,T,C); no weight gradient.  Chunks of kGradcamKC cotangents, T launches
+// per chunk; the workspace holds one chunk, so it stops growing at K = kGradcamKC.  A cotangent's dx is
+// bit-identical whatever K and its position.
+size_t bilstm_train_backward_multi_workspace_bytes(int K, int T, int C, int H);
+void bilstm_train_backward_multi(const float* dy, int K, int T, int C, int H, const float* const w_ih[2],
+                                 const float* const w_hh[2], const float* gates, const float* cells, float* dx,
+                                 void* ws, size_t wsb, hipStream_t s);
 // y (rows,out) = x (rows,in) W^T + b ; backward dx = dy W, dw = dy^T x, db = column sums of dy
 void linear_forward(const float* x, int rows, int in, int out, const float* w, const float* b, float* y, hipStream_t s);
 void linear_backward(const float* dy, const float* x, int rows, int in, int out, const float* w, float* dx, float* dw,
@@ -101,6 +131,34 @@ class CamBackbone {
   int stem_bn_ = 0;
   std::vector<BNp> bn_;
   std::vector<Blk> blocks_;
+};
+
+// ---- the Grad-CAM engine ------------------------------------------------------------
+// compute_gradcam for every band and target frame of one clip in one pass: one train-mode backbone forward,
+// GAP, BiLSTM with saved activations, head, then all K = n_bands * (1 + n_frames) cotangents through the
+// backward together and the heat maps on the device.
+class GradCam {
+ public:
+  GradCam(const StateDict& sd, int device);
+  int device() const { return bb_.device(); }
+  int n_mels() const { return nm_; }
+  int hidden() const { return hid_; }
+  int bn_stats_floats() const { return bb_.bn_stats_floats(); }
+  // throws M2S_E_ARG for a shape forward would refuse
+  size_t workspace_bytes(int T, int H, int W, int n_bands, int n_frames) const;
+  // frames (T,H,W), mean / std (n_mels) device; band_mask (n_bands,n_mels) 0/1 and frame_idx (n_frames) HOST.
+  // heat_seq (n_bands,T,H,W), heat_frame (n_bands,n_frames,H,W); optional pred_norm (T,n_mels), dpooled (K,T,C),
+  // bn_stats.  Arguments are checked before any launch.
+  void forward(const float* frames, int T, int H, int W, const float* mean, const float* sd, const float* band_mask,
+               int n_bands, const int* frame_idx, int n_frames, int reduction, float* heat_seq, float* heat_frame,
+               float* pred_norm, float* dpooled, float* bn_stats, void* ws, size_t wsb, hipStream_t s);
+
+ private:
+  CamBackbone bb_;
+  Arena arena_;
+  int nm_ = 0, hid_ = 0;
+  size_t w_ih_[2] = {0, 0}, w_hh_[2] = {0, 0}, b_ih_[2] = {0, 0}, b_hh_[2] = {0, 0}, head_w_ = 0, head_b_ = 0;
+  RaggedTable tab_;  // frame_idx and band_mask on their way to the device
 };
 
 }  // namespace m2s

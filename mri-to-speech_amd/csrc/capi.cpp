@@ -17,6 +17,10 @@ struct m2s_vocoder {
 struct m2s_cam {
   m2s::CamBackbone impl;
 };
+struct m2s_gradcam {
+  m2s::GradCam impl;
+  m2s_gradcam(const m2s::StateDict& sd, int device) : impl(sd, device) {}
+};
 struct m2s_melspec {
   m2s::MelSpec impl;
   m2s_melspec(const m2s_melspec_cfg& c, const float* basis, int device) : impl(c, basis, device) {}
@@ -450,6 +454,83 @@ int m2s_bilstm_train_backward(const float* x, const float* dy, int B, int T, int
     float* db[2] = {grads ? grads[2] : nullptr, grads ? grads[5] : nullptr};
     m2s::bilstm_train_backward(x, dy, B, T, C, H, wih, whh, gates, cells, hid, dx, dwih, dwhh, db, ws, ws_bytes,
                                S(stream));
+  });
+}
+
+int m2s_gradcam_create(const m2s_tensor* sd, int n, int device, m2s_gradcam** out) {
+  return guarded([&] {
+    M2S_CHECK(out && (sd || n == 0), "null argument");
+    check_device(device);
+    DeviceGuard g(device);
+    *out = new m2s_gradcam(m2s::make_state_dict(sd, n), device);
+  });
+}
+
+void m2s_gradcam_destroy(m2s_gradcam* g) {
+  if (!g) return;
+  guarded([&] {
+    DeviceGuard dg(g->impl.device());
+    delete g;
+  });
+}
+
+int m2s_gradcam_n_mels(const m2s_gradcam* g) { return g ? g->impl.n_mels() : 0; }
+
+int m2s_gradcam_bn_stats_floats(const m2s_gradcam* g) { return g ? g->impl.bn_stats_floats() : 0; }
+
+int m2s_gradcam_chunk(void) { return m2s::kGradcamKC; }
+
+size_t m2s_gradcam_workspace_bytes(const m2s_gradcam* g, int T, int H, int W, int n_bands, int n_frames) {
+  return size_query(g, [&] { return g->impl.workspace_bytes(T, H, W, n_bands, n_frames); });
+}
+
+int m2s_gradcam_forward(m2s_gradcam* g, const float* frames, int T, int H, int W, const float* mean, const float* std_,
+                        const float* band_mask, int n_bands, const int* frame_idx, int n_frames, int reduction,
+                        float* heat_seq, float* heat_frame, float* pred_norm, float* dpooled, float* bn_stats,
+                        void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(g && frames && mean && std_ && band_mask && heat_seq && ws, "null argument");
+    DeviceGuard dg(g->impl.device());
+    g->impl.forward(frames, T, H, W, mean, std_, band_mask, n_bands, frame_idx, n_frames, reduction, heat_seq,
+                    heat_frame, pred_norm, dpooled, bn_stats, ws, ws_bytes, S(stream));
+  });
+}
+
+int m2s_gradcam_cotangents(const float* pred_norm, int T, int n_mels, const float* mean, const float* std_,
+                           const float* band_mask, int n_bands, const int* frame_idx, int n_frames, int reduction,
+                           float* dpred, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(pred_norm && mean && std_ && band_mask && dpred && (frame_idx || n_frames == 0), "null argument");
+    M2S_CHECK(T >= 1 && n_mels >= 1 && n_bands >= 1 && n_frames >= 0 && (reduction == 0 || reduction == 1),
+              "gradcam_cotangents: bad argument");
+    const long K = (long)n_bands * (1 + (long)n_frames);
+    M2S_CHECK(K <= 2147483647L / 4, "gradcam_cotangents: too many targets");
+    m2s::launch_gradcam_cotangents(pred_norm, mean, std_, band_mask, frame_idx, n_frames, T, n_mels, 0, (int)K,
+                                   reduction == 1, dpred, S(stream));
+  });
+}
+
+size_t m2s_bilstm_train_backward_multi_workspace_bytes(int K, int T, int C, int H) {
+  return size_query(true, [&] { return m2s::bilstm_train_backward_multi_workspace_bytes(K, T, C, H); });
+}
+
+int m2s_bilstm_train_backward_multi(const float* dy, int K, int T, int C, int H, const float* const* w,
+                                    const float* gates, const float* cells, float* dx, void* ws, size_t ws_bytes,
+                                    void* stream) {
+  return guarded([&] {
+    M2S_CHECK(dy && w && gates && cells && dx && ws, "null argument");
+    const float* wih[2] = {w[0], w[4]};
+    const float* whh[2] = {w[1], w[5]};
+    M2S_CHECK(wih[0] && wih[1] && whh[0] && whh[1], "null LSTM weight");
+    m2s::bilstm_train_backward_multi(dy, K, T, C, H, wih, whh, gates, cells, dx, ws, ws_bytes, S(stream));
+  });
+}
+
+int m2s_cam_heatmap(const float* feats, int N, int C, int h, int w, const float* weights, const int* frame, int M,
+                    int H, int W, float* out, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(feats && weights && frame && out && N >= 1 && M >= 0, "bad argument");
+    m2s::launch_cam_heatmap(feats, N, C, h, w, weights, 1.f, frame, 0, 0, 0, 0, M, H, W, out, S(stream));
   });
 }
 

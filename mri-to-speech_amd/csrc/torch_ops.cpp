@@ -20,6 +20,10 @@
 //   cam_backbone       backbone(x) in train() (batch-statistics BN)    mri_gradcam_formant.py:153-160,221-225
 //   bilstm_train_*     model.rnn(seq) forward / autograd backward      mri_gradcam_formant.py:162-164,247-248
 //   linear_*           model.head(...) forward / autograd backward     mri_gradcam_formant.py:165
+//   gradcam            compute_gradcam, all bands and target frames    mri_gradcam_formant.py:128-279,407-426
+//   gradcam_cotangents the targets' gradients w.r.t. pred_norm         mri_gradcam_formant.py:230-247,254-266
+//   bilstm_train_backward_multi  the LSTM backward of all targets      mri_gradcam_formant.py:247-248,262-266
+//   cam_heatmap        _compute_cam_from_grads                         mri_gradcam_formant.py:169-200
 //   gap_*              feats.mean(dim=(2,3)) forward / backward        mri_gradcam_formant.py:162
 //   mel_spectrogram    mel_spectrogram / compute_mel_db up to the dB map   meldataset.py:57-93,
 //                      mri2speech_code/preprocess_rtmri_data.py:121-147
@@ -425,6 +429,118 @@ std::tuple<at::Tensor, std::vector<at::Tensor>> bilstm_train_backward(const at::
   return {dx, grads};
 }
 
+// ---- Grad-CAM engine (include/m2s.h "Grad-CAM engine") ---------------------------------------------------
+m2s_gradcam* Gc(int64_t h) {
+  TORCH_CHECK(h != 0, "null gradcam handle");
+  return reinterpret_cast<m2s_gradcam*>(h);
+}
+
+at::Tensor frame_table(at::IntArrayRef idx, const at::Tensor& like) {
+  const std::vector<int> v = host_lengths(idx, "frame index");
+  return at::tensor(v, at::TensorOptions().dtype(at::kInt)).to(like.device());
+}
+
+// frames (T,H,W), mean / std (n_mels), band_mask (n_bands,n_mels) 0/1, frame_idx host list, reduction 0 mean / 1 sum
+// -> heat_seq (n_bands,T,H,W), heat_frame (n_bands,F,H,W), pred_norm (T,n_mels), dpooled (K,T,208) or (0,T,208),
+//    bn_stats (flat)
+std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor, at::Tensor> gradcam(int64_t h, const at::Tensor& frames,
+                                                                               const at::Tensor& mean,
+                                                                               const at::Tensor& std_,
+                                                                               const at::Tensor& band_mask,
+                                                                               at::IntArrayRef frame_idx,
+                                                                               int64_t reduction, bool want_dpooled) {
+  TORCH_CHECK(frames.dim() == 3, "gradcam: frames must be (T,H,W)");
+  TORCH_CHECK(band_mask.dim() == 2, "gradcam: band_mask must be (n_bands,n_mels)");
+  const Guard g(frames.device());
+  const at::Tensor x = f32_on_device(frames, "frames");
+  const at::Tensor mu = f32_on_device(mean, "mean"), sd = f32_on_device(std_, "std");
+  const at::Tensor mask = band_mask.to(at::kCPU, at::kFloat).contiguous();  // validated on the host before any launch
+  const int T = x.size(0), H = x.size(1), W = x.size(2), nb = mask.size(0), nm = m2s_gradcam_n_mels(Gc(h));
+  TORCH_CHECK(T > 0, "gradcam: empty clip");
+  TORCH_CHECK(mask.size(1) == nm && mu.numel() == nm && sd.numel() == nm, "gradcam: mean / std / band_mask must have ",
+              nm, " mel bins");
+  const std::vector<int> fi = host_lengths(frame_idx, "gradcam frame index");
+  const int F = (int)fi.size();
+  for (int v : fi) TORCH_CHECK_INDEX(v >= 0 && v < T, "gradcam: target frame ", v, " outside [0, ", T, ")");
+  const int64_t K = (int64_t)nb * (1 + F);
+  at::Tensor heat_seq = at::empty({nb, T, H, W}, x.options()), heat_frame = at::empty({nb, F, H, W}, x.options());
+  at::Tensor pred = at::empty({T, nm}, x.options());
+  at::Tensor dpooled = at::empty({want_dpooled ? K : 0, T, 208}, x.options());
+  at::Tensor stats = at::empty({(int64_t)m2s_gradcam_bn_stats_floats(Gc(h))}, x.options());
+  const size_t wsb = m2s_gradcam_workspace_bytes(Gc(h), T, H, W, nb, F);
+  TORCH_CHECK(wsb > 0, "libm2s gradcam: ", m2s_last_error());
+  at::Tensor ws = workspace(wsb, x);
+  ok(m2s_gradcam_forward(Gc(h), x.data_ptr<float>(), T, H, W, mu.data_ptr<float>(), sd.data_ptr<float>(),
+                         mask.data_ptr<float>(), nb, fi.data(), F, (int)reduction, heat_seq.data_ptr<float>(),
+                         F ? heat_frame.data_ptr<float>() : nullptr, pred.data_ptr<float>(),
+                         want_dpooled ? dpooled.data_ptr<float>() : nullptr, stats.data_ptr<float>(), ws.data_ptr(),
+                         ws.numel(), S()),
+     "gradcam");
+  return {heat_seq, heat_frame, pred, dpooled, stats};
+}
+
+// pred_norm (T,n_mels), band_mask (n_bands,n_mels) -> dpred (K,T,n_mels)
+at::Tensor gradcam_cotangents(const at::Tensor& pred_, const at::Tensor& mean, const at::Tensor& std_,
+                              const at::Tensor& band_mask, at::IntArrayRef frame_idx, int64_t reduction) {
+  TORCH_CHECK(pred_.dim() == 2 && band_mask.dim() == 2, "gradcam_cotangents: pred_norm (T,n_mels), band_mask (n_bands,n_mels)");
+  const Guard g(pred_.device());
+  const at::Tensor pred = f32_on_device(pred_, "pred_norm"), mu = f32_on_device(mean, "mean");
+  const at::Tensor sd = f32_on_device(std_, "std"), mask = f32_on_device(band_mask, "band_mask");
+  const int T = pred.size(0), nm = pred.size(1), nb = mask.size(0), F = (int)frame_idx.size();
+  TORCH_CHECK(mask.size(1) == nm && mu.numel() == nm && sd.numel() == nm, "gradcam_cotangents: mel bin counts differ");
+  TORCH_CHECK(T > 0 && nb > 0, "gradcam_cotangents: empty input");
+  const at::Tensor fi = frame_table(frame_idx, pred);
+  at::Tensor out = at::empty({(int64_t)nb * (1 + F), T, nm}, pred.options());
+  ok(m2s_gradcam_cotangents(pred.data_ptr<float>(), T, nm, mu.data_ptr<float>(), sd.data_ptr<float>(),
+                            mask.data_ptr<float>(), nb, F ? fi.data_ptr<int>() : nullptr, F, (int)reduction,
+                            out.data_ptr<float>(), S()),
+     "gradcam_cotangents");
+  return out;
+}
+
+// dy (K,T,H), weights as bilstm_train_forward, gates (2,1,T,4H), cells (2,1,T,H) -> dx (K,T,C)
+at::Tensor bilstm_train_backward_multi(const at::Tensor& dy_, const std::vector<at::Tensor>& w, const at::Tensor& gates,
+                                       const at::Tensor& cells) {
+  TORCH_CHECK(dy_.dim() == 3, "bilstm_train_backward_multi: dy must be (K,T,H)");
+  const Guard g(dy_.device());
+  const at::Tensor dy = f32_on_device(dy_, "dy");
+  std::vector<at::Tensor> wc;
+  for (const auto& t : w) wc.push_back(f32_on_device(t, "lstm weight"));
+  const auto p = f32_ptrs(wc, 8, "bilstm_train_backward_multi");
+  const int K = dy.size(0), T = dy.size(1), Hd = wc[1].size(1), C = wc[0].size(1);
+  TORCH_CHECK(dy.size(2) == Hd && wc[0].size(0) == 4 * Hd && wc[1].size(0) == 4 * Hd, "bilstm_train_backward_multi: weight shapes");
+  const at::Tensor gs = f32_on_device(gates, "gates"), cs = f32_on_device(cells, "cells");
+  TORCH_CHECK(gs.sizes() == at::IntArrayRef({2, 1, T, 4 * Hd}) && cs.sizes() == at::IntArrayRef({2, 1, T, Hd}),
+              "bilstm_train_backward_multi: gates (2,1,T,4H) and cells (2,1,T,H) of one sequence");
+  at::Tensor dx = at::empty({K, T, C}, dy.options());
+  if ((int64_t)K * T == 0) return dx;
+  const size_t wsb = m2s_bilstm_train_backward_multi_workspace_bytes(K, T, C, Hd);
+  TORCH_CHECK(wsb > 0, "libm2s bilstm_train_backward_multi: ", m2s_last_error());
+  at::Tensor ws = workspace(wsb, dy);
+  ok(m2s_bilstm_train_backward_multi(dy.data_ptr<float>(), K, T, C, Hd, p.data(), gs.data_ptr<float>(),
+                                     cs.data_ptr<float>(), dx.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "bilstm_train_backward_multi");
+  return dx;
+}
+
+// feats (N,C,h,w), weights (M,C), frame host list (M) -> heat maps (M,H,W)
+at::Tensor cam_heatmap(const at::Tensor& feats_, const at::Tensor& weights_, at::IntArrayRef frame, int64_t H, int64_t W) {
+  TORCH_CHECK(feats_.dim() == 4 && weights_.dim() == 2, "cam_heatmap: feats (N,C,h,w), weights (M,C)");
+  const Guard g(feats_.device());
+  const at::Tensor feats = f32_on_device(feats_, "feats"), wt = f32_on_device(weights_, "weights");
+  const int N = feats.size(0), C = feats.size(1), h = feats.size(2), w = feats.size(3), M = wt.size(0);
+  TORCH_CHECK(wt.size(1) == C && (int64_t)frame.size() == M, "cam_heatmap: one weight row and one frame index per map");
+  TORCH_CHECK(N > 0 && H > 0 && W > 0 && H <= INT32_MAX && W <= INT32_MAX, "cam_heatmap: empty input");
+  for (int64_t v : frame) TORCH_CHECK_INDEX(v >= 0 && v < N, "cam_heatmap: frame ", v, " outside [0, ", N, ")");
+  at::Tensor out = at::empty({M, H, W}, feats.options());
+  if (M == 0) return out;
+  const at::Tensor fi = frame_table(frame, feats);
+  ok(m2s_cam_heatmap(feats.data_ptr<float>(), N, C, h, w, wt.data_ptr<float>(), fi.data_ptr<int>(), M, (int)H, (int)W,
+                     out.data_ptr<float>(), S()),
+     "cam_heatmap");
+  return out;
+}
+
 // x (..., in), w (out, in), b (out) -> y (..., out)
 at::Tensor linear_forward(const at::Tensor& x_, const at::Tensor& w_, const c10::optional<at::Tensor>& b_) {
   const Guard g(x_.device());
@@ -523,6 +639,12 @@ TORCH_LIBRARY(m2s, m) {
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_backward(Tensor dy, Tensor x, Tensor[] weights, Tensor gates, Tensor cells, Tensor hid)"
         " -> (Tensor, Tensor[])");
+  m.def("gradcam(int handle, Tensor frames, Tensor mean, Tensor std, Tensor band_mask, int[] frame_idx, int reduction,"
+        " bool want_dpooled) -> (Tensor, Tensor, Tensor, Tensor, Tensor)");
+  m.def("gradcam_cotangents(Tensor pred_norm, Tensor mean, Tensor std, Tensor band_mask, int[] frame_idx, int reduction)"
+        " -> Tensor");
+  m.def("bilstm_train_backward_multi(Tensor dy, Tensor[] weights, Tensor gates, Tensor cells) -> Tensor");
+  m.def("cam_heatmap(Tensor feats, Tensor weights, int[] frame, int H, int W) -> Tensor");
   m.def("linear_forward(Tensor x, Tensor weight, Tensor? bias) -> Tensor");
   m.def("linear_backward(Tensor dy, Tensor x, Tensor weight) -> (Tensor, Tensor, Tensor)");
   m.def("gap_forward(Tensor x) -> Tensor");
@@ -548,6 +670,10 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);
   m.impl("bilstm_train_backward", &bilstm_train_backward);
+  m.impl("gradcam", &gradcam);
+  m.impl("gradcam_cotangents", &gradcam_cotangents);
+  m.impl("bilstm_train_backward_multi", &bilstm_train_backward_multi);
+  m.impl("cam_heatmap", &cam_heatmap);
   m.impl("linear_forward", &linear_forward);
   m.impl("linear_backward", &linear_backward);
   m.impl("gap_forward", &gap_forward);

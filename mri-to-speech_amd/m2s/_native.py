@@ -116,6 +116,20 @@ def lib():
         "m2s_bilstm_train_workspace_bytes": (sz, [i, i, i, i]),
         "m2s_bilstm_train_forward": (i, [fp, i, i, i, i, vp, fp, fp, fp, fp, vp, sz, vp]),
         "m2s_bilstm_train_backward": (i, [fp, fp, i, i, i, i, vp, fp, fp, fp, fp, vp, vp, sz, vp]),
+        # Grad-CAM engine: band_mask / frame_idx of m2s_gradcam_forward are host arrays, the stage calls take
+        # device pointers throughout
+        "m2s_gradcam_create": (i, [C.POINTER(Tensor), i, i, C.POINTER(vp)]),
+        "m2s_gradcam_destroy": (None, [vp]),
+        "m2s_gradcam_n_mels": (i, [vp]),
+        "m2s_gradcam_bn_stats_floats": (i, [vp]),
+        "m2s_gradcam_chunk": (i, []),
+        "m2s_gradcam_workspace_bytes": (sz, [vp, i, i, i, i, i]),
+        "m2s_gradcam_forward": (i, [vp, fp, i, i, i, fp, fp, C.POINTER(C.c_float), i, C.POINTER(i), i, i, fp, fp, fp,
+                                    fp, fp, vp, sz, vp]),
+        "m2s_gradcam_cotangents": (i, [fp, i, i, fp, fp, fp, i, vp, i, i, fp, vp]),
+        "m2s_bilstm_train_backward_multi_workspace_bytes": (sz, [i, i, i, i]),
+        "m2s_bilstm_train_backward_multi": (i, [fp, i, i, i, i, vp, fp, fp, fp, vp, sz, vp]),
+        "m2s_cam_heatmap": (i, [fp, i, i, i, i, fp, vp, i, i, i, fp, vp]),
         "m2s_linear_forward": (i, [fp, i, i, i, fp, fp, fp, vp]),
         "m2s_linear_backward": (i, [fp, fp, i, i, i, fp, fp, fp, fp, vp]),
         "m2s_gap_forward": (i, [fp, C.c_int64, i, fp, vp]),
@@ -162,6 +176,11 @@ def exported_symbols() -> List[str]:
                         "m2s_cam_destroy", "m2s_cam_bn_layers",
                         "m2s_cam_bn_channels", "m2s_cam_workspace_bytes", "m2s_cam_backbone",
                         "m2s_bilstm_train_workspace_bytes", "m2s_bilstm_train_forward", "m2s_bilstm_train_backward",
+                        "m2s_gradcam_create", "m2s_gradcam_destroy", "m2s_gradcam_n_mels", "m2s_gradcam_bn_stats_floats",
+                        "m2s_gradcam_chunk",
+                        "m2s_gradcam_workspace_bytes", "m2s_gradcam_forward", "m2s_gradcam_cotangents",
+                        "m2s_bilstm_train_backward_multi_workspace_bytes", "m2s_bilstm_train_backward_multi",
+                        "m2s_cam_heatmap",
                         "m2s_linear_forward", "m2s_linear_backward", "m2s_gap_forward", "m2s_gap_backward",
                         "m2s_melspec_create", "m2s_melspec_destroy", "m2s_melspec_n_mels", "m2s_melspec_frames",
                         "m2s_melspec_workspace_bytes", "m2s_melspec_forward",

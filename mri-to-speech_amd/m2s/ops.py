@@ -32,6 +32,9 @@ WINDOW_MERGES = {"latest": 0, "mean": 1}
 STREAM_OPS = ("hifigan_forward_chunk",)
 # analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
 ANALYSIS_OPS = ("mel_spectrogram",)
+# Grad-CAM engine (m2s/gradcam.py; handle = GradCam.handle): every band and target frame of a clip in one call, and
+# its stages (include/m2s.h "Grad-CAM engine")
+GRADCAM_OPS = ("gradcam", "gradcam_cotangents", "bilstm_train_backward_multi", "cam_heatmap")
 
 # timm tf_efficientnetv2_b2 (features_only): stride and output channels of the stem (index 0) and of
 # the 29 blocks that follow (effnet_features' n_blocks = how many of them ran)
@@ -196,6 +199,26 @@ def _register_fakes():
     @f("m2s::bilstm_train_backward")
     def _lstm_bwd(dy, x, weights, gates, cells, hid):
         return torch.empty_like(x), [torch.empty_like(weights[i]) for i in (0, 1, 2, 4, 5, 6)]
+
+    @f("m2s::gradcam")
+    def _gradcam(handle, frames, mean, std, band_mask, frame_idx, reduction, want_dpooled):
+        t, h, w = frames.shape
+        nb, nm, nf = band_mask.shape[0], band_mask.shape[1], len(frame_idx)
+        e = lambda *shape: frames.new_empty(shape, dtype=torch.float32)
+        return (e(nb, t, h, w), e(nb, nf, h, w), e(t, nm), e(nb * (1 + nf) if want_dpooled else 0, t, 208),
+                e(CAM_BN_STATS))
+
+    @f("m2s::gradcam_cotangents")
+    def _gradcam_cot(pred_norm, mean, std, band_mask, frame_idx, reduction):
+        return pred_norm.new_empty((band_mask.shape[0] * (1 + len(frame_idx)), *pred_norm.shape), dtype=torch.float32)
+
+    @f("m2s::bilstm_train_backward_multi")
+    def _lstm_bwd_multi(dy, weights, gates, cells):
+        return dy.new_empty((dy.shape[0], dy.shape[1], weights[0].shape[1]), dtype=torch.float32)
+
+    @f("m2s::cam_heatmap")
+    def _heatmap(feats, weights, frame, H, W):
+        return feats.new_empty((weights.shape[0], H, W), dtype=torch.float32)
 
     @f("m2s::linear_forward")
     def _lin(x, weight, bias):
