@@ -43,71 +43,59 @@ CamBackbone::CamBackbone(const StateDict& sd, int device) : device_(device) {
     stem_bn_ = add_bn(P + "bn1", EFF_STEM);
   }
   auto zero = [](int) { return 0.f; };
-  int cin = EFF_STEM;
-  for (int s = 0; s < 6; ++s) {
-    const StageDef& sdf = kStages[s];
-    for (int r = 0; r < sdf.reps; ++r) {
-      Blk b;
-      b.type = sdf.type;
-      b.stride = r == 0 ? sdf.stride : 1;
-      b.cin = cin;
-      b.cout = sdf.cout;
-      b.skip = b.stride == 1 && cin == sdf.cout;
-      const std::string q = P + "blocks." + std::to_string(s) + "." + std::to_string(r) + ".";
-      auto conv3 = [&](PConv& pc, const std::string& wk, int ci, int co) {
-        const float* w = need(sd, wk, {co, ci, 3, 3}).data;
-        pc = make_pconv(KIND_CONV2D, ci, co, 9, M2S_DT_F32);
-        pc.ks = 3;
-        pc.stride = b.stride;
-        pc.macs_per_row = 9.0 * co * ci;
-        pack_conv(arena_, M2S_DT_F32, pc, [&](int, int n, int t, int c) { return w[((size_t)n * ci + c) * 9 + t]; }, zero);
-      };
-      auto conv1 = [&](PConv& pc, const std::string& wk, int ci, int co) {
-        const float* w = need(sd, wk, {co, ci, 1, 1}).data;
-        pc = make_pconv(KIND_GEMM, ci, co, 1, M2S_DT_F32);
-        pc.macs_per_row = (double)co * ci;
-        pack_conv(arena_, M2S_DT_F32, pc, [&](int, int n, int, int c) { return w[(size_t)n * ci + c]; }, zero);
-      };
-      if (b.type == 0) {
-        conv3(b.c1, q + "conv.weight", cin, b.cout);
-        b.bn[0] = add_bn(q + "bn1", b.cout);
-      } else if (b.type == 1) {
-        b.mid = make_divisible(cin * (double)sdf.exp);
-        conv3(b.c1, q + "conv_exp.weight", cin, b.mid);
-        b.bn[0] = add_bn(q + "bn1", b.mid);
-        conv1(b.c2, q + "conv_pwl.weight", b.mid, b.cout);
-        b.bn[1] = add_bn(q + "bn2", b.cout);
-      } else {
-        b.mid = make_divisible(cin * (double)sdf.exp);
-        b.rd = (int)std::lround(b.mid * (sdf.se / sdf.exp));
-        const int m = b.mid, cs = chan_stride(m), rd = b.rd;
-        conv1(b.c1, q + "conv_pw.weight", cin, m);
-        b.bn[0] = add_bn(q + "bn1", m);
-        const float* wd = need(sd, q + "conv_dw.weight", {m, 1, 3, 3}).data;
-        std::vector<float> w9((size_t)cs * 9, 0.f);
-        for (int c = 0; c < m; ++c)
-          for (int t = 0; t < 9; ++t) w9[(size_t)t * cs + c] = wd[(size_t)c * 9 + t];
-        b.dw = arena_.add_vec(w9);
-        b.bn[1] = add_bn(q + "bn2", m);
-        const float* w1 = need(sd, q + "se.conv_reduce.weight", {rd, m, 1, 1}).data;
-        const float* b1 = need(sd, q + "se.conv_reduce.bias", {rd}).data;
-        const float* w2 = need(sd, q + "se.conv_expand.weight", {m, rd, 1, 1}).data;
-        const float* b2 = need(sd, q + "se.conv_expand.bias", {m}).data;
-        b.se1 = make_pconv(KIND_GEMM, m, rd, 1, M2S_DT_F32);
-        b.se1.macs_per_row = (double)m * rd;
-        pack_conv(arena_, M2S_DT_F32, b.se1, [&](int, int n, int, int c) { return w1[(size_t)n * m + c]; },
-                  [&](int n) { return b1[n]; });
-        b.se2 = make_pconv(KIND_GEMM, rd, m, 1, M2S_DT_F32);
-        b.se2.macs_per_row = (double)m * rd;
-        pack_conv(arena_, M2S_DT_F32, b.se2, [&](int, int n, int, int c) { return w2[(size_t)n * rd + c]; },
-                  [&](int n) { return b2[n]; });
-        conv1(b.c2, q + "conv_pwl.weight", m, b.cout);
-        b.bn[2] = add_bn(q + "bn3", b.cout);
-      }
-      blocks_.push_back(b);
-      cin = sdf.cout;
+  for_each_backbone_block([&](const BlockDef& d) {
+    Blk b{d};
+    const std::string q = d.key();
+    const int cin = d.cin;
+    auto conv3 = [&](PConv& pc, const std::string& wk, int ci, int co) {
+      const float* w = need(sd, wk, {co, ci, 3, 3}).data;
+      pc = make_pconv(KIND_CONV2D, ci, co, 9, M2S_DT_F32);
+      pc.ks = 3;
+      pc.stride = b.stride;
+      pc.macs_per_row = 9.0 * co * ci;
+      pack_conv(arena_, M2S_DT_F32, pc, [&](int, int n, int t, int c) { return w[((size_t)n * ci + c) * 9 + t]; }, zero);
+    };
+    auto conv1 = [&](PConv& pc, const std::string& wk, int ci, int co) {
+      const float* w = need(sd, wk, {co, ci, 1, 1}).data;
+      pc = make_pconv(KIND_GEMM, ci, co, 1, M2S_DT_F32);
+      pc.macs_per_row = (double)co * ci;
+      pack_conv(arena_, M2S_DT_F32, pc, [&](int, int n, int, int c) { return w[(size_t)n * ci + c]; }, zero);
+    };
+    if (b.type == 0) {
+      conv3(b.c1, q + "conv.weight", cin, b.cout);
+      b.bn[0] = add_bn(q + "bn1", b.cout);
+    } else if (b.type == 1) {
+      conv3(b.c1, q + "conv_exp.weight", cin, b.mid);
+      b.bn[0] = add_bn(q + "bn1", b.mid);
+      conv1(b.c2, q + "conv_pwl.weight", b.mid, b.cout);
+      b.bn[1] = add_bn(q + "bn2", b.cout);
+    } else {
+      const int m = b.mid, cs = chan_stride(m), rd = b.rd;
+      conv1(b.c1, q + "conv_pw.weight", cin, m);
+      b.bn[0] = add_bn(q + "bn1", m);
+      const float* wd = need(sd, q + "conv_dw.weight", {m, 1, 3, 3}).data;
+      std::vector<float> w9((size_t)cs * 9, 0.f);
+      for (int c = 0; c < m; ++c)
+        for (int t = 0; t < 9; ++t) w9[(size_t)t * cs + c] = wd[(size_t)c * 9 + t];
+      b.dw = arena_.add_vec(w9);
+      b.bn[1] = add_bn(q + "bn2", m);
+      const float* w1 = need(sd, q + "se.conv_reduce.weight", {rd, m, 1, 1}).data;
+      const float* b1 = need(sd, q + "se.conv_reduce.bias", {rd}).data;
+      const float* w2 = need(sd, q + "se.conv_expand.weight", {m, rd, 1, 1}).data;
+      const float* b2 = need(sd, q + "se.conv_expand.bias", {m}).data;
+      b.se1 = make_pconv(KIND_GEMM, m, rd, 1, M2S_DT_F32);
+      b.se1.macs_per_row = (double)m * rd;
+      pack_conv(arena_, M2S_DT_F32, b.se1, [&](int, int n, int, int c) { return w1[(size_t)n * m + c]; },
+                [&](int n) { return b1[n]; });
+      b.se2 = make_pconv(KIND_GEMM, rd, m, 1, M2S_DT_F32);
+      b.se2.macs_per_row = (double)m * rd;
+      pack_conv(arena_, M2S_DT_F32, b.se2, [&](int, int n, int, int c) { return w2[(size_t)n * rd + c]; },
+                [&](int n) { return b2[n]; });
+      conv1(b.c2, q + "conv_pwl.weight", m, b.cout);
+      b.bn[2] = add_bn(q + "bn3", b.cout);
     }
-  }
+    blocks_.push_back(b);
+  });
   arena_.upload(device);
   for (auto& b : blocks_) {
     b.c1.resolve(arena_);
@@ -137,27 +125,15 @@ struct CamBufs {  // ping-pong block outputs, expanded maps, SE means / hidden /
 
 static CamDims cam_dims(int H, int W) {
   CamDims d;
-  int oh, ow, p;
-  same_pad(H, 3, 2, &oh, &p);
-  same_pad(W, 3, 2, &ow, &p);
-  d.io = (size_t)oh * ow * chan_stride(EFF_STEM);
-  int cin = EFF_STEM;
-  for (int s = 0; s < 6; ++s)
-    for (int r = 0; r < kStages[s].reps; ++r) {
-      const int st = r == 0 ? kStages[s].stride : 1;
-      int nh, nw;
-      same_pad(oh, 3, st, &nh, &p);
-      same_pad(ow, 3, st, &nw, &p);
-      if (kStages[s].type != 0) {
-        const int cs = chan_stride(make_divisible(cin * (double)kStages[s].exp));
-        d.mid = std::max(d.mid, (size_t)(kStages[s].type == 2 ? oh * ow : nh * nw) * cs);
-        d.cs_mid = std::max(d.cs_mid, cs);
-      }
-      d.io = std::max(d.io, (size_t)nh * nw * chan_stride(kStages[s].cout));
-      cin = kStages[s].cout;
-      oh = nh;
-      ow = nw;
+  for_each_backbone_map(H, W, [&](const BlockDef& b, const BlockMap& m) {
+    if (b.type != 0) {
+      const int cs = chan_stride(b.mid);
+      d.mid = std::max(d.mid, (size_t)(b.type == 2 ? m.ih * m.iw : m.oh * m.ow) * cs);
+      d.cs_mid = std::max(d.cs_mid, cs);
     }
+    // every map a block reads or writes (block 0 reads the stem's output)
+    d.io = std::max({d.io, (size_t)m.ih * m.iw * chan_stride(b.cin), (size_t)m.oh * m.ow * chan_stride(b.cout)});
+  });
   return d;
 }
 

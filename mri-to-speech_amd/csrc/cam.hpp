@@ -118,9 +118,7 @@ class CamBackbone {
     int C = 0;
     size_t g = 0, b = 0;  // gamma, beta (arena offsets)
   };
-  struct Blk {
-    int type = 0, stride = 1, cin = 0, cout = 0, mid = 0, rd = 0;
-    bool skip = false;
+  struct Blk : BlockDef {
     PConv c1, c2, se1, se2;
     size_t dw = 0;
     int bn[3] = {-1, -1, -1};

@@ -1,46 +1,21 @@
-// Weight packing and execution plans for the acoustic model (CNN + BiLSTM + head) and the
-// HiFi-GAN generator.  Packing mirrors what the reference does at load time and folds what is
-// constant at inference:
-//   * BatchNorm (eps 1e-3, torch's alpha = w / sqrt(var + eps), beta = b - mean * alpha) into
-//     the preceding conv (timm BatchNormAct2d);
-//   * the grey -> RGB repeat (mri_acoustic_model.py:43-44) into conv_stem (sum over in-channels);
-//   * weight norm w = g * v / ||v|| (models.py:94-108; run_mri_video_inference.py:99-115);
-//   * LSTM b_ih + b_hh.
+// Execution plans of the acoustic model (CNN + BiLSTM + head) and the HiFi-GAN generator: which kernel runs for
+// which block, shape and switch, the scratch layouts, and the ragged / windowed / chunk calls.  The weights are
+// packed by pack_acoustic.cpp / pack_vocoder.cpp (host code); the constructors here read the switches, pack,
+// upload the arena and resolve device pointers.
 #include "model.hpp"
 
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <type_traits>
+#include <utility>
 
 #include "pack.hpp"
 #include "prof.hpp"
 
 namespace m2s {
-
-// ------------------------------------------------------------------------------------------
-StateDict make_state_dict(const m2s_tensor* t, int n) {
-  StateDict sd;
-  for (int i = 0; i < n; ++i) {
-    M2S_CHECK(t[i].name != nullptr, "state dict entry without a name");
-    if (t[i].elem != M2S_ELEM_F32) continue;  // num_batches_tracked etc.
-    M2S_CHECK(t[i].ndim >= 0 && t[i].ndim <= 4, std::string("bad ndim for ") + t[i].name);
-    HostTensor h;
-    h.data = static_cast<const float*>(t[i].data);
-    for (int d = 0; d < t[i].ndim; ++d) h.shape.push_back(t[i].shape[d]);
-    sd[t[i].name] = h;
-  }
-  return sd;
-}
-
-
-size_t Arena::add(const void* p, size_t bytes) {
-  size_t off = (host_.size() + 255) & ~size_t(255);
-  host_.resize(off + bytes);
-  if (bytes) std::memcpy(host_.data() + off, p, bytes);
-  return off;
-}
 
 void Arena::upload(int device) {
   M2S_HIP(hipSetDevice(device));
@@ -53,450 +28,33 @@ Arena::~Arena() {
   if (dev_) (void)hipFree(dev_);
 }
 
+// The M2S_* switches: read once, when an engine is created; "0" turns a flag off, anything else on.
+static void env_flag(const char* name, bool& v) {
+  if (const char* e = std::getenv(name)) v = std::strcmp(e, "0") != 0;
+}
+static void env_int(const char* name, int& v) {
+  if (const char* e = std::getenv(name)) v = std::atoi(e);
+}
 
 // ------------------------------------------------------------------------------------------
 // Acoustic model
-
-struct BN {
-  std::vector<float> a, b;
-};
-static BN fold_bn(const StateDict& sd, const std::string& p, int c) {
-  const float* w = need(sd, p + ".weight", {c}).data;
-  const float* bb = need(sd, p + ".bias", {c}).data;
-  const float* m = need(sd, p + ".running_mean", {c}).data;
-  const float* v = need(sd, p + ".running_var", {c}).data;
-  BN r;
-  r.a.resize(c);
-  r.b.resize(c);
-  for (int i = 0; i < c; ++i) {
-    const float invstd = 1.0f / std::sqrt(v[i] + 1e-3f);
-    r.a[i] = invstd * w[i];
-    r.b[i] = bb[i] - m[i] * r.a[i];
-  }
-  return r;
-}
-
 Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int device)
     : dtype_(dtype), device_(device), n_mels_(n_mels), hidden_(hidden) {
-  M2S_CHECK(dtype == M2S_DT_F32 || dtype == M2S_DT_BF16 || dtype == M2S_DT_BF16X3 || dtype == M2S_DT_FP8, "bad dtype");
-  M2S_CHECK(n_mels > 0 && hidden > 0 && hidden % 8 == 0, "bad n_mels / rnn_hidden");
-  if (const char* e = std::getenv("M2S_IR_FUSED")) ir_fused_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_IR_WS")) ir_ws_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_IR_WS_S2")) ir_ws_s2_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_IRWS_MIN")) irws_min_ = std::atoi(e);
-  if (const char* e = std::getenv("M2S_IRWS_F32")) irws_f32_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_SEWS_MIN")) sews_min_cus_ = std::atoi(e);
-  if (const char* e = std::getenv("M2S_STEM_FUSED")) stem_fused_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_EXPAND")) f8_expand_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_S2")) f8_s2_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_ER")) f8_er_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_ER8_X8")) er8_x8_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_ER2")) f8_er2_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_SE_Y8")) se_y8_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_SE_FUSED")) se_fused_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_ER_FUSED")) er_fused_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_SE_SP")) se_sp_ = std::strcmp(e, "0") != 0;  // A/B only
-  if (const char* e = std::getenv("M2S_SE_WS")) se_ws_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_ER_MRG")) er_mrg_ = std::strcmp(e, "0") != 0;  // A/B and tests only
-  if (const char* e = std::getenv("M2S_IR_S2BAND")) ir_s2band_ = std::strcmp(e, "0") != 0;  // A/B and tests only
-  if (const char* e = std::getenv("M2S_LSTM_PERSISTENT")) lstm_persistent_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_LSTM_MID")) lstm_mid_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_LSTM_X3")) lstm_x3_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_LSTM_X3G")) lstm_x3g_ = std::strcmp(e, "0") != 0;
-  const std::string P = "cnn.backbone.";
-  {  // stem: fold repeat(1,3,1,1) by summing the 3 input channels; then BN
-    const float* w = need(sd, P + "conv_stem.weight", {EFF_STEM, 3, 3, 3}).data;
-    BN bn = fold_bn(sd, P + "bn1", EFF_STEM);
-    std::vector<float> w9(EFF_STEM * 9);
-    for (int o = 0; o < EFF_STEM; ++o)
-      for (int t = 0; t < 9; ++t)
-        w9[o * 9 + t] = (w[(o * 3 + 0) * 9 + t] + w[(o * 3 + 1) * 9 + t] + w[(o * 3 + 2) * 9 + t]) * bn.a[o];
-    stem_w_ = arena_.add_vec(w9);
-    stem_b_ = arena_.add_vec(bn.b);
-  }
-  // fp8 engines run the bf16 kernels (and bf16 packings) except the stride-1 IR blocks' SE-gated conv_pwl,
-  // which gets an e4m3 copy for the block-scaled MFMA (gemm128.hip) below
-  const int pdt = dtype == M2S_DT_FP8 ? M2S_DT_BF16 : dtype;
-  int cin = EFF_STEM;
-  for (int s = 0; s < 6; ++s) {
-    const StageDef& sdf = kStages[s];
-    for (int r = 0; r < sdf.reps; ++r) {
-      Block b;
-      b.type = sdf.type;
-      b.stride = r == 0 ? sdf.stride : 1;
-      b.cin = cin;
-      b.cout = sdf.cout;
-      b.skip = b.stride == 1 && cin == sdf.cout;
-      const std::string q = P + "blocks." + std::to_string(s) + "." + std::to_string(r) + ".";
-      const int k = sdf.k;
-      auto conv2d_kxk = [&](PConv& pc, const std::string& wk, int ci, int co, const BN& bn) {
-        const float* w = need(sd, wk, {co, ci, k, k}).data;
-        pc = make_pconv(KIND_CONV2D, ci, co, k * k, pdt);
-        pc.ks = k;
-        pc.stride = b.stride;
-        pc.macs_per_row = (double)co * ci * k * k;
-        pack_conv(arena_, pdt, pc, [&](int, int n, int t, int c) { return w[((size_t)n * ci + c) * k * k + t] * bn.a[n]; },
-                  [&](int n) { return bn.b[n]; });
-      };
-      auto conv1x1 = [&](PConv& pc, const std::string& wk, int ci, int co, const BN& bn) {
-        const float* w = need(sd, wk, {co, ci, 1, 1}).data;
-        pc = make_pconv(KIND_GEMM, ci, co, 1, pdt);
-        pc.macs_per_row = (double)co * ci;
-        pack_conv(arena_, pdt, pc, [&](int, int n, int, int c) { return w[(size_t)n * ci + c] * bn.a[n]; },
-                  [&](int n) { return bn.b[n]; });
-      };
-      if (b.type == 0) {
-        conv2d_kxk(b.c1, q + "conv.weight", cin, b.cout, fold_bn(sd, q + "bn1", b.cout));
-      } else if (b.type == 1) {
-        b.mid = make_divisible(cin * (double)sdf.exp);
-        conv2d_kxk(b.c1, q + "conv_exp.weight", cin, b.mid, fold_bn(sd, q + "bn1", b.mid));
-        conv1x1(b.c2, q + "conv_pwl.weight", b.mid, b.cout, fold_bn(sd, q + "bn2", b.cout));
-        if (dtype == M2S_DT_BF16X3 && b.stride == 1 && b.skip && k == 3 &&
-            er_sp_supported(32, 32, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
-          // er_sp_fused.hip stage stream: per conv_exp k-step (tap, 32 input channels) a W_hi and a W_lo
-          // stage of nt fragments [n16][lane][8]; then conv_pwl's W_hi stages and W_lo stages, piece
-          // j = (k-step j / ON, n16 j % ON), K permuted as in er_fused.hip
-          int nt = 0;
-          const int csi = b.c1.cs_in, cso = chan_stride(b.cout), nst = er_sp_nt_stages(csi, b.mid, cso, &nt);
-          const int kc = csi / 32, nce = 9 * kc * 2, on_n = cso / 16, pn = on_n * (b.mid / 32), nps = (pn + nt - 1) / nt;
-          const float* we = need(sd, q + "conv_exp.weight", {b.mid, cin, 3, 3}).data;
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, b.mid, 1, 1}).data;
-          const BN e1 = fold_bn(sd, q + "bn1", b.mid), e2 = fold_bn(sd, q + "bn2", b.cout);
-          std::vector<uint16_t> st((size_t)nst * nt * 64 * 8, 0);
-          for (int sg = 0; sg < nst; ++sg)
-            for (int pc = 0; pc < nt; ++pc)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int row = ln & 15, g8 = ln >> 4;
-                  float v = 0.f;
-                  int plane;
-                  if (sg < nce) {
-                    plane = sg & 1;
-                    const int ks = sg >> 1, t = ks / kc, c = (ks % kc) * 32 + 8 * g8 + e, n = 16 * pc + row;
-                    if (c < cin) v = we[((size_t)n * cin + c) * 9 + t] * e1.a[n];
-                  } else {
-                    plane = (sg - nce) / nps;
-                    const int j = ((sg - nce) % nps) * nt + pc;
-                    if (j >= pn) continue;
-                    const int kk = j / on_n, on = j % on_n, o = on * 16 + row;
-                    const int c = 32 * kk + (e < 4 ? 4 * g8 + e : 16 + 4 * g8 + e - 4);
-                    if (o < b.cout) v = wq[(size_t)o * b.mid + c] * e2.a[o];
-                  }
-                  uint16_t hi, lo;
-                  split_host(v, &hi, &lo);
-                  st[(((size_t)sg * nt + pc) * 64 + ln) * 8 + e] = plane == 0 ? hi : lo;
-                }
-          b.er_sp_w = arena_.add_vec(st);
-          b.er_sp = true;
-        } else if (dtype == M2S_DT_BF16X3 && b.stride == 2 && k == 3 &&
-                   ers2_sp_supported(8, 16, b.c1.cs_in, b.mid, chan_stride(b.cout))) {
-          // ers2_sp_kernel (ers2_fused.hip): conv_exp [hi/lo][k-step][n16][lane][8] (lane groups 0-1:
-          // tap 2s, 2-3: tap 2s + 1), conv_pwl [hi/lo][n16][k-step][lane][8] with the permuted K
-          const int csi = b.c1.cs_in, cso = chan_stride(b.cout), ks_n = (9 * csi + 31) / 32, ntn = b.mid / 16;
-          const int onn = cso / 16, pkn = b.mid / 32;
-          const float* we = need(sd, q + "conv_exp.weight", {b.mid, cin, 3, 3}).data;
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, b.mid, 1, 1}).data;
-          const BN e1 = fold_bn(sd, q + "bn1", b.mid), e2 = fold_bn(sd, q + "bn2", b.cout);
-          const size_t fe_half = (size_t)ks_n * ntn * 64 * 8, fp_half = (size_t)onn * pkn * 64 * 8;
-          std::vector<uint16_t> fe(2 * fe_half, 0), fp(2 * fp_half, 0);
-          for (int s2 = 0; s2 < ks_n; ++s2)
-            for (int nt = 0; nt < ntn; ++nt)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int g8 = ln >> 4, n = nt * 16 + (ln & 15), t = 2 * s2 + (g8 >> 1), c = 8 * (g8 & 1) + e;
-                  const float v = t < 9 && c < cin ? we[((size_t)n * cin + c) * 9 + t] * e1.a[n] : 0.f;
-                  const size_t i = (((size_t)s2 * ntn + nt) * 64 + ln) * 8 + e;
-                  split_host(v, &fe[i], &fe[fe_half + i]);
-                }
-          for (int on = 0; on < onn; ++on)
-            for (int ks = 0; ks < pkn; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int n = on * 16 + (ln & 15), g4 = 4 * (ln >> 4);
-                  const int c = 32 * ks + (e < 4 ? g4 + e : 16 + g4 + e - 4);
-                  const float v = n < b.cout ? wq[(size_t)n * b.mid + c] * e2.a[n] : 0.f;
-                  const size_t i = (((size_t)on * pkn + ks) * 64 + ln) * 8 + e;
-                  split_host(v, &fp[i], &fp[fp_half + i]);
-                }
-          b.er_wexp = arena_.add_vec(fe);
-          b.er_wpwl = arena_.add_vec(fp);
-          b.ers_sp = true;
-        } else if (pdt == M2S_DT_BF16 && b.stride == 1 && b.skip && k == 3 &&
-            er_fused_supported(64, 64, cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-          // er_fused.hip operand orders: conv_exp [tap][n16][lane][8] (lane = (k8 group, row));
-          // conv_pwl [n16][k-step][lane][8] with the k-slot permutation of the kernel's header
-          const float* we = need(sd, q + "conv_exp.weight", {b.mid, cin, 3, 3}).data;
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, b.mid, 1, 1}).data;
-          const BN e1 = fold_bn(sd, q + "bn1", b.mid), e2 = fold_bn(sd, q + "bn2", b.cout);
-          std::vector<uint16_t> fe((size_t)9 * 8 * 64 * 8), fp((size_t)2 * 4 * 64 * 8);
-          for (int t = 0; t < 9; ++t)
-            for (int nt = 0; nt < 8; ++nt)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int n = nt * 16 + (ln & 15), c = 8 * (ln >> 4) + e;
-                  fe[(((size_t)t * 8 + nt) * 64 + ln) * 8 + e] = f2bf_host(we[((size_t)n * cin + c) * 9 + t] * e1.a[n]);
-                }
-          for (int on = 0; on < 2; ++on)
-            for (int ks = 0; ks < 4; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int n = on * 16 + (ln & 15), g4 = 4 * (ln >> 4);
-                  const int c = 32 * ks + (e < 4 ? g4 + e : 16 + g4 + e - 4);
-                  fp[(((size_t)on * 4 + ks) * 64 + ln) * 8 + e] = f2bf_host(wq[(size_t)n * b.mid + c] * e2.a[n]);
-                }
-          b.er_wexp = arena_.add_vec(fe);
-          b.er_wpwl = arena_.add_vec(fp);
-          b.er_frag = true;
-          if (dtype == M2S_DT_FP8) {
-            // er8_fused.hip: conv_exp [q][nt][half][lane][16 B], byte 16 half + j of lane (r16, g) = tap 4q + g
-            // (zero past tap 8), input channel 16 half + j of output channel 16 nt + r16; conv_pwl
-            // [on][half][lane][16 B], byte b = 4 nt + e of lane (r16, g) = mid channel 16 nt + 4 g + e
-            std::vector<float> s1(128, 1.f), s2(32, 1.f);
-            auto wexp_at = [&](int n, int c, int t) { return we[((size_t)n * cin + c) * 9 + t] * e1.a[n]; };
-            for (int n = 0; n < 128; ++n) {
-              float amax = 0.f;
-              for (int c = 0; c < 32; ++c)
-                for (int t = 0; t < 9; ++t) amax = std::max(amax, std::fabs(wexp_at(n, c, t)));
-              if (amax > 0.f) s1[n] = amax / 448.f;
-            }
-            for (int o = 0; o < 32; ++o) {
-              float amax = 0.f;
-              for (int c = 0; c < 128; ++c) amax = std::max(amax, std::fabs(wq[(size_t)o * b.mid + c] * e2.a[o]));
-              if (amax > 0.f) s2[o] = amax / 448.f;
-            }
-            std::vector<uint8_t> f8e((size_t)3 * 8 * 2 * 64 * 16, 0), f8p((size_t)2 * 2 * 64 * 16, 0);
-            for (int q4 = 0; q4 < 3; ++q4)
-              for (int nt = 0; nt < 8; ++nt)
-                for (int h = 0; h < 2; ++h)
-                  for (int ln = 0; ln < 64; ++ln)
-                    for (int j = 0; j < 16; ++j) {
-                      const int t = 4 * q4 + (ln >> 4), n = nt * 16 + (ln & 15), c = 16 * h + j;
-                      if (t < 9)
-                        f8e[((((size_t)q4 * 8 + nt) * 2 + h) * 64 + ln) * 16 + j] =
-                            e4m3_bits_host(e4m3_host(wexp_at(n, c, t) / s1[n]));
-                    }
-            for (int on = 0; on < 2; ++on)
-              for (int h = 0; h < 2; ++h)
-                for (int ln = 0; ln < 64; ++ln)
-                  for (int j = 0; j < 16; ++j) {
-                    const int o = on * 16 + (ln & 15), bb = 16 * h + j, c = 16 * (bb >> 2) + 4 * (ln >> 4) + (bb & 3);
-                    f8p[(((size_t)on * 2 + h) * 64 + ln) * 16 + j] =
-                        e4m3_bits_host(e4m3_host(wq[(size_t)o * b.mid + c] * e2.a[o] / s2[o]));
-                  }
-            b.er8_wexp = arena_.add_vec(f8e);
-            b.er8_sexp = arena_.add_vec(s1);
-            b.er8_wpwl = arena_.add_vec(f8p);
-            b.er8_spwl = arena_.add_vec(s2);
-            b.er8 = true;
-          }
-        } else if (pdt == M2S_DT_BF16 && b.stride == 1 && b.skip && k == 3 &&
-                   er2_fused_supported(32, 32, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-          // er2_fused.hip stage stream [20][16 pieces][lane][8]: stages 0..17 = conv_exp k-step s (tap
-          // s / 2, input channels 32 (s % 2) ..), piece = n16; stages 18 / 19 = conv_pwl k-steps 0..3 /
-          // 4..6, piece = local k-step * 4 + n16, with er_fused.hip's k-slot permutation
-          const float* we = need(sd, q + "conv_exp.weight", {b.mid, cin, 3, 3}).data;
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, b.mid, 1, 1}).data;
-          const BN e1 = fold_bn(sd, q + "bn1", b.mid), e2 = fold_bn(sd, q + "bn2", b.cout);
-          std::vector<uint16_t> st((size_t)er2_stage_elems(), 0);
-          for (int sg = 0; sg < 20; ++sg)
-            for (int pc = 0; pc < 16; ++pc)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int row = ln & 15, g8 = ln >> 4;
-                  float v = 0.f;
-                  if (sg < 18) {
-                    const int n = 16 * pc + row, c = (sg & 1) * 32 + 8 * g8 + e, t = sg >> 1;
-                    if (pc < 14 && c < cin) v = we[((size_t)n * cin + c) * 9 + t] * e1.a[n];
-                  } else {
-                    const int kk = pc >> 2, n = 16 * (pc & 3) + row, ks = (sg == 18 ? 0 : 4) + kk;
-                    const int c = 32 * ks + (e < 4 ? 4 * g8 + e : 16 + 4 * g8 + e - 4);
-                    if ((sg == 18 || kk < 3) && n < b.cout) v = wq[(size_t)n * b.mid + c] * e2.a[n];
-                  }
-                  st[(((size_t)sg * 16 + pc) * 64 + ln) * 8 + e] = f2bf_host(v);
-                }
-          b.er_wexp = arena_.add_vec(st);
-          b.er_frag = true;
-          if (dtype == M2S_DT_FP8 && er8w_fused_supported(32, 32, b.c1.cs_in, b.mid, b.cout)) {
-            // er8w_fused.hip stage stream: conv_exp K step q = [nt 0..15][half][lane (r16, g)][16 B], byte 16 half + j =
-            // tap 2q + (g >> 1), input channel 32 (g & 1) + 16 half + j of output channel 16 nt + r16 (zero past tap 8,
-            // channel 55, mid channel 223); conv_pwl [on][kq][half][lane][16 B], byte b = 16 half + j = mid channel
-            // 16 (8 kq + b / 4) + 4 g + (b & 3) of output channel 16 on + r16.  Weights / per-channel scale s = amax / 448
-            const int mid = b.mid, co = b.cout;
-            std::vector<float> s1(mid, 1.f), s2(64, 1.f);
-            auto wexp_at = [&](int n, int c, int t) { return we[((size_t)n * cin + c) * 9 + t] * e1.a[n]; };
-            for (int n = 0; n < mid; ++n) {
-              float amax = 0.f;
-              for (int c = 0; c < cin; ++c)
-                for (int t = 0; t < 9; ++t) amax = std::max(amax, std::fabs(wexp_at(n, c, t)));
-              if (amax > 0.f) s1[n] = amax / 448.f;
-            }
-            for (int o = 0; o < co; ++o) {
-              float amax = 0.f;
-              for (int c = 0; c < mid; ++c) amax = std::max(amax, std::fabs(wq[(size_t)o * mid + c] * e2.a[o]));
-              if (amax > 0.f) s2[o] = amax / 448.f;
-            }
-            std::vector<uint8_t> w8(er8w_stream_bytes(), 0);
-            for (int q2 = 0; q2 < 5; ++q2)
-              for (int nt = 0; nt < 16; ++nt)
-                for (int h = 0; h < 2; ++h)
-                  for (int ln = 0; ln < 64; ++ln)
-                    for (int j = 0; j < 16; ++j) {
-                      const int g4 = ln >> 4, t = 2 * q2 + (g4 >> 1), c = 32 * (g4 & 1) + 16 * h + j, n = 16 * nt + (ln & 15);
-                      if (t < 9 && c < cin && n < mid)
-                        w8[(((((size_t)q2 * 16 + nt) * 2 + h) * 64 + ln) * 16) + j] = e4m3_bits_host(e4m3_host(wexp_at(n, c, t) / s1[n]));
-                    }
-            const size_t pw0 = (size_t)5 * 32 * 1024;
-            for (int on = 0; on < 4; ++on)
-              for (int kq = 0; kq < 2; ++kq)
-                for (int h = 0; h < 2; ++h)
-                  for (int ln = 0; ln < 64; ++ln)
-                    for (int j = 0; j < 16; ++j) {
-                      const int o = 16 * on + (ln & 15), bb = 16 * h + j, ntp = 8 * kq + (bb >> 2);
-                      const int c = 16 * ntp + 4 * (ln >> 4) + (bb & 3);
-                      if (o < co && ntp < mid / 16)
-                        w8[pw0 + (((((size_t)on * 2 + kq) * 2 + h) * 64 + ln) * 16) + j] =
-                            e4m3_bits_host(e4m3_host(wq[(size_t)o * mid + c] * e2.a[o] / s2[o]));
-                    }
-            b.er8w_w = arena_.add_vec(w8);
-            b.er8w_sexp = arena_.add_vec(s1);
-            b.er8w_spwl = arena_.add_vec(s2);
-            b.er8w = true;
-          }
-        } else if (pdt == M2S_DT_BF16 && b.stride == 2 && k == 3 &&
-                   ers2_fused_supported(8, 16, b.c1.cs_in, b.mid, chan_stride(b.cout), b.c1.kp, b.c2.kp)) {
-          // ers2_fused.hip: conv_exp [k-step][n16][lane][8] (CIN 16: lane groups 0-1 tap 2s, 2-3 tap
-          // 2s + 1; CIN 32: tap s), conv_pwl [n16][k-step][lane][8] with the permuted K
-          const int csi = b.c1.cs_in, cso = chan_stride(b.cout), ks_n = (9 * csi + 31) / 32;
-          const float* we = need(sd, q + "conv_exp.weight", {b.mid, cin, 3, 3}).data;
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, b.mid, 1, 1}).data;
-          const BN e1 = fold_bn(sd, q + "bn1", b.mid), e2 = fold_bn(sd, q + "bn2", b.cout);
-          std::vector<uint16_t> fe((size_t)ers2_exp_elems(csi, b.mid), 0), fp((size_t)cso * b.mid, 0);
-          for (int s2 = 0; s2 < ks_n; ++s2)
-            for (int nt = 0; nt < b.mid / 16; ++nt)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int g8 = ln >> 4, n = nt * 16 + (ln & 15);
-                  const int t = csi == 16 ? 2 * s2 + (g8 >> 1) : s2, c = csi == 16 ? 8 * (g8 & 1) + e : 8 * g8 + e;
-                  const float v = t < 9 && c < cin ? we[((size_t)n * cin + c) * 9 + t] * e1.a[n] : 0.f;
-                  fe[(((size_t)s2 * (b.mid / 16) + nt) * 64 + ln) * 8 + e] = f2bf_host(v);
-                }
-          for (int on = 0; on < cso / 16; ++on)
-            for (int ks = 0; ks < b.mid / 32; ++ks)
-              for (int ln = 0; ln < 64; ++ln)
-                for (int e = 0; e < 8; ++e) {
-                  const int n = on * 16 + (ln & 15), g4 = 4 * (ln >> 4);
-                  const int c = 32 * ks + (e < 4 ? g4 + e : 16 + g4 + e - 4);
-                  const float v = n < b.cout ? wq[(size_t)n * b.mid + c] * e2.a[n] : 0.f;
-                  fp[(((size_t)on * (b.mid / 32) + ks) * 64 + ln) * 8 + e] = f2bf_host(v);
-                }
-          b.er_wexp = arena_.add_vec(fe);
-          b.er_wpwl = arena_.add_vec(fp);
-          b.er_frag = true;
-        }
-      } else {
-        b.mid = make_divisible(cin * (double)sdf.exp);
-        b.rd = (int)std::lround(b.mid * (sdf.se / sdf.exp));
-        const int m = b.mid, cs = chan_stride(m);
-        max_mid_cs_ = std::max(max_mid_cs_, cs);
-        conv1x1(b.c1, q + "conv_pw.weight", cin, m, fold_bn(sd, q + "bn1", m));
-        // the e4m3 expand (ir_pwdw / ir_pwdw_s2 x8; the stride-2 blocks' copy is used where ir_pwdw_s2 runs, blocks.5.0)
-        if (dtype == M2S_DT_FP8 && chan_stride(cin) <= 256) {
-          const float* wq = need(sd, q + "conv_pw.weight", {m, cin, 1, 1}).data;
-          const BN bn1 = fold_bn(sd, q + "bn1", m);
-          size_t boff = 0;
-          b.f8x_kp = round_up(chan_stride(cin), 128);
-          pack_gemm_f8(arena_, cin, m, round_up(cs, 32), b.f8x_kp, [&](int n, int c) { return wq[(size_t)n * cin + c] * bn1.a[n]; },
-                       [&](int n) { return bn1.b[n]; }, &b.f8x_w, &b.f8x_s, &boff);
-          b.f8_pw = true;
-        }
-        const float* wd = need(sd, q + "conv_dw.weight", {m, 1, k, k}).data;
-        BN bn2 = fold_bn(sd, q + "bn2", m);
-        std::vector<float> w9((size_t)cs * 9, 0.f), bd(cs, 0.f);
-        for (int c = 0; c < m; ++c) {
-          for (int t = 0; t < 9; ++t) w9[(size_t)t * cs + c] = wd[(size_t)c * 9 + t] * bn2.a[c];  // tap-major
-          bd[c] = bn2.b[c];
-        }
-        b.dw_w = arena_.add_vec(w9);
-        b.dw_b = arena_.add_vec(bd);
-        if (pdt == M2S_DT_BF16) {  // fused kernel: bf16 weight in the half matching the channel
-          std::vector<uint32_t> w2(w9.size());  // (v_dot2 against a (c, c+1) activation dword)
-          for (size_t i = 0; i < w9.size(); ++i) {
-            const uint32_t h = f2bf_host(w9[i]);
-            w2[i] = (i % cs) % 2 == 0 ? h : h << 16;
-          }
-          b.dw_w2 = arena_.add_vec(w2);
-        }
-        const float* w1 = need(sd, q + "se.conv_reduce.weight", {b.rd, m, 1, 1}).data;
-        const float* b1 = need(sd, q + "se.conv_reduce.bias", {b.rd}).data;
-        const float* w2 = need(sd, q + "se.conv_expand.weight", {m, b.rd, 1, 1}).data;
-        const float* b2 = need(sd, q + "se.conv_expand.bias", {m}).data;
-        // SE excitation as two GEMMs over all images: (N x mid) . W1^T -> SiLU -> . W2^T -> sigmoid
-        const int rd = b.rd;
-        // (fp8 engines keep the SE excitation in bf16: a gate error scales the whole block output)
-        const int se_dt = dtype == M2S_DT_FP8 ? M2S_DT_BF16 : dtype;
-        b.se1 = make_pconv(KIND_GEMM, m, rd, 1, se_dt);
-        b.se1.macs_per_row = (double)m * rd;
-        pack_conv(arena_, se_dt, b.se1, [&](int, int n, int, int c) { return w1[(size_t)n * m + c]; },
-                  [&](int n) { return b1[n]; });
-        b.se2 = make_pconv(KIND_GEMM, rd, m, 1, se_dt);
-        b.se2.macs_per_row = (double)m * rd;
-        pack_conv(arena_, se_dt, b.se2, [&](int, int n, int, int c) { return w2[(size_t)n * rd + c]; },
-                  [&](int n) { return b2[n]; });
-        conv1x1(b.c2, q + "conv_pwl.weight", m, b.cout, fold_bn(sd, q + "bn3", b.cout));
-        if (dtype == M2S_DT_FP8 && chan_stride(b.cout) <= 224) {  // (stride 2: used with ir_pwdw_s2's e4m3 output)
-          const float* wq = need(sd, q + "conv_pwl.weight", {b.cout, m, 1, 1}).data;
-          const BN bn3 = fold_bn(sd, q + "bn3", b.cout);
-          b.f8_kp = round_up(cs, 128);
-          b.f8_npad = std::max(round_up(chan_stride(b.cout), 64), chan_stride(b.cout) > 128 ? 224 : 128);
-          pack_gemm_f8(arena_, m, b.cout, b.f8_npad, b.f8_kp, [&](int n, int c) { return wq[(size_t)n * m + c] * bn3.a[n]; },
-                       [&](int n) { return bn3.b[n]; }, &b.f8_w, &b.f8_s, &b.f8_b);
-          b.f8_pwl = true;
-        }
-      }
-      blocks_.push_back(b);
-      cin = sdf.cout;
-    }
-  }
-  // BiLSTM: input projection of both directions as one fp32 GEMM (rows [fwd 4H | bwd 4H]).
-  const int H = hidden_;
-  const float* wih[2] = {need(sd, "rnn.lstm.weight_ih_l0", {4 * H, EFF_OUT}).data,
-                         need(sd, "rnn.lstm.weight_ih_l0_reverse", {4 * H, EFF_OUT}).data};
-  const float* bih[2] = {need(sd, "rnn.lstm.bias_ih_l0", {4 * H}).data, need(sd, "rnn.lstm.bias_ih_l0_reverse", {4 * H}).data};
-  const float* bhh[2] = {need(sd, "rnn.lstm.bias_hh_l0", {4 * H}).data, need(sd, "rnn.lstm.bias_hh_l0_reverse", {4 * H}).data};
-  const float* whh[2] = {need(sd, "rnn.lstm.weight_hh_l0", {4 * H, H}).data,
-                         need(sd, "rnn.lstm.weight_hh_l0_reverse", {4 * H, H}).data};
-  lstm_ih_ = make_pconv(KIND_GEMM, EFF_OUT, 8 * H, 1, M2S_DT_F32);
-  lstm_ih_.cs_in = EFF_OUT;  // 208 = 13 x 16: valid fp32 K chunking without padding
-  lstm_ih_.tpc = 1;
-  lstm_ih_.kp = EFF_OUT;
-  lstm_ih_.cs_out = 8 * H;
-  lstm_ih_.n_pad = round_up(8 * H, 64);
-  lstm_ih_.macs_per_row = 8.0 * H * EFF_OUT;
-  pack_conv(arena_, M2S_DT_F32, lstm_ih_,
-            [&](int, int n, int, int c) { return wih[n / (4 * H)][(size_t)(n % (4 * H)) * EFF_OUT + c]; },
-            [&](int n) { return bih[n / (4 * H)][n % (4 * H)] + bhh[n / (4 * H)][n % (4 * H)]; });
-  std::vector<float> wh((size_t)2 * 4 * H * H);
-  std::memcpy(wh.data(), whh[0], sizeof(float) * 4 * H * H);
-  std::memcpy(wh.data() + (size_t)4 * H * H, whh[1], sizeof(float) * 4 * H * H);
-  whh_ = arena_.add_vec(wh);
-  if (lstm_window_supported(H)) {  // the windowed path's copy: rows permuted so a workgroup's tile holds all four gates
-    pack_lstm_window_whh(whh, H, wh.data());
-    whh_win_ = arena_.add_vec(wh);
-  }
-  const float* hw = need(sd, "head.weight", {n_mels, H}).data;
-  const float* hb = need(sd, "head.bias", {n_mels}).data;
-  std::vector<float> wt((size_t)H * n_mels);
-  for (int n = 0; n < n_mels; ++n)
-    for (int k = 0; k < H; ++k) wt[(size_t)k * n_mels + n] = hw[(size_t)n * H + k];
-  head_wt_ = arena_.add_vec(wt);
-  head_b_ = arena_.add(hb, sizeof(float) * n_mels);
-
+  // (the last row: A/B and tests only)
+  for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
+           {"M2S_IR_FUSED", &ir_fused_},   {"M2S_IR_WS", &ir_ws_},         {"M2S_IR_WS_S2", &ir_ws_s2_},
+           {"M2S_IRWS_F32", &irws_f32_},   {"M2S_STEM_FUSED", &stem_fused_}, {"M2S_F8_EXPAND", &f8_expand_},
+           {"M2S_F8_S2", &f8_s2_},         {"M2S_F8_ER", &f8_er_},         {"M2S_ER8_X8", &er8_x8_},
+           {"M2S_F8_ER2", &f8_er2_},       {"M2S_SE_Y8", &se_y8_},         {"M2S_SE_FUSED", &se_fused_},
+           {"M2S_ER_FUSED", &er_fused_},   {"M2S_SE_WS", &se_ws_},         {"M2S_LSTM_PERSISTENT", &lstm_persistent_},
+           {"M2S_LSTM_MID", &lstm_mid_},   {"M2S_LSTM_X3", &lstm_x3_},     {"M2S_LSTM_X3G", &lstm_x3g_},
+           {"M2S_SE_SP", &se_sp_},         {"M2S_ER_MRG", &er_mrg_},       {"M2S_IR_S2BAND", &ir_s2band_}})
+    env_flag(name, *v);
+  env_int("M2S_IRWS_MIN", irws_min_);
+  env_int("M2S_SEWS_MIN", sews_min_cus_);
+  pack_acoustic(sd, n_mels, hidden, dtype, arena_, p_);
   arena_.upload(device);
-  M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&err_host_), sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
-  *err_host_ = 0;
-  M2S_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&err_dev_), err_host_, 0));
-  M2S_HIP(hipMalloc(&gsync_, std::max(lstm_small_sync_bytes(), lstm_x3g_sync_bytes())));
-  for (auto& b : blocks_) {
+  for (auto& b : p_.blocks) {
     b.c1.resolve(arena_);
     if (b.type != 0) b.c2.resolve(arena_);
     if (b.type == 2) {
@@ -504,7 +62,11 @@ Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int d
       b.se2.resolve(arena_);
     }
   }
-  lstm_ih_.resolve(arena_);
+  p_.lstm_ih.resolve(arena_);
+  M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&err_host_), sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
+  *err_host_ = 0;
+  M2S_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&err_dev_), err_host_, 0));
+  M2S_HIP(hipMalloc(&gsync_, std::max(lstm_small_sync_bytes(), lstm_x3g_sync_bytes())));
 }
 
 Acoustic::~Acoustic() {
@@ -515,24 +77,17 @@ Acoustic::~Acoustic() {
 unsigned Acoustic::take_async_error() { return __atomic_exchange_n(err_host_, 0u, __ATOMIC_ACQ_REL); }
 
 void Acoustic::effnet_dims(int H, int W, size_t* io, size_t* mid, size_t* se) const {
-  int oh, ow, ph, pw;
-  same_pad(H, 3, 2, &oh, &ph);
-  same_pad(W, 3, 2, &ow, &pw);
-  size_t mio = (size_t)oh * ow * chan_stride(EFF_STEM), mmid = 0, mse = 0;
-  for (const Block& b : blocks_) {
-    int nh, nw;
-    same_pad(oh, 3, b.stride, &nh, &ph);
-    same_pad(ow, 3, b.stride, &nw, &pw);
-    if (b.type == 1) mmid = std::max(mmid, (size_t)nh * nw * chan_stride(b.mid));
-    if (b.type == 2) {
-      mmid = std::max(mmid, (size_t)oh * ow * chan_stride(b.mid));
-      mse = std::max(mse, (size_t)dw_pixel_blocks(nh, nw) * chan_stride(b.mid));
-      if (b.stride == 2 && nh % 4 == 0) mse = std::max(mse, (size_t)ir_s2band_bands(nh) * chan_stride(b.mid));
+  size_t mio = 0, mmid = 0, mse = 0;
+  for_each_backbone_map(H, W, [&](const BlockDef& d, const BlockMap& m) {
+    if (d.type == 1) mmid = std::max(mmid, (size_t)m.oh * m.ow * chan_stride(d.mid));
+    if (d.type == 2) {
+      mmid = std::max(mmid, (size_t)m.ih * m.iw * chan_stride(d.mid));
+      mse = std::max(mse, (size_t)dw_pixel_blocks(m.oh, m.ow) * chan_stride(d.mid));
+      if (d.stride == 2 && m.oh % 4 == 0) mse = std::max(mse, (size_t)ir_s2band_bands(m.oh) * chan_stride(d.mid));
     }
-    mio = std::max(mio, (size_t)nh * nw * chan_stride(b.cout));
-    oh = nh;
-    ow = nw;
-  }
+    // every map a block reads or writes (block 0 reads the stem's output)
+    mio = std::max({mio, (size_t)m.ih * m.iw * chan_stride(d.cin), (size_t)m.oh * m.ow * chan_stride(d.cout)});
+  });
   *io = mio;
   *mid = mmid;
   *se = mse;
@@ -540,20 +95,13 @@ void Acoustic::effnet_dims(int H, int W, size_t* io, size_t* mid, size_t* se) co
 
 size_t Acoustic::effnet_x8(int H, int W) const {
   if (dtype_ != M2S_DT_FP8 || (!f8_expand_ && !f8_er_)) return 0;
-  int oh, ow, ph, pw;
-  same_pad(H, 3, 2, &oh, &ph);
-  same_pad(W, 3, 2, &ow, &pw);
   size_t mx = 0;
-  for (const Block& b : blocks_) {
-    int nh, nw;
-    same_pad(oh, 3, b.stride, &nh, &ph);
-    same_pad(ow, 3, b.stride, &nw, &pw);
-    if (b.f8_pw && f8_expand_) mx = std::max(mx, (size_t)oh * ow * b.f8x_kp);  // the block input's map
-    if (b.er8 && f8_er_) mx = std::max(mx, (size_t)nh * nw * 32);              // er8_fused x8 / y8 (N, H, W, 32)
-    if (b.er8w && f8_er_) mx = std::max(mx, (size_t)nh * nw * 64);             // er8w_fused x8 / y8 (N, H, W, 64)
-    oh = nh;
-    ow = nw;
-  }
+  for_each_backbone_map(H, W, [&](const BlockDef& d, const BlockMap& m) {
+    const Block& b = p_.blocks[d.index];
+    if (b.f8_pw && f8_expand_) mx = std::max(mx, (size_t)m.ih * m.iw * b.f8x_kp);  // the block input's map
+    if (b.er8 && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 32);              // er8_fused x8 / y8 (N, H, W, 32)
+    if (b.er8w && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 64);             // er8w_fused x8 / y8 (N, H, W, 64)
+  });
   return round_up((int)mx, 256);
 }
 
@@ -578,9 +126,9 @@ Acoustic::EffBufs<T> Acoustic::effnet_bufs(Workspace& ws, int N, int H, int W) c
   b.M = ws.take<T>(nc * mid * R);
   b.M2 = ws.take<T>(nc * mid * R);
   b.sums = ws.take<float>(nc * se);
-  b.se_mean = ws.take<T>(nc * max_mid_cs_ * R);
+  b.se_mean = ws.take<T>(nc * p_.max_mid_cs * R);
   b.se_hid = ws.take<T>(nc * SE_RD_MAX * R);
-  b.scale = ws.take<T>(nc * max_mid_cs_ * R);
+  b.scale = ws.take<T>(nc * p_.max_mid_cs * R);
   if (const size_t x8b = effnet_x8(H, W))
     for (uint8_t*& x : b.X8) x = ws.take<uint8_t>(nc * x8b);
   return b;
@@ -625,7 +173,7 @@ static ConvArgs conv2d_args(const Pass& p, const PConv& pc, const void* x, void*
 
 template <typename T>
 void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
-  const Block& b = blocks_[k];
+  const Block& b = p_.blocks[k];
   ConvArgs a = conv2d_args(p, b.c1, p.cur, p.nxt);
   a.act = ACT_SILU;
   a.res = b.skip ? p.cur : nullptr;
@@ -634,7 +182,7 @@ void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
 
 template <typename T>
 void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
-  const Block& b = blocks_[k];
+  const Block& b = p_.blocks[k];
   const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
   T *const cur = p.cur, *const nxt = p.nxt, *const M = p.b.M;
   uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
@@ -643,8 +191,8 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
   // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
   // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
   // er8_fused to its in-kernel conversion)
-  uint8_t* const er8_next = X8[0] && f8_er_ && k + 1 < blocks_.size() &&
-                                    ((er8_x8_ && blocks_[k + 1].er8) || (f8_er2_ && blocks_[k + 1].er8w))
+  uint8_t* const er8_next = X8[0] && f8_er_ && k + 1 < p_.blocks.size() &&
+                                    ((er8_x8_ && p_.blocks[k + 1].er8) || (f8_er2_ && p_.blocks[k + 1].er8w))
                                 ? (cur8 == X8[0] ? X8[1] : X8[0])
                                 : nullptr;
   if (std::is_same<T, sp_t>::value && er_fused_ && b.er_sp &&
@@ -673,7 +221,7 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
                     2.0 * px * b.mid * (9.0 * b.cin + b.cout), 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
   } else if (std::is_same<T, bf16_t>::value && er_fused_ && f8_er_ && f8_er2_ && b.er8w && cur8 &&
              er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
-    uint8_t* y8 = er8_next && blocks_[k + 1].er8w ? er8_next : nullptr;
+    uint8_t* y8 = er8_next && p_.blocks[k + 1].er8w ? er8_next : nullptr;
     launch_er8w_fused(reinterpret_cast<const bf16_t*>(cur), cur8, nc, nh, nw, static_cast<const uint8_t*>(arena_.ptr(b.er8w_w)),
                       static_cast<const float*>(arena_.ptr(b.er8w_sexp)), b.c1.b,
                       static_cast<const float*>(arena_.ptr(b.er8w_spwl)), b.c2.b, reinterpret_cast<bf16_t*>(nxt), y8,
@@ -689,8 +237,8 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
   } else if (std::is_same<T, bf16_t>::value && er_fused_ && b.er_frag && b.stride == 2 &&
              ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, chan_stride(b.cout), b.c1.kp, b.c2.kp)) {
     // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
-    uint8_t* y8 = er8_next && ((chan_stride(b.cout) == 32 && blocks_[k + 1].er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
-                               (chan_stride(b.cout) == 64 && blocks_[k + 1].er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
+    uint8_t* y8 = er8_next && ((chan_stride(b.cout) == 32 && p_.blocks[k + 1].er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
+                               (chan_stride(b.cout) == 64 && p_.blocks[k + 1].er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
                       ? er8_next
                       : nullptr;
     launch_ers2_fused(reinterpret_cast<const bf16_t*>(cur), nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid,
@@ -715,7 +263,7 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
 
 template <typename T>
 void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
-  const Block& b = blocks_[k];
+  const Block& b = p_.blocks[k];
   const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
   T *const cur = p.cur, *const M = p.b.M, *const M2 = p.b.M2, *const se_mean = p.b.se_mean;
   float* const sums = p.b.sums;
@@ -814,7 +362,7 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
 
 template <typename T>
 void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
-  const Block& b = blocks_[k];
+  const Block& b = p_.blocks[k];
   const int nc = p.nc, cs = chan_stride(b.mid);
   T *const se_mean = p.b.se_mean, *const se_hid = p.b.se_hid, *const scale = p.b.scale;
   hipStream_t s = p.s;
@@ -841,7 +389,7 @@ void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
 
 template <typename T>
 void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
-  const Block& b = blocks_[k];
+  const Block& b = p_.blocks[k];
   const int nc = p.nc, nh = p.nh, nw = p.nw, cs = chan_stride(b.mid);
   T *const cur = p.cur, *const nxt = p.nxt, *const M2 = p.b.M2, *const scale = p.b.scale;
   uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
@@ -850,11 +398,11 @@ void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
   const bool f8 = p.f8, sews = p.sews, mid_f32 = p.mid_f32;
   // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
   // ir_pwdw_s2, whose input map is this block's nh x nw output)
-  const bool want8 = X8[0] && f8_expand_ && k + 1 < blocks_.size() && blocks_[k + 1].f8_pw &&
-                     (blocks_[k + 1].stride == 1 ||
-                      (f8_s2_ && ir_fused_s2_supported(nh, nw, blocks_[k + 1].c1.cs_in, chan_stride(blocks_[k + 1].mid), false)));
+  const bool want8 = X8[0] && f8_expand_ && k + 1 < p_.blocks.size() && p_.blocks[k + 1].f8_pw &&
+                     (p_.blocks[k + 1].stride == 1 ||
+                      (f8_s2_ && ir_fused_s2_supported(nh, nw, p_.blocks[k + 1].c1.cs_in, chan_stride(p_.blocks[k + 1].mid), false)));
   // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
-  const int ld8 = want8 ? blocks_[k + 1].f8x_kp : 0;
+  const int ld8 = want8 ? p_.blocks[k + 1].f8x_kp : 0;
   if (f8 && want8 && se_y8_) next8 = cur8 == X8[0] ? X8[1] : X8[0];
   if (f8 && se_ws_ && se_ws_f8_supported(nh * nw, cs, chan_stride(b.cout))) {
     const double rows = (double)nc * nh * nw;
@@ -918,10 +466,10 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
     constexpr bool SPL = std::is_same<T, sp_t>::value;
     const bool front = ((std::is_same<T, bf16_t>::value && (dtype_ == M2S_DT_BF16 || dtype_ == M2S_DT_FP8)) || SPL) && stem_fused_ && !(probe && stop_after >= 0 && stop_after < 2) &&
-                       blocks_.size() >= 2 && blocks_[0].type == 0 && blocks_[0].stride == 1 && !blocks_[0].skip &&
-                       blocks_[0].cout == 16 && blocks_[0].c1.cs_in == 32 && blocks_[0].c1.kp == 288 &&
-                       blocks_[1].type == 0 && blocks_[1].stride == 1 && blocks_[1].skip && blocks_[1].cout == 16 &&
-                       blocks_[1].c1.cs_in == 16 && blocks_[1].c1.kp == 160 && chan_stride(16) == 16;
+                       p_.blocks.size() >= 2 && p_.blocks[0].type == 0 && p_.blocks[0].stride == 1 && !p_.blocks[0].skip &&
+                       p_.blocks[0].cout == 16 && p_.blocks[0].c1.cs_in == 32 && p_.blocks[0].c1.kp == 288 &&
+                       p_.blocks[1].type == 0 && p_.blocks[1].stride == 1 && p_.blocks[1].skip && p_.blocks[1].cout == 16 &&
+                       p_.blocks[1].c1.cs_in == 16 && p_.blocks[1].c1.kp == 160 && chan_stride(16) == 16;
     cur = A;
     p.nxt = p.b.B;
     p.cur8 = nullptr;
@@ -929,16 +477,16 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     int bi = 0;
     if (front) {
       const double px = (double)nc * oh * ow;
-      launch_stem_b0(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, static_cast<const float*>(arena_.ptr(stem_w_)),
-                     static_cast<const float*>(arena_.ptr(stem_b_)), blocks_[0].c1.w, blocks_[0].c1.b, blocks_[0].c1.kp,
-                     blocks_[1].c1.w, blocks_[1].c1.b, blocks_[1].c1.kp, A, SPL,
+      launch_stem_b0(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, static_cast<const float*>(arena_.ptr(p_.stem_w)),
+                     static_cast<const float*>(arena_.ptr(p_.stem_b)), p_.blocks[0].c1.w, p_.blocks[0].c1.b, p_.blocks[0].c1.kp,
+                     p_.blocks[1].c1.w, p_.blocks[1].c1.b, p_.blocks[1].c1.kp, A, SPL,
                      2.0 * px * (EFF_STEM * 9 + 16 * 9 * 32 + 16 * 9 * 16), 4.0 * nc * H * W + (SPL ? 4.0 : 2.0) * px * 16, s);
       cc = 16;
       bi = 2;
     } else {
       ProfScope ps(std::is_same<T, bf16_t>::value ? std::string("stem32_kernel") : tname<T>("stem_kernel"), 2.0 * nc * oh * ow * EFF_STEM * 27, 4.0 * nc * H * W + (sizeof(T) * Elem<T>::R) * (double)nc * oh * ow * 32, s);
-      launch_stem<T>(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, static_cast<const float*>(arena_.ptr(stem_w_)),
-                     static_cast<const float*>(arena_.ptr(stem_b_)), EFF_STEM, chan_stride(EFF_STEM), A, s);
+      launch_stem<T>(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, static_cast<const float*>(arena_.ptr(p_.stem_w)),
+                     static_cast<const float*>(arena_.ptr(p_.stem_b)), EFF_STEM, chan_stride(EFF_STEM), A, s);
     }
     auto tap = [&](int done) {
       if (stop_after == done && probe) {
@@ -954,8 +502,8 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     };
     if (tap(bi)) continue;  // bi = 0, or 2 after the fused front
     bool stopped = false;
-    for (size_t k = front ? 2 : 0; k < blocks_.size(); ++k) {
-      const Block& b = blocks_[k];
+    for (size_t k = front ? 2 : 0; k < p_.blocks.size(); ++k) {
+      const Block& b = p_.blocks[k];
       p.next8 = nullptr;  // the e4m3 copy of this block's output, if the block wrote one
       same_pad(oh, 3, b.stride, &p.nh, &p.qt);
       same_pad(ow, 3, b.stride, &p.nw, &p.ql);
@@ -993,7 +541,7 @@ size_t Acoustic::lstm_sync_bytes() {
 void Acoustic::lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps,
                                double rows, hipStream_t s) {
   const int H = hidden_;
-  const float* whh = static_cast<const float*>(arena_.ptr(whh_));
+  const float* whh = static_cast<const float*>(arena_.ptr(p_.whh));
   // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
   const double bytes = 4.0 * 2 * 4 * H * H + 4.0 * rows * (8.0 * H + 2.0 * H);
   const double f2 = 2.0 * 2 * 4.0 * H * H * seq_steps, f3 = 3.0 * 2 * 4.0 * H * H * seq_steps;
@@ -1040,7 +588,7 @@ void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_nor
   const LstmBufs b = lstm_bufs(ws, B, T);
   float* const hs = b.hs;
   StageTag tag("bilstm");
-  ConvArgs a = conv_args(lstm_ih_);
+  ConvArgs a = conv_args(p_.lstm_ih);
   a.x = feats;
   a.y = b.pre;
   a.M = (int)BT;
@@ -1049,13 +597,13 @@ void Acoustic::bilstm(const float* feats, int B, int T, float* y, float* mel_nor
   // 0.13 ms slower).  The K summation order therefore differs between the two size classes (fp32 rounding only).
   // (keyed on the projection's row count M: a ragged call of N packed rows switches where a dense one of N does)
   a.kwave = BT <= 64 ? 1 : 0;
-  run_conv<float>(a, lstm_ih_, s);
+  run_conv<float>(a, p_.lstm_ih, s);
   lstm_recurrence(b.pre, hs, b.cst, b.sync, B, T, (double)B * (T - 1), (double)BT, s);
   if (mel_norm) {
     StageTag head("head");
     ProfScope ps("mel_head_kernel", 2.0 * BT * H * n_mels_, 4.0 * BT * (2 * H + n_mels_), s);
-    launch_mel_head(hs, (int)BT, H, static_cast<const float*>(arena_.ptr(head_wt_)),
-                    static_cast<const float*>(arena_.ptr(head_b_)), n_mels_, mel_norm, s);
+    launch_mel_head(hs, (int)BT, H, static_cast<const float*>(arena_.ptr(p_.head_wt)),
+                    static_cast<const float*>(arena_.ptr(p_.head_b)), n_mels_, mel_norm, s);
   }
   if (y) launch_add2(hs, hs + BT * H, y, (long)(BT * H), s);
 }
@@ -1155,12 +703,12 @@ void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long
   float *const pre_packed = rb.pre_packed, *const pre = rb.d.pre, *const hs = rb.d.hs;
   rtab_.upload(lengths, B, tab, s);
   StageTag tag("bilstm");
-  ConvArgs a = conv_args(lstm_ih_);
+  ConvArgs a = conv_args(p_.lstm_ih);
   a.x = feats;
   a.y = pre_packed;
   a.M = (int)N;
   a.kwave = N <= 64 ? 1 : 0;  // as bilstm: by the projection's row count
-  run_conv<float>(a, lstm_ih_, s);
+  run_conv<float>(a, p_.lstm_ih, s);
   {
     ProfScope ps("ragged_pre_scatter_kernel", 0.0, 2.0 * 4.0 * N * 8.0 * H, s);
     launch_ragged_pre_scatter(pre_packed, tab, B, T, 8 * H, pre, s);
@@ -1171,8 +719,8 @@ void Acoustic::bilstm_ragged(const float* feats, const int* lengths, int B, long
   StageTag head("head");
   ProfScope ps("ragged_head_gather_kernel", mel_norm ? 2.0 * N * H * n_mels_ : 0.0,
                4.0 * N * (2 * H + (mel_norm ? n_mels_ : 0) + (y ? H : 0)), s);
-  launch_ragged_head_gather(hs, tab, B, T, H, static_cast<const float*>(arena_.ptr(head_wt_)),
-                            static_cast<const float*>(arena_.ptr(head_b_)), n_mels_, y, mel_norm, s);
+  launch_ragged_head_gather(hs, tab, B, T, H, static_cast<const float*>(arena_.ptr(p_.head_wt)),
+                            static_cast<const float*>(arena_.ptr(p_.head_b)), n_mels_, y, mel_norm, s);
 }
 
 void Acoustic::forward_ragged(const float* frames, const int* lengths, int B, long N, int H, int W, float* mel_norm,
@@ -1264,12 +812,12 @@ void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int
   StageTag tag("bilstm");
   // the projection, once per FRAME row; one K order for every row count (kwave stays 0: a row's bits must not
   // depend on how many rows the call holds, or a stream's chunking would show)
-  ConvArgs a = conv_args(lstm_ih_);
+  ConvArgs a = conv_args(p_.lstm_ih);
   a.x = feats;
   a.y = b.pre;
   a.M = (int)N;
   a.kwave = 0;
-  run_conv<float>(a, lstm_ih_, s);
+  run_conv<float>(a, p_.lstm_ih, s);
   {
     ProfScope ps("lstm_window_table_kernel", 0.0, 4.0 * (5.0 * B + 2.0 * S), s);
     launch_lstm_window_table(b.tab, B, W, p.mean, p.max_windows, b.win, s);
@@ -1282,7 +830,7 @@ void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int
     launch_lstm_window_step0(b.pre, b.win, S, !p.mean, split, b.hop[0], b.c, p.mean ? b.hf : (W == 1 ? b.hm : nullptr),
                              p.mean ? b.hf + (size_t)W * plane : b.hm + (size_t)p.R * H, s);
   }
-  const float* wperm = static_cast<const float*>(arena_.ptr(whh_win_));
+  const float* wperm = static_cast<const float*>(arena_.ptr(p_.whh_win));
   for (int j = 1; j < W; ++j) {
     const void* hin = b.hop[(j - 1) & 1];
     void* hout = j + 1 < W ? b.hop[j & 1] : nullptr;
@@ -1302,8 +850,8 @@ void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int
   if (mel_norm) {
     StageTag head("head");
     ProfScope ps("mel_head_kernel", 2.0 * p.R * H * n_mels_, 4.0 * p.R * (2 * H + n_mels_), s);
-    launch_mel_head(b.hm, (int)p.R, H, static_cast<const float*>(arena_.ptr(head_wt_)),
-                    static_cast<const float*>(arena_.ptr(head_b_)), n_mels_, mel_norm, s);
+    launch_mel_head(b.hm, (int)p.R, H, static_cast<const float*>(arena_.ptr(p_.head_wt)),
+                    static_cast<const float*>(arena_.ptr(p_.head_b)), n_mels_, mel_norm, s);
   }
   if (y) launch_add2(b.hm, b.hm + (size_t)p.R * H, y, (long)((size_t)p.R * H), s);
 }
@@ -1320,197 +868,17 @@ void Acoustic::forward_windowed(const float* frames, const int* lengths, const i
 
 // ------------------------------------------------------------------------------------------
 // Vocoder
-static std::vector<float> fold_wn(const StateDict& sd, const std::string& p, std::vector<int64_t> shape) {
-  auto it = sd.find(p + ".weight");
-  if (it != sd.end()) {
-    const HostTensor& t = need(sd, p + ".weight", shape);
-    return std::vector<float>(t.data, t.data + t.numel());
-  }
-  std::vector<int64_t> gs(shape.size(), 1);
-  gs[0] = shape[0];
-  const HostTensor& g = need(sd, p + ".weight_g", gs);
-  const HostTensor& v = need(sd, p + ".weight_v", shape);
-  const size_t inner = v.numel() / shape[0];
-  std::vector<float> w(v.numel());
-  for (int64_t i = 0; i < shape[0]; ++i) {
-    double acc = 0.0;
-    for (size_t j = 0; j < inner; ++j) acc += (double)v.data[i * inner + j] * v.data[i * inner + j];
-    const float sc = g.data[i] / (float)std::sqrt(acc);
-    for (size_t j = 0; j < inner; ++j) w[i * inner + j] = v.data[i * inner + j] * sc;
-  }
-  return w;
-}
-
 Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int device)
     : h_(h), dtype_(dtype), device_(device) {
-  M2S_CHECK(dtype == M2S_DT_F32 || dtype == M2S_DT_BF16 || dtype == M2S_DT_BF16X3 || dtype == M2S_DT_FP8, "bad dtype");
-  M2S_CHECK(h.resblock == 1 || h.resblock == 2, "resblock must be 1 or 2");
-  // fp8 engines: e4m3 resblock (MRF) convs at C = 64 / 128 / 256; conv_pre, the upsamplers and the fused
-  // C = 32 ResBlock1 kernel stay bf16
-  const int io_dt = dtype == M2S_DT_FP8 ? M2S_DT_BF16 : dtype;
-  if (const char* e = std::getenv("M2S_MRF_FUSED")) mrf_fused_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_MRF_BATCH")) mrf_batch_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_MRF_HALO")) mrf_halo_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_MRF64")) f8_mrf64_ = std::strcmp(e, "0") != 0;
-  if (const char* e = std::getenv("M2S_F8_MRF32")) f8_mrf32_ = std::strcmp(e, "0") != 0;
-  M2S_CHECK(h.n_up >= 1 && h.n_up <= 8 && h.n_kernels >= 1 && h.n_kernels <= 8, "bad generator config");
-  const int c0 = h.upsample_initial_channel;
-  {  // conv_pre: Conv1d(num_mels, c0, 7), no weight norm (models.py:94)
-    const HostTensor& w = need(sd, "conv_pre.weight", {c0, h.num_mels, 7});
-    const HostTensor& b = need(sd, "conv_pre.bias", {c0});
-    pre_ = make_pconv(KIND_CONV1D, h.num_mels, c0, 7, io_dt);
-    pre_.ks = 7;
-    pre_.pad_left = 0;  // F.pad(x, (0, 6)): look-ahead of 6 frames, zeros past the end
-    pre_.macs_per_row = (double)c0 * h.num_mels * 7;
-    const int ci = h.num_mels;
-    pack_conv(arena_, io_dt, pre_, [&](int, int n, int t, int c) { return w.data[((size_t)n * ci + c) * 7 + t]; },
-              [&](int n) { return b.data[n]; });
-  }
-  hop_ = 1;
-  for (int i = 0; i < h.n_up; ++i) {
-    const int u = h.upsample_rates[i], k = h.upsample_kernel_sizes[i];
-    const int ci = c0 >> i, co = c0 >> (i + 1);
-    M2S_CHECK(co >= 4, "generator too narrow");
-    // ConvTranspose1d(k, u, padding (k-u)/2) (models.py:98-101) gives L*u outputs only when k - u is
-    // even and non-negative; the polyphase packing and conv_post's look-ahead assume exactly L*u
-    M2S_CHECK(u >= 1 && k >= u && (k - u) % 2 == 0,
-              "upsample kernel " + std::to_string(k) + " / rate " + std::to_string(u) +
-                  ": k - u must be even and >= 0 (output length L*u)");
-    hop_ *= u;
-    const std::string p = "ups." + std::to_string(i);
-    std::vector<float> w = fold_wn(sd, p, {ci, co, k});  // ConvTranspose1d weight (in, out, k)
-    const HostTensor& b = need(sd, p + ".bias", {co});
-    PConv pc = make_pconv(KIND_CONVT, ci, co, (k + u - 1) / u, io_dt);
-    pc.phases = u;
-    pc.ct_u = u;
-    pc.ct_pad = (k - u) / 2;
-    pc.ct_k = k;
-    pc.macs_per_row = (double)ci * co * k / u;  // per output position, averaged over phases
-    const int pad = pc.ct_pad;
-    pack_conv(arena_, io_dt, pc,
-              [&](int ph, int n, int t, int c) {
-                const int j = (ph + pad) % u + t * u;  // tap t of phase ph uses kernel index j
-                return j < k ? w[((size_t)c * co + n) * k + j] : 0.f;
-              },
-              [&](int n) { return b.data[n]; });
-    ups_.push_back(pc);
-    for (int j = 0; j < h.n_kernels; ++j) {
-      RB rb;
-      rb.k = h.resblock_kernel_sizes[j];
-      const int kk = rb.k;
-      M2S_CHECK(h.n_dilations[j] >= 1 && h.n_dilations[j] <= 8, "resblock dilations: 1..8 per kernel size");
-      for (int d = 0; d < h.n_dilations[j]; ++d) rb.dil.push_back(h.resblock_dilation_sizes[j][d]);
-      const std::string q = "resblocks." + std::to_string(i * h.n_kernels + j);
-      auto mk = [&](const std::string& name, int dil) {
-        std::vector<float> wv = fold_wn(sd, name, {co, co, kk});
-        const HostTensor& bv = need(sd, name + ".bias", {co});
-        PConv c = make_pconv(KIND_CONV1D, co, co, kk, dtype);
-        c.ks = kk;
-        c.dil = dil;
-        c.pad_left = (kk - 1) * dil;  // get_padding(k, d) = k*d - d, then truncation: causal (utils.py:33-34)
-        c.macs_per_row = (double)co * co * kk;
-        pack_conv(arena_, dtype, c, [&](int, int n, int t, int cc) { return wv[((size_t)n * co + cc) * kk + t]; },
-                  [&](int n) { return bv.data[n]; });
-        return c;
-      };
-      const bool fsplit = dtype == M2S_DT_BF16X3;
-      // (fp8 engines: the fused bf16 ResBlock1 at C = 32 / 64, e4m3 convs at the wider stages)
-      const bool frag = (dtype == M2S_DT_BF16 || dtype == M2S_DT_FP8 || fsplit) && h.resblock == 1 &&
-                        rb1_fused_supported(co, chan_stride(co), kk, rb.dil.data(), (int)rb.dil.size(), kk * co, fsplit);
-      auto mk_frag = [&](const std::string& name) {  // fragment order of mrf_fused.hip
-        std::vector<float> wv = fold_wn(sd, name, {co, co, kk});
-        const int taps = rb1_frag_taps(co, kk, fsplit), nt16 = co / 16, k32 = co / 32, hr = fsplit ? 2 : 1;
-        std::vector<uint16_t> f((size_t)taps * hr * nt16 * k32 * 64 * 8);
-        size_t o = 0;
-        for (int t = 0; t < taps; ++t)
-          for (int half = 0; half < hr; ++half)
-            for (int nt = 0; nt < nt16; ++nt)
-              for (int kc = 0; kc < k32; ++kc)
-                for (int ln = 0; ln < 64; ++ln)
-                  for (int e = 0; e < 8; ++e) {
-                    const int n = nt * 16 + (ln & 15), c = kc * 32 + 8 * (ln >> 4) + e;
-                    const float w = t < kk ? wv[((size_t)n * co + c) * kk + t] : 0.f;
-                    if (fsplit) {
-                      uint16_t hi, lo;
-                      split_host(w, &hi, &lo);
-                      f[o++] = half ? lo : hi;
-                    } else {
-                      f[o++] = f2bf_host(w);
-                    }
-                  }
-        return arena_.add_vec(f);
-      };
-      // fp8: the C = 128 / 256 (and, f8_mrf64_, C = 64) resblock convs as e4m3 bytes for conv1d_f8 (K = 128
-      // block-scaled MFMA; C = 64: two taps a K step)
-      const bool q8 = dtype == M2S_DT_FP8 && h.resblock == 1 &&
-                      ((co >= 128 && !frag) || (co == 64 && f8_mrf64_) || (co == 32 && f8_mrf32_)) &&
-                      conv1d_f8_supported(co, kk);
-      auto mk_q8 = [&](const std::string& name) {
-        std::vector<float> wv = fold_wn(sd, name, {co, co, kk});
-        const HostTensor& bv = need(sd, name + ".bias", {co});
-        RB::F8 f;
-        pack_gemm_f8(
-            arena_, kk * co, co, co, round_up(kk * co, 128),
-            [&](int n, int kx) { return wv[((size_t)n * co + kx % co) * kk + kx / co]; },  // K = tap-major t C + c
-            [&](int n) { return bv.data[n]; }, &f.w, &f.s, &f.b);
-        return f;
-      };
-      bool halo = fsplit && h.resblock == 1 && !frag;
-      for (size_t d = 0; d < rb.dil.size(); ++d) halo = halo && conv1d_halo_sp_supported(co, chan_stride(co), kk, rb.dil[d]);
-      auto mk_halo = [&](const std::string& name) {  // fragment order of conv1d_halo.hip
-        std::vector<float> wv = fold_wn(sd, name, {co, co, kk});
-        std::vector<uint16_t> f(conv1d_halo_frag_elems(co, kk));
-        size_t o = 0;
-        for (int t = 0; t < kk; ++t)
-          for (int kc = 0; kc < co / 32; ++kc)
-            for (int half = 0; half < 2; ++half)
-              for (int nt = 0; nt < co / 16; ++nt)
-                for (int ln = 0; ln < 64; ++ln)
-                  for (int e = 0; e < 8; ++e) {
-                    const int n = nt * 16 + (ln & 15), c = kc * 32 + 8 * (ln >> 4) + e;
-                    uint16_t hi, lo;
-                    split_host(wv[((size_t)n * co + c) * kk + t], &hi, &lo);
-                    f[o++] = half ? lo : hi;
-                  }
-        return arena_.add_vec(f);
-      };
-      for (size_t d = 0; d < rb.dil.size(); ++d) {
-        if (h.resblock == 1) {
-          rb.c1.push_back(mk(q + ".convs1." + std::to_string(d), rb.dil[d]));
-          rb.c2.push_back(mk(q + ".convs2." + std::to_string(d), 1));
-          if (frag) {
-            rb.f1_off.push_back(mk_frag(q + ".convs1." + std::to_string(d)));
-            rb.f2_off.push_back(mk_frag(q + ".convs2." + std::to_string(d)));
-          }
-          if (halo) {
-            rb.h1_off.push_back(mk_halo(q + ".convs1." + std::to_string(d)));
-            rb.h2_off.push_back(mk_halo(q + ".convs2." + std::to_string(d)));
-          }
-          if (q8) {
-            rb.q1.push_back(mk_q8(q + ".convs1." + std::to_string(d)));
-            rb.q2.push_back(mk_q8(q + ".convs2." + std::to_string(d)));
-          }
-        } else {
-          rb.c1.push_back(mk(q + ".convs." + std::to_string(d), rb.dil[d]));
-        }
-      }
-      rbs_.push_back(rb);
-    }
-  }
-  post_c_ = c0 >> h.n_up;
-  {
-    std::vector<float> w = fold_wn(sd, "conv_post", {1, post_c_, 7});
-    const HostTensor& b = need(sd, "conv_post.bias", {1});
-    std::vector<float> wt((size_t)7 * post_c_);
-    for (int c = 0; c < post_c_; ++c)
-      for (int t = 0; t < 7; ++t) wt[(size_t)t * post_c_ + c] = w[(size_t)c * 7 + t];
-    post_w_ = arena_.add_vec(wt);
-    post_b_ = b.data[0];
-  }
+  for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
+           {"M2S_MRF_FUSED", &mrf_fused_}, {"M2S_MRF_BATCH", &mrf_batch_}, {"M2S_MRF_HALO", &mrf_halo_},
+           {"M2S_F8_MRF64", &f8_mrf64_},   {"M2S_F8_MRF32", &f8_mrf32_}})
+    env_flag(name, *v);
+  pack_vocoder(sd, h, dtype, f8_mrf64_, f8_mrf32_, arena_, p_);
   arena_.upload(device);
-  pre_.resolve(arena_);
-  for (auto& u : ups_) u.resolve(arena_);
-  for (auto& rb : rbs_) {
+  p_.pre.resolve(arena_);
+  for (auto& u : p_.ups) u.resolve(arena_);
+  for (auto& rb : p_.rbs) {
     for (auto& c : rb.c1) c.resolve(arena_);
     for (auto& c : rb.c2) c.resolve(arena_);
     for (size_t o : rb.f1_off) rb.f1.push_back(static_cast<const bf16_t*>(arena_.ptr(o)));
@@ -1524,30 +892,6 @@ Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int dev
         f.bp = static_cast<const float*>(arena_.ptr(f.b));
       }
   }
-  // Reach (m2s.config.generator_reach is the same rule): the interval of input positions that output frame 0, the
-  // samples 0 .. hop - 1, depends on, carried from the waveform back to the mel.  conv_post and conv_pre read 6
-  // positions ahead; a causal MRF stage reads sum((k - 1) d [+ (k - 1) for ResBlock1's second conv]) positions
-  // back, the largest over its kernel sizes; a transposed conv of rate u, kernel k, padding p reads inputs
-  // ceil((n + p - k + 1) / u) .. floor((n + p) / u) for output n.  Level l is the input of upsampler l.
-  auto fdiv = [](long a, long b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
-  long lo = 0, hi = hop_ - 1 + 6, scale = hop_;
-  for (int i = h.n_up - 1; i >= 0; --i) {
-    long mrf = 0;
-    for (int j = 0; j < h.n_kernels; ++j) {
-      long r = 0;
-      for (int d = 0; d < h.n_dilations[j]; ++d)
-        r += (long)(h.resblock_kernel_sizes[j] - 1) * (h.resblock_dilation_sizes[j][d] + (h.resblock == 1 ? 1 : 0));
-      mrf = std::max(mrf, r);
-    }
-    const long u = h.upsample_rates[i], k = h.upsample_kernel_sizes[i], p = (k - u) / 2;
-    lo = -fdiv(-(lo - mrf + p - k + 1), u);
-    hi = fdiv(hi + p, u);
-    scale /= u;
-    lvl_back_[i] = (int)-fdiv(lo, scale);
-    lvl_ahead_[i] = (int)fdiv(hi, scale);
-  }
-  back_ = (int)-lo;
-  ahead_ = (int)hi + 6;
 }
 
 size_t Vocoder::act_elems(int B, int T) const {
@@ -1617,11 +961,11 @@ void Vocoder::forward_from_norm(const float* mel_norm, const float* mean, const 
 }
 
 // Ragged batches.  Workspace: clip table, padded ln-mel, padded wav, then the generator's buffers for (B, Tmax).
-Vocoder::RaggedBufs Vocoder::ragged_bufs(Workspace& ws, int B, int Tmax) const {
+Vocoder::RaggedBufs Vocoder::ragged_bufs(Workspace& ws, int B, int Tmax, int tab_cols) const {
   RaggedBufs b{};
-  b.tab = ws.take<int>((size_t)2 * B);
+  b.tab = ws.take<int>((size_t)tab_cols * B);
   b.ln_buf = mel_in(ws, B, Tmax);
-  b.wav_pad = ws.take<float>((size_t)B * Tmax * hop_);
+  b.wav_pad = ws.take<float>((size_t)B * Tmax * p_.hop);
   return b;
 }
 
@@ -1655,8 +999,8 @@ void Vocoder::ragged_run(const float* x, const float* mean, const float* std_, c
     run_t<A>(rb.ln_buf, B, T, wav_pad, ws, s, mask_tab);
   });
   StageTag tag("voc_post");
-  ProfScope ps("ragged_wav_pack_kernel", 0.0, 2.0 * 4.0 * N * hop_, s);
-  launch_ragged_wav_pack(wav_pad, tab, B, T, hop_, wav, s);
+  ProfScope ps("ragged_wav_pack_kernel", 0.0, 2.0 * 4.0 * N * p_.hop, s);
+  launch_ragged_wav_pack(wav_pad, tab, B, T, p_.hop, wav, s);
 }
 
 void Vocoder::forward_ragged(const float* mel, const int* lengths, int B, long N, float* wav, Workspace& ws,
@@ -1689,18 +1033,18 @@ Vocoder::ChunkPlan Vocoder::chunk_plan(const int* lengths, const int* context, c
     M2S_CHECK((long)context[b] + hold[b] < lengths[b],
               c + ": context " + std::to_string(context[b]) + " + hold " + std::to_string(hold[b]) +
                   " leaves no row of its " + std::to_string(lengths[b]) + " to emit");
-    left = left && context[b] >= back_;
-    right = right && hold[b] >= ahead_;
+    left = left && context[b] >= p_.back;
+    right = right && hold[b] >= p_.ahead;
     cmin = std::min(cmin, context[b]);
   }
   p.mask = !right && p.d.Tmin < T;
   p.tab.assign((size_t)(5 + nl) * B, 0);
   int start = 0, rows_now = T;  // the block as it stands: rows start .. start + rows_now - 1 of every span
   for (int l = 0; l < nl; ++l) {
-    int s0 = left ? cmin - lvl_back_[l] : 0, e0 = start + rows_now;
+    int s0 = left ? cmin - p_.lvl_back[l] : 0, e0 = start + rows_now;
     if (right) {
       int need = 0;
-      for (int b = 0; b < B; ++b) need = std::max(need, lengths[b] - hold[b] + lvl_ahead_[l]);
+      for (int b = 0; b < B; ++b) need = std::max(need, lengths[b] - hold[b] + p_.lvl_ahead[l]);
       e0 = std::min(e0, need);
     }
     s0 = std::max(s0, start);
@@ -1726,20 +1070,13 @@ Vocoder::ChunkPlan Vocoder::chunk_plan(const int* lengths, const int* context, c
   return p;
 }
 
-Vocoder::ChunkBufs Vocoder::chunk_bufs(Workspace& ws, int B, int Tmax) const {
-  ChunkBufs b{};
-  b.tab = ws.take<int>((size_t)(5 + h_.n_up) * B);
-  b.ln_buf = mel_in(ws, B, Tmax);
-  b.wav_pad = ws.take<float>((size_t)B * Tmax * hop_);
-  return b;
-}
 
 size_t Vocoder::chunk_workspace_bytes(const int* lengths, const int* context, const int* hold, int B) const {
   long n = 0;
   for (int b = 0; lengths && b < B; ++b) n += lengths[b];
   const ChunkPlan p = chunk_plan(lengths, context, hold, B, n);
   return Workspace::bytes([&](Workspace& ws) {
-    chunk_bufs(ws, B, p.d.Tmax);
+    ragged_bufs(ws, B, p.d.Tmax, 5 + h_.n_up);
     gen_ws(ws, B, p.d.Tmax);
   });
 }
@@ -1748,7 +1085,7 @@ void Vocoder::forward_chunk(const float* mel, const int* lengths, const int* con
                             float* wav, Workspace& ws, hipStream_t s) {
   const ChunkPlan p = chunk_plan(lengths, context, hold, B, N);
   const int nm = h_.num_mels, cs = chan_stride(nm), T = p.d.Tmax;
-  const ChunkBufs cb = chunk_bufs(ws, B, T);
+  const RaggedBufs cb = ragged_bufs(ws, B, T, 5 + h_.n_up);
   rtab_.upload_ints(p.tab.data(), p.tab.size(), cb.tab, s);
   Cone cone{};
   for (int l = 0; l < h_.n_up; ++l) {
@@ -1768,9 +1105,9 @@ void Vocoder::forward_chunk(const float* mel, const int* lengths, const int* con
     run_t<A>(cb.ln_buf, B, T, cb.wav_pad, ws, s, p.mask ? cb.tab : nullptr, p.crop ? &cone : nullptr);
   });
   StageTag tag("voc_post");
-  ProfScope ps("chunk_wav_pack_kernel", 0.0, 2.0 * 4.0 * p.out_rows * hop_, s);
+  ProfScope ps("chunk_wav_pack_kernel", 0.0, 2.0 * 4.0 * p.out_rows * p_.hop, s);
   const int* const emit = cb.tab + (size_t)2 * B;  // [src | dst | n]
-  launch_chunk_wav_pack(cb.wav_pad, emit, emit + B, emit + (size_t)2 * B, B, p.t_final, hop_, wav, s);
+  launch_chunk_wav_pack(cb.wav_pad, emit, emit + B, emit + (size_t)2 * B, B, p.t_final, p_.hop, wav, s);
 }
 
 constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right pad of 6 (launch_conv_post)
@@ -1784,13 +1121,13 @@ constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right 
 template <typename T>
 void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out,
                                 hipStream_t s) {
-  const int nk = h_.n_kernels, np = (int)rbs_[i * nk].dil.size();
+  const int nk = h_.n_kernels, np = (int)p_.rbs[i * nk].dil.size();
   int ord[CONV_BATCH];
   for (int j = 0; j < nk; ++j) ord[j] = j;
-  std::sort(ord, ord + nk, [&](int x, int y) { return rbs_[i * nk + x].c1[0].kp > rbs_[i * nk + y].c1[0].kp; });
+  std::sort(ord, ord + nk, [&](int x, int y) { return p_.rbs[i * nk + x].c1[0].kp > p_.rbs[i * nk + y].c1[0].kp; });
   auto a_in = [&](int j, int p) -> const T* { return p == 0 ? X : Bt[j][1 + ((p - 1) & 1)]; };  // lrelu(x) of pair p
   bool halo = mrf_halo_;  // input rows staged once per tile (conv1d_halo.hip) where the stage has the weights for it
-  for (int j = 0; j < nk; ++j) halo = halo && !rbs_[i * nk + j].h1.empty();
+  for (int j = 0; j < nk; ++j) halo = halo && !p_.rbs[i * nk + j].h1.empty();
   auto launch_batch = [&](ConvArgs* cs, int n, double fl, double by) {
     if (halo)
       launch_conv1d_halo_sp(cs, n, s, fl, by);
@@ -1802,7 +1139,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
     double fl = 0.0, by = 0.0, f, b;
     for (int jj = 0; jj < nk; ++jj) {
       const int j = ord[jj];
-      const RB& rb = rbs_[i * nk + j];
+      const RB& rb = p_.rbs[i * nk + j];
       ConvArgs c = conv_args(rb.c1[p]);
       if (halo) c.w = rb.h1[p];
       c.x = a_in(j, p);
@@ -1820,7 +1157,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
     fl = by = 0.0;
     for (int jj = 0; jj < nk; ++jj) {
       const int j = p + 1 < np ? ord[jj] : jj;
-      const RB& rb = rbs_[i * nk + j];
+      const RB& rb = p_.rbs[i * nk + j];
       ConvArgs c = conv_args(rb.c2[p]);
       if (halo) c.w = rb.h2[p];
       c.x = Bt[j][0];
@@ -1886,7 +1223,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     mtab = cone->mask[l];
     if (cone->drop[l] == 0 && cone->keep[l] == Tc) return;
     const long scale = L / Tc, keep = cone->keep[l] * scale;
-    const size_t row_bytes = sizeof(T) * Elem<T>::R * (size_t)ups_[l].cs_in;
+    const size_t row_bytes = sizeof(T) * Elem<T>::R * (size_t)p_.ups[l].cs_in;
     StageTag tag("glue");
     ProfScope ps("crop_rows_kernel", 0.0, 2.0 * B * keep * row_bytes, s);
     launch_crop_rows(S, B, L, cone->drop[l] * scale, keep, row_bytes, Hb[0], s);
@@ -1895,10 +1232,10 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     L = (int)keep;
   };
   auto is_batched = [&](int i) {  // stage i's MRF runs as batched split launches (mrf_stage_batched)
-    const PConv& up = ups_[i];
-    const bool fused = (std::is_same<T, bf16_t>::value || SPL) && mrf_fused_ && !rbs_[i * nk].f1.empty();
+    const PConv& up = p_.ups[i];
+    const bool fused = (std::is_same<T, bf16_t>::value || SPL) && mrf_fused_ && !p_.rbs[i * nk].f1.empty();
     bool b = SPL && mrf_batch_ && !fused && h_.resblock == 1 && nk <= CONV_BATCH && up.cout >= 32 && up.cout % 32 == 0;
-    for (int j = 0; j < nk; ++j) b = b && rbs_[i * nk + j].dil.size() == rbs_[i * nk].dil.size();
+    for (int j = 0; j < nk; ++j) b = b && p_.rbs[i * nk + j].dil.size() == p_.rbs[i * nk].dil.size();
     return b;
   };
   // split: the upsampler's input S may already hold lrelu(x) (slope 0.1, models.py:116-117), written so
@@ -1907,7 +1244,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
   bool s_act = SPL;
   {
     StageTag tag("voc_pre");
-    ConvArgs a = conv_args(pre_);
+    ConvArgs a = conv_args(p_.pre);
     a.x = mel_nlc;
     a.y = S;
     a.L_in = L;
@@ -1917,10 +1254,10 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       a.act = ACT_LRELU;
       a.act_slope = 0.1f;
     }
-    run_conv<T>(a, pre_, s);
+    run_conv<T>(a, p_.pre, s);
   }
   for (int i = 0; i < h_.n_up; ++i) {
-    const PConv& up = ups_[i];
+    const PConv& up = p_.ups[i];
     const bool batched = is_batched(i);
     crop(i);
     StageTag tag("ups_c" + std::to_string(up.cout));
@@ -1954,7 +1291,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     // every resblock of the stage must carry e4m3 weights (q8 is decided per resblock: k <= 31)
     bool stage_f8 = std::is_same<T, bf16_t>::value;
     for (int j = 0; j < nk && stage_f8; ++j) {
-      const RB& rb = rbs_[i * nk + j];
+      const RB& rb = p_.rbs[i * nk + j];
       stage_f8 = rb.q1.size() == rb.dil.size() && rb.q2.size() == rb.dil.size() && !rb.dil.empty();
     }
     if (stage_f8) {
@@ -1972,7 +1309,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       }
       const double rows = (double)B * L;
       for (int j = 0; j < nk; ++j) {
-        const RB& rb = rbs_[i * nk + j];
+        const RB& rb = p_.rbs[i * nk + j];
         const int np = (int)rb.dil.size();
         const bf16_t* cur = reinterpret_cast<const bf16_t*>(X);
         const uint8_t* cur8 = X8;
@@ -1996,7 +1333,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       continue;
     }
     for (int j = 0; j < nk; ++j) {
-      const RB& rb = rbs_[i * nk + j];
+      const RB& rb = p_.rbs[i * nk + j];
       const T* hcur = X;
       const int np = (int)rb.dil.size();
       const int accum = j == 0 ? 0 : (j == nk - 1 ? 2 : 1);
@@ -2055,9 +1392,9 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     }
   }
   StageTag tag("voc_post");
-  mask_tail(S, L, CONV_POST_TAPS - 1, chan_stride(post_c_));
-  ProfScope ps(tname<T>(post_c_ <= 64 ? "conv_post_tile_kernel" : "conv_post_kernel"), 2.0 * B * L * post_c_ * 7, (sizeof(T) * Elem<T>::R) * (double)B * L * post_c_ + 4.0 * B * L, s);
-  launch_conv_post<T>(S, B, L, post_c_, chan_stride(post_c_), static_cast<const float*>(arena_.ptr(post_w_)), post_b_,
+  mask_tail(S, L, CONV_POST_TAPS - 1, chan_stride(p_.post_c));
+  ProfScope ps(tname<T>(p_.post_c <= 64 ? "conv_post_tile_kernel" : "conv_post_kernel"), 2.0 * B * L * p_.post_c * 7, (sizeof(T) * Elem<T>::R) * (double)B * L * p_.post_c + 4.0 * B * L, s);
+  launch_conv_post<T>(S, B, L, p_.post_c, chan_stride(p_.post_c), static_cast<const float*>(arena_.ptr(p_.post_w)), p_.post_b,
                       wav, s);
 }
 

@@ -23,7 +23,8 @@ struct HostTensor {
 using StateDict = std::map<std::string, HostTensor>;
 StateDict make_state_dict(const m2s_tensor* t, int n);
 
-// Host staging of every packed array; one device allocation per model.
+// Host staging of every packed array; one device allocation per model.  The packers (pack_acoustic.cpp,
+// pack_vocoder.cpp) fill it with add(); upload() moves it to the device and frees the host copy.
 class Arena {
  public:
   size_t add(const void* p, size_t bytes);
@@ -33,11 +34,13 @@ class Arena {
   }
   void upload(int device);
   void* ptr(size_t off) const { return static_cast<char*>(dev_) + off; }
-  size_t bytes() const { return host_.size(); }
+  size_t bytes() const { return bytes_; }                  // staged so far (kept across upload)
+  const uint8_t* host() const { return host_.data(); }     // the staged bytes, until upload()
   ~Arena();
 
  private:
   std::vector<uint8_t> host_;
+  size_t bytes_ = 0;
   void* dev_ = nullptr;
 };
 
@@ -145,6 +148,92 @@ struct WindowPlan {
 // M2S_E_ARG, before any launch: window outside 1..16, an unknown merge, a context with mean, a context entry outside
 // 0..min(W - 1, len - 1), and the ragged calls' own argument errors
 WindowPlan window_plan(const int* lengths, const int* context, int B, long rows, int window, int merge);
+
+// ---- packed plans: what the packers produce beside the arena bytes (offsets until the engine resolves them) ----
+// One block of the tf_efficientnetv2_b2 backbone as pack.hpp's for_each_backbone_block yields it: block `index`
+// is rep `rep` of `stage`.
+struct BlockDef {
+  int index = 0, stage = 0, rep = 0;
+  int type = 0;  // 0 cn, 1 er, 2 ir
+  int k = 3, stride = 1, cin = 0, cout = 0, mid = 0, rd = 0;
+  bool skip = false;
+  std::string key() const {  // state-dict prefix
+    return "cnn.backbone.blocks." + std::to_string(stage) + "." + std::to_string(rep) + ".";
+  }
+};
+// ... packed for the inference engine
+struct Block : BlockDef {
+  PConv c1, c2;              // cn: c1 ; er: conv_exp, conv_pwl ; ir: conv_pw, conv_pwl
+  size_t dw_w = 0, dw_b = 0;  // ir depthwise, tap-major (9 x cs_mid) and (cs_mid), fp32
+  size_t dw_w2 = 0;           // bf16 engines: the same taps as bf16 in the channel's dword half
+  PConv se1, se2;             // ir SE: conv_reduce (mid -> rd, SiLU), conv_expand (rd -> mid, sigmoid)
+  size_t er_wexp = 0, er_wpwl = 0;  // bf16 er 32 -> 128 -> 32 stride 1: fused-kernel fragment orders
+  bool er_frag = false;
+  // fp8 engines, er 32 -> 128 -> 32 stride 1 on e4m3 (er8_fused.hip): fragments, per-channel scales
+  size_t er8_wexp = 0, er8_sexp = 0, er8_wpwl = 0, er8_spwl = 0;
+  bool er8 = false;
+  // fp8 engines, er 56 -> 224 -> 56 stride 1 on e4m3 (er8w_fused.hip): stage stream, per-channel scales
+  size_t er8w_w = 0, er8w_sexp = 0, er8w_spwl = 0;
+  bool er8w = false;
+  size_t er_sp_w = 0;  // split fp32 er stride 1: er_sp_fused.hip stage stream
+  bool er_sp = false;
+  bool ers_sp = false;  // split fp32 er stride 2 (blocks.1.0): er_wexp / er_wpwl in [hi/lo] fragment order
+  // fp8 engines, ir conv_pwl: e4m3 bytes [f8_npad][f8_kp] of W / scale, per-channel scales, bias
+  size_t f8_w = 0, f8_s = 0, f8_b = 0;
+  int f8_kp = 0, f8_npad = 0;
+  bool f8_pwl = false;
+  // fp8 engines, ir conv_pw (stride 1): e4m3 bytes [round_up(cs_mid, 32)][f8x_kp] of W / scale, scales
+  size_t f8x_w = 0, f8x_s = 0;
+  int f8x_kp = 0;
+  bool f8_pw = false;
+};
+
+struct AcousticPlan {
+  size_t stem_w = 0, stem_b = 0;
+  std::vector<Block> blocks;
+  PConv lstm_ih;
+  size_t whh = 0, head_wt = 0, head_b = 0;
+  size_t whh_win = 0;  // W_hh in lstm_window.hip's row order (pack_lstm_window_whh)
+  int max_mid_cs = 0;
+};
+// pack_acoustic.cpp: BatchNorm folded, every weight array of a `dtype` engine staged in `ar`.  Host code only.
+void pack_acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, Arena& ar, AcousticPlan& p);
+
+// One resblock of the HiFi-GAN generator.
+struct RB {
+  int k = 3;
+  std::vector<int> dil;
+  std::vector<PConv> c1, c2;  // resblock "1": c1 (dilated) + c2 ; "2": c1 only
+  // bf16 resblock "1" at C in {32, 64}: the same weights in the fused kernel's fragment order
+  std::vector<size_t> f1_off, f2_off;
+  std::vector<const bf16_t*> f1, f2;
+  // split resblock "1" at C in {64, 128}: conv1d_halo.hip fragment order
+  std::vector<size_t> h1_off, h2_off;
+  std::vector<const bf16_t*> h1, h2;
+  // fp8 resblock "1" at C in {128, 256}: e4m3 [C][k C] weights, scales, biases (conv1d_f8)
+  struct F8 {
+    size_t w = 0, s = 0, b = 0;
+    const void* wp = nullptr;
+    const float* sp = nullptr;
+    const float* bp = nullptr;
+  };
+  std::vector<F8> q1, q2;
+};
+
+struct VocoderPlan {
+  PConv pre;
+  std::vector<PConv> ups;
+  std::vector<RB> rbs;
+  size_t post_w = 0;
+  float post_b = 0.f;
+  int post_c = 0, hop = 1;
+  // reach in mel rows (interval propagation over the config): of the whole generator, and of what follows level l
+  int back = 0, ahead = 0, lvl_back[8] = {}, lvl_ahead[8] = {};
+};
+// pack_vocoder.cpp: weight norm folded, every weight array staged in `ar`, and the reach.  f8_mrf64 / f8_mrf32:
+// fp8 engines also get e4m3 copies of the C = 64 / C = 32 resblock convs.  Host code only.
+void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f8_mrf64, bool f8_mrf32, Arena& ar,
+                  VocoderPlan& p);
 
 class Acoustic {
  public:
@@ -268,41 +357,12 @@ class Acoustic {
     // conv_pwl runs on se_ws; ... and ir_ws handed it plain fp32 rows
     bool f8, sews, mid_f32;
   };
-  size_t whh_win_ = 0;  // W_hh in lstm_window.hip's row order (pack_lstm_window_whh)
   // the recurrence kernel for (B, T): the selection ladder shared by bilstm and bilstm_ragged.  seq_steps / rows:
   // the recurrent steps and (b, t) rows that count as algorithmic work (a ragged call: the valid ones)
   void lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps, double rows,
                        hipStream_t s);
   static size_t lstm_sync_bytes();
   RaggedTable rtab_;
-  struct Block {
-    int type = 0;  // 0 cn, 1 er, 2 ir
-    int stride = 1, cin = 0, cout = 0, mid = 0, rd = 0;
-    bool skip = false;
-    PConv c1, c2;              // cn: c1 ; er: conv_exp, conv_pwl ; ir: conv_pw, conv_pwl
-    size_t dw_w = 0, dw_b = 0;  // ir depthwise, tap-major (9 x cs_mid) and (cs_mid), fp32
-    size_t dw_w2 = 0;           // bf16 engines: the same taps as bf16 in the channel's dword half
-    PConv se1, se2;             // ir SE: conv_reduce (mid -> rd, SiLU), conv_expand (rd -> mid, sigmoid)
-    size_t er_wexp = 0, er_wpwl = 0;  // bf16 er 32 -> 128 -> 32 stride 1: fused-kernel fragment orders
-    bool er_frag = false;
-    // fp8 engines, er 32 -> 128 -> 32 stride 1 on e4m3 (er8_fused.hip): fragments, per-channel scales
-    size_t er8_wexp = 0, er8_sexp = 0, er8_wpwl = 0, er8_spwl = 0;
-    bool er8 = false;
-    // fp8 engines, er 56 -> 224 -> 56 stride 1 on e4m3 (er8w_fused.hip): stage stream, per-channel scales
-    size_t er8w_w = 0, er8w_sexp = 0, er8w_spwl = 0;
-    bool er8w = false;
-    size_t er_sp_w = 0;  // split fp32 er stride 1: er_sp_fused.hip stage stream
-    bool er_sp = false;
-    bool ers_sp = false;  // split fp32 er stride 2 (blocks.1.0): er_wexp / er_wpwl in [hi/lo] fragment order
-    // fp8 engines, ir conv_pwl: e4m3 bytes [f8_npad][f8_kp] of W / scale, per-channel scales, bias
-    size_t f8_w = 0, f8_s = 0, f8_b = 0;
-    int f8_kp = 0, f8_npad = 0;
-    bool f8_pwl = false;
-    // fp8 engines, ir conv_pw (stride 1): e4m3 bytes [round_up(cs_mid, 32)][f8x_kp] of W / scale, scales
-    size_t f8x_w = 0, f8x_s = 0;
-    int f8x_kp = 0;
-    bool f8_pw = false;
-  };
   template <typename T>
   void effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
                 Workspace& ws, hipStream_t s);
@@ -324,11 +384,7 @@ class Acoustic {
 
   int dtype_, device_, n_mels_, hidden_;
   Arena arena_;
-  size_t stem_w_ = 0, stem_b_ = 0;
-  std::vector<Block> blocks_;
-  PConv lstm_ih_;
-  size_t whh_ = 0, head_wt_ = 0, head_b_ = 0;
-  int max_mid_cs_ = 0;
+  AcousticPlan p_;
   unsigned* err_host_ = nullptr;  // pinned, host-mapped: set by lstm_persistent_kernel on a barrier timeout
   unsigned* err_dev_ = nullptr;
   // the granule BiLSTM kernels' sync buffer (lstm_small / lstm_x3g), zeroed once, and its epoch count
@@ -341,7 +397,7 @@ class Vocoder {
  public:
   Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int device);
   int device() const { return device_; }
-  int hop() const { return hop_; }
+  int hop() const { return p_.hop; }
   int num_mels() const { return h_.num_mels; }
   size_t workspace_bytes(int B, int T) const;
   void forward(const float* mel, int layout, int B, int T, float* wav, Workspace& ws, hipStream_t s);
@@ -360,8 +416,8 @@ class Vocoder {
   // which clip b's rows context[b] .. lengths[b] - hold[b] - 1 are emitted: packed wav (out_rows * hop).  Stateless;
   // the rows equal the whole clip's where context >= back or the span starts the clip, and hold >= ahead or it ends it.
   void reach(int* back, int* ahead) const {
-    *back = back_;
-    *ahead = ahead_;
+    *back = p_.back;
+    *ahead = p_.ahead;
   }
   size_t chunk_workspace_bytes(const int* lengths, const int* context, const int* hold, int B) const;
   void forward_chunk(const float* mel, const int* lengths, const int* context, const int* hold, int B, long N,
@@ -370,14 +426,14 @@ class Vocoder {
   // (m2s_vocoder_set_chunk_cone, for tests and timing); off: every stage runs on the full spans.  Same contract
   bool chunk_cone_ = true;
   size_t act_elems(int B, int T) const;
-  bool mrf_fused_ = true;
+  bool mrf_fused_ = true;  // bf16: fused ResBlock1 kernel for C in {32, 64} (env M2S_MRF_FUSED=0 disables)
   bool mrf_halo_ = true;   // split: C = 64 MRF convs with once-staged input rows (env M2S_MRF_HALO=0: conv_gemm)
   // fp8: the C = 64 / 32 MRF convs on e4m3 (conv1d_f8, 128 / C taps a K step; env M2S_F8_MRF64=1 / M2S_F8_MRF32=1).
   // Off: the fused bf16 ResBlock1 keeps a resblock's intermediates on chip and is faster at configs[4] (8 x 1000
   // frames, same box, gpurun_out/f8s2: fp8 step 74.8 ms with both fused, 79.7 with C = 64 on e4m3, 85.1 with both)
   bool f8_mrf64_ = false;
   bool f8_mrf32_ = false;
-  bool mrf_batch_ = true;  // split: resblocks of a conv_gemm MRF stage batched per launch (env M2S_MRF_BATCH=0 disables)  // bf16: fused ResBlock1 kernel for C in {32, 64} (env M2S_MRF_FUSED=0 disables)
+  bool mrf_batch_ = true;  // split: resblocks of a conv_gemm MRF stage batched per launch (env M2S_MRF_BATCH=0 disables)
 
  private:
   // tab (ragged calls, with a clip shorter than Tn): the device clip table; the input S of every upsampler and of
@@ -403,12 +459,13 @@ class Vocoder {
   void gen_ws(Workspace& ws, int B, int T) const;  // gen_bufs of the engine's dtype
   // the channel-last generator input, rows x cs(num_mels) activation elements
   void* mel_in(Workspace& ws, int B, int T) const;
-  struct RaggedBufs {  // a ragged call's prefix: clip table, padded ln-mel, padded wav; then gen_bufs at (B, Tmax)
+  struct RaggedBufs {  // a ragged or chunk call's prefix: clip table, padded ln-mel, padded wav; then gen_bufs at (B, Tmax)
     int* tab;
     void* ln_buf;
     float* wav_pad;
   };
-  RaggedBufs ragged_bufs(Workspace& ws, int B, int Tmax) const;
+  // tab_cols: ints per clip of the table (ragged: off, len; chunk: 5 + n_up columns, chunk_plan)
+  RaggedBufs ragged_bufs(Workspace& ws, int B, int Tmax, int tab_cols = 2) const;
   // A chunk call, validated (M2S_E_ARG before any launch): the padded block, the rows each level keeps, and the
   // device table [off | len | src | dst | n | len at level 0 | ... | len at level n_up - 1], B ints a column:
   // clip b's emitted rows are rows src[b] .. src[b] + n[b] - 1 of the final block and packed rows dst[b] ...
@@ -421,47 +478,15 @@ class Vocoder {
     std::vector<int> tab;
   };
   ChunkPlan chunk_plan(const int* lengths, const int* context, const int* hold, int B, long rows) const;
-  struct ChunkBufs {  // clip table, padded ln-mel, padded wav; then gen_bufs at (B, Tmax)
-    int* tab;
-    void* ln_buf;
-    float* wav_pad;
-  };
-  ChunkBufs chunk_bufs(Workspace& ws, int B, int Tmax) const;
   void ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
                   float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
   template <typename T>
   void mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out, hipStream_t s);
-  struct RB {
-    int k = 3;
-    std::vector<int> dil;
-    std::vector<PConv> c1, c2;  // resblock "1": c1 (dilated) + c2 ; "2": c1 only
-    // bf16 resblock "1" at C in {32, 64}: the same weights in the fused kernel's fragment order
-    std::vector<size_t> f1_off, f2_off;
-    std::vector<const bf16_t*> f1, f2;
-    // split resblock "1" at C in {64, 128}: conv1d_halo.hip fragment order
-    std::vector<size_t> h1_off, h2_off;
-    std::vector<const bf16_t*> h1, h2;
-    // fp8 resblock "1" at C in {128, 256}: e4m3 [C][k C] weights, scales, biases (conv1d_f8)
-    struct F8 {
-      size_t w = 0, s = 0, b = 0;
-      const void* wp = nullptr;
-      const float* sp = nullptr;
-      const float* bp = nullptr;
-    };
-    std::vector<F8> q1, q2;
-  };
   m2s_hifigan_h h_;
-  int dtype_, device_, hop_ = 1;
-  // reach in mel rows (interval propagation over h_): of the whole generator, and of what follows level l
-  int back_ = 0, ahead_ = 0, lvl_back_[8] = {}, lvl_ahead_[8] = {};
+  int dtype_, device_;
   Arena arena_;
-  PConv pre_;
-  std::vector<PConv> ups_;
-  std::vector<RB> rbs_;
+  VocoderPlan p_;
   RaggedTable rtab_;
-  size_t post_w_ = 0;
-  float post_b_ = 0.f;
-  int post_c_ = 0;
 };
 
 // The pipeline calls' scratch: mel_norm (rows, n_mels), the dense call's channel-last vocoder input (4 bytes an
