@@ -132,6 +132,27 @@ void launch_ir_pwdw_s2(const void* x, int N, int cs_in, int kp, const void* wpw,
 bool conv1d_halo_sp_supported(int C, int cs, int k, int dil);
 size_t conv1d_halo_frag_elems(int C, int k);
 void launch_conv1d_halo_sp(const struct ConvArgs* a, int n, hipStream_t s, double flops, double bytes);
+// One ResBlock1 pair x' = x + c2(lrelu(c1(lrelu(x)))) per launch with the tensor between the two convs kept in
+// LDS (conv1d_halo_pair_kernel): x holds lrelu(x), the residual is recovered from it as the c2 launches do.
+// chain = false: n independent pairs (grid.z), y = the pair's output (act: stored as lrelu(x'), the next pair's
+// operand; accum as ConvArgs::accum, the MRF sum read from and written to y).  chain = true: the n pairs of one
+// tile run in order in one workgroup, pair j accumulating as its accum says into a running sum in registers
+// (rounded to hi + lo between pairs as the stored sum is), and only the last pair's y is written.
+struct HaloPair {
+  const void* x;
+  const void* w1;  // c1 (k taps, dilation dil) and c2 (k taps, dilation 1) in conv1d_halo fragment order
+  const void* w2;
+  const float* b1;
+  const float* b2;
+  void* y;
+  int k, dil;
+  int accum;
+  int act;  // LeakyReLU 0.1 on the value stored
+};
+bool conv1d_halo_pair_supported(int C, int cs, int k, int dil);
+bool conv1d_halo_pair_fills(int C, int B, int L);  // clips x tiles fill the device's resident workgroup slots
+void launch_conv1d_halo_pair(const HaloPair* p, int n, int C, int B, int L, bool chain, float div, hipStream_t s,
+                             double flops, double bytes);
 // w1/w2 are in fragment order: [rb1_frag_taps(C, k, split)][hi/lo if split][C/16][C/32][64 lanes][8] bf16,
 // element (tap t, n16, k32, lane, e) = W[n16*16 + lane%16][k32*32 + 8*(lane/16) + e][t] (zero taps past k).
 bool rb1_fused_supported(int C, int cs, int k, const int* dil, int np, int kp, bool split);

@@ -872,9 +872,10 @@ Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int dev
     : h_(h), dtype_(dtype), device_(device) {
   for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
            {"M2S_MRF_FUSED", &mrf_fused_}, {"M2S_MRF_BATCH", &mrf_batch_}, {"M2S_MRF_HALO", &mrf_halo_},
-           {"M2S_F8_MRF64", &f8_mrf64_},   {"M2S_F8_MRF32", &f8_mrf32_}})
+           {"M2S_F8_MRF64", &f8_mrf64_},   {"M2S_F8_MRF32", &f8_mrf32_},   {"M2S_MRF_PAIR", &mrf_pair_},
+           {"M2S_MRF_CHAIN", &mrf_chain_}, {"M2S_MRF_PAIR128", &mrf_pair128_}})
     env_flag(name, *v);
-  pack_vocoder(sd, h, dtype, f8_mrf64_, f8_mrf32_, arena_, p_);
+  pack_vocoder(sd, h, dtype, f8_mrf64_, f8_mrf32_, arena_, p_, mrf_pair_ && mrf_pair128_);
   arena_.upload(device);
   p_.pre.resolve(arena_);
   for (auto& u : p_.ups) u.resolve(arena_);
@@ -1118,6 +1119,8 @@ constexpr int CONV_POST_TAPS = 7;  // conv_post: Conv1d(C, 1, 7) behind a right 
 // invertible: x = a > 0 ? a : 10 a) and stores lrelu(xt + x) for the next pair's c1.  Per pair:
 // one launch for the c1 of every resblock, one for the c2 (the last pair's c2 accumulates the MRF
 // sum S = (x_0 + x_1 + ...) / num_kernels in resblock order, models.py:119-125, so it stays serial).
+// C = 64 (M2S_MRF_PAIR): one launch per pair instead, c1 and c2 fused with the tensor between them in LDS
+// (conv1d_halo_pair_kernel); the last pairs chained in one launch where the pass fills the chip.
 template <typename T>
 void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out,
                                 hipStream_t s) {
@@ -1128,6 +1131,58 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
   auto a_in = [&](int j, int p) -> const T* { return p == 0 ? X : Bt[j][1 + ((p - 1) & 1)]; };  // lrelu(x) of pair p
   bool halo = mrf_halo_;  // input rows staged once per tile (conv1d_halo.hip) where the stage has the weights for it
   for (int j = 0; j < nk; ++j) halo = halo && !p_.rbs[i * nk + j].h1.empty();
+  // each (c1, c2) pair in one launch (conv1d_halo_pair_kernel) where every pair of the stage is within its reach;
+  // a stage with one that is not runs as a whole on the launches below
+  const int C = p_.ups[i].cout;
+  bool pair = halo && mrf_pair_ && std::is_same<T, sp_t>::value && (C == 64 || mrf_pair128_);
+  for (int j = 0; j < nk && pair; ++j)
+    for (int d : p_.rbs[i * nk + j].dil) pair = pair && conv1d_halo_pair_supported(C, chan_stride(C), p_.rbs[i * nk + j].k, d);
+  for (int j = 0; j < nk; ++j)  // C = 128 has the fragments for the pair kernel only
+    for (int d : p_.rbs[i * nk + j].dil) halo = halo && conv1d_halo_sp_supported(C, chan_stride(C), p_.rbs[i * nk + j].k, d);
+  if (pair) {
+    const double es = sizeof(T) * Elem<T>::R, act = es * B * L * C;
+    auto make = [&](int j, int p, double* fl, double* by) {
+      const RB& rb = p_.rbs[i * nk + j];
+      HaloPair h{};
+      h.x = a_in(j, p);
+      h.w1 = rb.h1[p];
+      h.w2 = rb.h2[p];
+      h.b1 = conv_args(rb.c1[p]).bias;
+      h.b2 = conv_args(rb.c2[p]).bias;
+      h.k = rb.k;
+      h.dil = rb.dil[p];
+      *fl += 2.0 * (rb.c1[p].macs_per_row + rb.c2[p].macs_per_row) * B * L;
+      *by += act + es * 2.0 * C * C * rb.k;  // x in, both weight sets; the caller adds what is stored
+      return h;
+    };
+    for (int p = 0; p + 1 < np; ++p) {  // a_{p+1} = lrelu(x + xt) of every resblock, longest K first
+      HaloPair hp[CONV_BATCH];
+      double fl = 0.0, by = 0.0;
+      for (int jj = 0; jj < nk; ++jj) {
+        hp[jj] = make(ord[jj], p, &fl, &by);
+        hp[jj].y = Bt[ord[jj]][1 + (p & 1)];
+        hp[jj].act = 1;
+        by += act;
+      }
+      launch_conv1d_halo_pair(hp, nk, C, B, L, false, 1.f, s, fl, by);
+    }
+    // the last pairs in resblock order: xs = sum_j resblock_j(x); S = xs / num_kernels, lrelu'd for an upsampler
+    HaloPair hp[CONV_BATCH];
+    double fl = 0.0, by = 0.0;
+    const bool chain = mrf_chain_ && conv1d_halo_pair_fills(C, B, L);
+    for (int j = 0; j < nk; ++j) {
+      double f = 0.0, b = 0.0;
+      hp[j] = make(j, np - 1, &f, &b);
+      hp[j].y = S;
+      hp[j].accum = j == 0 ? 0 : (j == nk - 1 ? 2 : 1);
+      hp[j].act = act_out && j == nk - 1;
+      if (!chain) launch_conv1d_halo_pair(&hp[j], 1, C, B, L, false, (float)nk, s, f, b + act * (hp[j].accum ? 2 : 1));
+      fl += f;
+      by += b;
+    }
+    if (chain) launch_conv1d_halo_pair(hp, nk, C, B, L, true, (float)nk, s, fl, by + act);
+    return;
+  }
   auto launch_batch = [&](ConvArgs* cs, int n, double fl, double by) {
     if (halo)
       launch_conv1d_halo_sp(cs, n, s, fl, by);

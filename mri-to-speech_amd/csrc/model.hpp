@@ -231,9 +231,10 @@ struct VocoderPlan {
   int back = 0, ahead = 0, lvl_back[8] = {}, lvl_ahead[8] = {};
 };
 // pack_vocoder.cpp: weight norm folded, every weight array staged in `ar`, and the reach.  f8_mrf64 / f8_mrf32:
-// fp8 engines also get e4m3 copies of the C = 64 / C = 32 resblock convs.  Host code only.
+// fp8 engines also get e4m3 copies of the C = 64 / C = 32 resblock convs; pair128: split engines also get the
+// C = 128 resblock convs in conv1d_halo fragment order (the fused pair kernel at C = 128).  Host code only.
 void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f8_mrf64, bool f8_mrf32, Arena& ar,
-                  VocoderPlan& p);
+                  VocoderPlan& p, bool pair128 = false);
 
 class Acoustic {
  public:
@@ -428,6 +429,15 @@ class Vocoder {
   size_t act_elems(int B, int T) const;
   bool mrf_fused_ = true;  // bf16: fused ResBlock1 kernel for C in {32, 64} (env M2S_MRF_FUSED=0 disables)
   bool mrf_halo_ = true;   // split: C = 64 MRF convs with once-staged input rows (env M2S_MRF_HALO=0: conv_gemm)
+  // split: each (c1, c2) pair of the C = 64 stage in one launch, the tensor between the convs kept in LDS
+  // (conv1d_halo_pair_kernel; env M2S_MRF_PAIR=0: one launch per conv; also off with M2S_MRF_HALO=0 / M2S_MRF_BATCH=0)
+  bool mrf_pair_ = true;
+  // ... and the last pair of every resblock chained in one launch with the MRF sum in registers, where the pass
+  // fills the chip (env M2S_MRF_CHAIN=0: one launch per resblock, the sum read and written in memory)
+  bool mrf_chain_ = true;
+  // ... and the C = 128 stage on the same kernel (8 waves, one workgroup per CU) instead of conv_gemm's batches
+  // (env M2S_MRF_PAIR128=1; packs that stage's weights a second time, in fragment order)
+  bool mrf_pair128_ = false;
   // fp8: the C = 64 / 32 MRF convs on e4m3 (conv1d_f8, 128 / C taps a K step; env M2S_F8_MRF64=1 / M2S_F8_MRF32=1).
   // Off: the fused bf16 ResBlock1 keeps a resblock's intermediates on chip and is faster at configs[4] (8 x 1000
   // frames, same box, gpurun_out/f8s2: fp8 step 74.8 ms with both fused, 79.7 with C = 64 on e4m3, 85.1 with both)

@@ -99,7 +99,7 @@ void generator_reach(const m2s_hifigan_h& h, VocoderPlan& p) {
 }  // namespace
 
 void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f8_mrf64, bool f8_mrf32, Arena& ar,
-                  VocoderPlan& p) {
+                  VocoderPlan& p, bool pair128) {
   M2S_CHECK(dtype == M2S_DT_F32 || dtype == M2S_DT_BF16 || dtype == M2S_DT_BF16X3 || dtype == M2S_DT_FP8, "bad dtype");
   M2S_CHECK(h.resblock == 1 || h.resblock == 2, "resblock must be 1 or 2");
   // fp8 engines: e4m3 resblock (MRF) convs at C = 64 / 128 / 256; conv_pre, the upsamplers and the fused
@@ -164,7 +164,10 @@ void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f
                       ((co >= 128 && !frag) || (co == 64 && f8_mrf64) || (co == 32 && f8_mrf32)) &&
                       conv1d_f8_supported(co, kk);
       bool halo = fsplit && h.resblock == 1 && !frag;
-      for (size_t d = 0; d < rb.dil.size(); ++d) halo = halo && conv1d_halo_sp_supported(co, chan_stride(co), kk, rb.dil[d]);
+      // C = 64: the per-conv kernel and the fused pair share the fragments; C = 128 (pair128): the fused pair's only
+      for (size_t d = 0; d < rb.dil.size(); ++d)
+        halo = halo && (conv1d_halo_sp_supported(co, chan_stride(co), kk, rb.dil[d]) ||
+                        (pair128 && co == 128 && conv1d_halo_pair_supported(co, chan_stride(co), kk, rb.dil[d])));
       auto load = [&](const std::string& name) {
         return RbWeights{fold_wn(sd, name, {co, co, kk}), need(sd, name + ".bias", {co}).data, co, kk};
       };
