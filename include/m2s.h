@@ -171,10 +171,29 @@ typedef struct m2s_hifigan_h {
 typedef struct m2s_vocoder m2s_vocoder;
 
 /* Frame preprocessing after the host decode (replaces _preprocess_frame,
- * run_mri_video_inference.py:34-54, except the cv2.resize): frames uint8 (n,h,w) grey
+ * run_mri_video_inference.py:34-54, on frames that already have the model's size): frames uint8 (n,h,w) grey
  * (channels = 1) or (n,h,w,3) BGR (channels = 3) -> out (n,h,w) fp32, per frame z-score then
  * min-max to [0, 1]; a constant frame gives zeros.  Device pointers, stream-ordered. */
 int m2s_preprocess_frames(const uint8_t* frames, int n, int h, int w, int channels, float* out, void* stream);
+
+/* The whole frame front end on the device, resize included: frames uint8 (n,h,w) grey (channels = 1) or
+ * (n,h,w,3) BGR (channels = 3) at the scanner's size -> out (n,out_h,out_w) fp32.  BGR -> grey first (the
+ * reference resizes the grey frame), then the resize, then the normalisation, in one kernel with no workspace.
+ * Serves both frame conventions of the reference:
+ *   inference   scripts/run_mri_video_inference.py:34-54 (_preprocess_frame): cv2.INTER_LINEAR, per-frame
+ *               z-score, min-max to [0, 1]            -> M2S_FRAME_LINEAR, M2S_FRAME_ZSCORE_MINMAX
+ *   training    mri2speech_code/preprocess_rtmri_data.py:99-113: cv2.INTER_AREA, / 255
+ *                                                     -> M2S_FRAME_AREA, M2S_FRAME_UNIT
+ * The resize is OpenCV's 8-bit two-tap fixed-point path (11-bit weights), which INTER_AREA also takes where no
+ * axis shrinks.  Limits, each M2S_E_ARG before anything is launched: channels is 1 or 3; h <= out_h and
+ * w <= out_w (shrinking takes other OpenCV paths: true area averaging, the exact-2x case); h*w <= 65536 and
+ * out_h*out_w <= 65536; interp and norm are values of the enums below.  n = 0 is a no-op.  Equal sizes give
+ * m2s_preprocess_frames' output bit for bit with LINEAR + ZSCORE_MINMAX.  Stateless: nothing is staged from the
+ * host, so the call can be captured into a graph.  Device pointers, stream-ordered. */
+enum m2s_frame_interp { M2S_FRAME_LINEAR = 0, M2S_FRAME_AREA = 1 };
+enum m2s_frame_norm { M2S_FRAME_ZSCORE_MINMAX = 0, M2S_FRAME_UNIT = 1 };
+int m2s_preprocess_frames_resize(const uint8_t* frames, int n, int h, int w, int channels, int out_h, int out_w,
+                                 int interp, int norm, float* out, void* stream);
 
 /* Packs a Generator state dict (weight_g/weight_v or plain weight after remove_weight_norm).
  * Strict like load_state_dict(ckpt['generator']): a missing key is M2S_E_ARG.  Synchronous. */

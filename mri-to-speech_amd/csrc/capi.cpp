@@ -215,6 +215,14 @@ int m2s_preprocess_frames(const uint8_t* frames, int n, int h, int w, int channe
   });
 }
 
+int m2s_preprocess_frames_resize(const uint8_t* frames, int n, int h, int w, int channels, int out_h, int out_w,
+                                 int interp, int norm, float* out, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(n >= 0 && (n == 0 || (frames && out)), "bad argument");
+    m2s::launch_frames(frames, n, h, w, channels, out_h, out_w, interp, norm, out, S(stream));  // checks the limits
+  });
+}
+
 int m2s_vocoder_create(const m2s_tensor* sd, int n, const m2s_hifigan_h* h, int dtype, int device, m2s_vocoder** out) {
   return guarded([&] {
     M2S_CHECK(out && h && (sd || n == 0), "null argument");

@@ -234,8 +234,15 @@ void launch_ers2_fused(const bf16_t* x, int N, int H, int W, int OH, int OW, int
                        bf16_t* y, double flops, double bytes, hipStream_t s, uint8_t* y8 = nullptr);
 
 // Decoded frames -> model input: uint8 (N,H,W) grey or (N,H,W,3) BGR -> fp32 (N,H,W) in [0, 1]
-// (_preprocess_frame, run_mri_video_inference.py:34-54, minus the host-side resize).  (preprocess.hip)
+// (_preprocess_frame, run_mri_video_inference.py:34-54, on frames already at the model's size).  (preprocess.hip)
 void launch_preprocess(const uint8_t* frames, int N, int H, int W, int channels, float* out, hipStream_t s);
+
+// The same with the resize on the device: uint8 (N,h,w) grey or (N,h,w,3) BGR at the scanner's size -> fp32
+// (N,out_h,out_w).  interp 0 = cv2.INTER_LINEAR, 1 = cv2.INTER_AREA (OpenCV's 8-bit two-tap path; no axis may
+// shrink); norm 0 = per-frame z-score + min-max (_preprocess_frame), 1 = / 255 (preprocess_rtmri_data.py:99-113).
+// At most 65536 pixels a frame on either side.  One workgroup per frame, no workspace.  (frames.hip)
+void launch_frames(const uint8_t* frames, int N, int h, int w, int channels, int out_h, int out_w, int interp, int norm,
+                   float* out, hipStream_t s);
 
 // Global average pool: x (N,P,cs) T -> feats (N,C) fp32 (dense, row stride C).
 template <typename T>

@@ -2,8 +2,8 @@
 // model consumes.  Restates scripts/run_mri_video_inference.py:34-54 (_preprocess_frame) after
 // the host decode: BGR -> grey (cv2.COLOR_BGR2GRAY's 8-bit fixed point: (1868 B + 9617 G +
 // 4899 R + 2^13) >> 14), per-frame z-score (numpy mean / population std), then min-max to [0, 1]
-// (zeros when the frame is constant).  Resizing stays on the host (cv2.resize), so H x W here is
-// already the model's input size.
+// (zeros when the frame is constant).  H x W here is already the model's input size; frames at the
+// scanner's size go through frames.hip, which resizes them on the device as well.
 //
 // One 1024-thread workgroup per frame, two passes over the frame's bytes (L2-resident between
 // them): pass 1 reduces sum, sum of squares, min and max of the grey values in integers (exact);

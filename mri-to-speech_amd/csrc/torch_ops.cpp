@@ -15,6 +15,8 @@
 //   hifigan_forward    Generator.forward                               models.py:113-131
 //   pipeline_forward   the no_grad section of main()                   run_mri_video_inference.py:222-242
 //   preprocess_frames  _preprocess_frame after the host decode         run_mri_video_inference.py:34-54
+//   preprocess_frames_resize  the same with cv2.resize on the device, and the training convention
+//                      (INTER_AREA, / 255)                            mri2speech_code/preprocess_rtmri_data.py:99-113
 //   *_ragged           the same forward passes over clips of different lengths, packed (include/m2s.h)
 //   hifigan_forward_chunk  Generator.forward on spans of a stream, emitting the rows that are final (include/m2s.h)
 //   cam_backbone       backbone(x) in train() (batch-statistics BN)    mri_gradcam_formant.py:153-160,221-225
@@ -334,6 +336,22 @@ at::Tensor preprocess_frames(const at::Tensor& frames) {
   return out;
 }
 
+// decoded frames uint8 (T,h,w) grey or (T,h,w,3) BGR at the scanner's size -> (T,out_h,out_w) fp32, resized and
+// normalised on the device (interp: m2s_frame_interp, norm: m2s_frame_norm)
+at::Tensor preprocess_frames_resize(const at::Tensor& frames, int64_t out_h, int64_t out_w, int64_t interp, int64_t norm) {
+  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte, "preprocess_frames_resize: uint8 HIP tensor expected");
+  TORCH_CHECK(frames.dim() == 3 || (frames.dim() == 4 && frames.size(3) == 3), "preprocess_frames_resize: (T,h,w[,3])");
+  TORCH_CHECK(out_h > 0 && out_w > 0 && out_h <= 65536 && out_w <= 65536, "preprocess_frames_resize: bad output size");
+  const Guard g(frames.device());
+  const at::Tensor x = frames.contiguous();
+  const int n = x.size(0), hh = x.size(1), ww = x.size(2), ch = x.dim() == 4 ? 3 : 1;
+  at::Tensor out = at::empty({n, out_h, out_w}, x.options().dtype(at::kFloat));
+  ok(m2s_preprocess_frames_resize(x.data_ptr<uint8_t>(), n, hh, ww, ch, (int)out_h, (int)out_w, (int)interp, (int)norm,
+                                  out.data_ptr<float>(), S()),
+     "preprocess_frames_resize");
+  return out;
+}
+
 m2s_cam* Cm(int64_t h) {
   TORCH_CHECK(h != 0, "null cam handle");
   return reinterpret_cast<m2s_cam*>(h);
@@ -635,6 +653,7 @@ TORCH_LIBRARY(m2s, m) {
         " int n_mels) -> Tensor");
   m.def("hifigan_forward_chunk(int handle, Tensor mel, int[] lengths, int[] context, int[] hold, int hop) -> Tensor");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
+  m.def("preprocess_frames_resize(Tensor frames, int out_h, int out_w, int interp, int norm) -> Tensor");
   m.def("cam_backbone(int handle, Tensor frames) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_backward(Tensor dy, Tensor x, Tensor[] weights, Tensor gates, Tensor cells, Tensor hid)"
@@ -667,6 +686,7 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("acoustic_forward_windowed", &acoustic_forward_windowed);
   m.impl("hifigan_forward_chunk", &hifigan_forward_chunk);
   m.impl("preprocess_frames", &preprocess_frames);
+  m.impl("preprocess_frames_resize", &preprocess_frames_resize);
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);
   m.impl("bilstm_train_backward", &bilstm_train_backward);

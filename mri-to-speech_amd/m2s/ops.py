@@ -32,6 +32,11 @@ WINDOW_MERGES = {"latest": 0, "mean": 1}
 STREAM_OPS = ("hifigan_forward_chunk",)
 # analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
 ANALYSIS_OPS = ("mel_spectrogram",)
+# frame front end: native-size uint8 frames -> resized, normalised fp32 frames (csrc/frames.hip); interp / norm are the
+# values of m2s_frame_interp / m2s_frame_norm (include/m2s.h)
+FRAME_OPS = ("preprocess_frames_resize",)
+FRAME_INTERPS = {"linear": 0, "area": 1}
+FRAME_NORMS = {"zscore": 0, "unit": 1}
 # Grad-CAM engine (m2s/gradcam.py; handle = GradCam.handle): every band and target frame of a clip in one call, and
 # its stages (include/m2s.h "Grad-CAM engine")
 GRADCAM_OPS = ("gradcam", "gradcam_cotangents", "bilstm_train_backward_multi", "cam_heatmap")
@@ -183,6 +188,10 @@ def _register_fakes():
     @f("m2s::preprocess_frames")
     def _pre(frames):
         return frames.new_empty(tuple(frames.shape[:3]), dtype=torch.float32)
+
+    @f("m2s::preprocess_frames_resize")
+    def _pre_resize(frames, out_h, out_w, interp, norm):
+        return frames.new_empty((frames.shape[0], out_h, out_w), dtype=torch.float32)
 
     @f("m2s::cam_backbone")
     def _cam(handle, frames):

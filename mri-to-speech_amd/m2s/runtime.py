@@ -269,16 +269,31 @@ def mel_glue(mel_norm: torch.Tensor, mean: torch.Tensor, std: torch.Tensor):
                                 torch.as_tensor(std).to(d))
 
 
-def preprocess_frames(frames: torch.Tensor) -> torch.Tensor:
-    """Decoded uint8 frames on the device, (T,H,W) grey or (T,H,W,3) BGR -> (T,H,W) fp32 in [0, 1]
-    (_preprocess_frame, run_mri_video_inference.py:34-54; resizing stays on the host)."""
+def preprocess_frames(frames: torch.Tensor, size=None, interp: str = "linear", norm: str = "zscore") -> torch.Tensor:
+    """Decoded uint8 frames on the device, (T,h,w) grey or (T,h,w,3) BGR -> (T,H,W) fp32 in [0, 1].
+
+    ``size=None`` with the defaults: the frames already have the model's size and get _preprocess_frame's
+    normalisation (run_mri_video_inference.py:34-54; ``torch.ops.m2s.preprocess_frames``).  Otherwise the frames
+    are at the scanner's size and ``torch.ops.m2s.preprocess_frames_resize`` resizes them to ``size`` = (H, W)
+    (default: their own size) on the device as ``cv2.resize`` would (``interp`` "linear" = INTER_LINEAR, "area" =
+    INTER_AREA; no axis may shrink, at most 65536 pixels a frame) and normalises them (``norm`` "zscore" = per-frame
+    z-score + min-max, "unit" = / 255).  ("linear", "zscore") is the reference's inference convention, ("area",
+    "unit") its training convention (mri2speech_code/preprocess_rtmri_data.py:99-113)."""
     if frames.dtype != torch.uint8:
         raise N.M2SError(f"expected uint8 frames, got {frames.dtype}")
     if frames.device.type != "cuda":
         raise N.M2SError("preprocess_frames runs on the HIP device; move the decoded frames there first")
     if not (frames.dim() == 3 or (frames.dim() == 4 and frames.shape[-1] == 3)):
         raise N.M2SError(f"expected (T,H,W) or (T,H,W,3) frames, got {tuple(frames.shape)}")
-    return _ops.load().preprocess_frames(frames.contiguous())
+    if interp not in _ops.FRAME_INTERPS:
+        raise N.M2SError(f"interp {interp!r} is none of {sorted(_ops.FRAME_INTERPS)}")
+    if norm not in _ops.FRAME_NORMS:
+        raise N.M2SError(f"norm {norm!r} is none of {sorted(_ops.FRAME_NORMS)}")
+    if size is None and interp == "linear" and norm == "zscore":
+        return _ops.load().preprocess_frames(frames.contiguous())
+    out_h, out_w = (int(frames.shape[1]), int(frames.shape[2])) if size is None else (int(size[0]), int(size[1]))
+    return _ops.load().preprocess_frames_resize(frames.contiguous(), out_h, out_w, _ops.FRAME_INTERPS[interp],
+                                                _ops.FRAME_NORMS[norm])
 
 
 class Pipeline:

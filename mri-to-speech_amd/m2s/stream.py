@@ -1,6 +1,7 @@
 """Streaming inference: frames in, mel rows and audio out while the clip is still arriving.
 
-* ``AcousticStream``  frames -> the mel rows of exactly those frames (the windowed engine call)
+* ``AcousticStream``  frames -> the mel rows of exactly those frames (the windowed engine call); uint8 frames at the
+                      scanner's size are resized and normalised on the device first (csrc/frames.hip)
 * ``VocoderStream``   mel rows -> the audio of the rows that have become final (the chunk call)
 * ``push_all``        several ``VocoderStream``s through one engine call
 * ``SpeechStream``    the two chained through the mel glue: frames -> mel rows of the pushed frames + audio
@@ -29,10 +30,11 @@ class AcousticStream:
     """``engine``: an ``m2s.runtime.AcousticEngine`` (anything with ``effnet(frames) -> (n, F)`` and
     ``bilstm_windowed(feats, lengths, window, merge, context) -> (y, mel_norm)``)."""
 
-    def __init__(self, engine, window: int = 4):
+    def __init__(self, engine, window: int = 4, size=(256, 256), interp: str = "linear", norm: str = "zscore"):
         if not 1 <= int(window) <= 16:
             raise ValueError(f"window = {window} outside 1..16")
         self.engine, self.window = engine, int(window)
+        self.size, self.interp, self.norm = (int(size[0]), int(size[1])), interp, norm  # the uint8 front end
         self._tail = None  # the last <= window - 1 feature rows of the stream so far
 
     def reset(self) -> None:
@@ -46,7 +48,12 @@ class AcousticStream:
 
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         """frames (n,[1,]H,W) fp32 in [0, 1] on the engine's device, n >= 1 -> mel_norm (n, n_mels) for exactly
-        these frames."""
+        these frames.  uint8 frames, (n,h,w) grey or (n,h,w,3) BGR at the scanner's size, go through the device
+        front end first (``runtime.preprocess_frames`` to the ``size`` (H, W) / ``interp`` / ``norm`` given at
+        construction)."""
+        if frames.dtype == torch.uint8:
+            from .runtime import preprocess_frames
+            frames = preprocess_frames(frames, self.size, self.interp, self.norm)
         if frames.dim() == 4:
             frames = frames[:, 0]
         if frames.dim() != 3 or frames.shape[0] < 1:
@@ -152,9 +159,9 @@ class SpeechStream:
     stream), so a clip streamed in any chunking gives ``Pipeline.forward_windowed``'s mel rows bit for bit and its
     waveform to rounding."""
 
-    def __init__(self, pipeline, window: int = 4):
+    def __init__(self, pipeline, window: int = 4, size=(256, 256), interp: str = "linear", norm: str = "zscore"):
         self.pipeline = pipeline
-        self.acoustic = AcousticStream(pipeline.ac, window)
+        self.acoustic = AcousticStream(pipeline.ac, window, size, interp, norm)
         self.vocoder = VocoderStream(pipeline.voc)
 
     def reset(self) -> None:
@@ -162,8 +169,9 @@ class SpeechStream:
         self.vocoder.reset()
 
     def push(self, frames: torch.Tensor):
-        """frames (n,[1,]H,W) -> dict: mel_norm / mel_db / mel_log (n, n_mels) of the pushed frames, wav = the
-        samples of the rows that became final (``VocoderStream.push``)."""
+        """frames (n,[1,]H,W) fp32, or uint8 (n,h,w[,3]) at the scanner's size (``AcousticStream.push``) -> dict:
+        mel_norm / mel_db / mel_log (n, n_mels) of the pushed frames, wav = the samples of the rows that became
+        final (``VocoderStream.push``)."""
         from .runtime import mel_glue
         mn = self.acoustic.push(frames)
         db, ln = mel_glue(mn, self.pipeline.mean, self.pipeline.std)

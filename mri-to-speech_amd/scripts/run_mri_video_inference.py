@@ -15,6 +15,11 @@ How it runs (this is not the reference's control flow):
   (T,H,W[,3]) uint8 stack), stages each chunk in pinned host memory, copies it on a side HIP stream
   and normalises it there (``torch.ops.m2s.preprocess_frames``: BGR -> grey, per-frame z-score +
   min-max, :34-54), so chunk k+1 decodes while chunk k crosses PCIe and normalises.
+* Frames smaller than the model's 256 x 256 (scanners deliver 68 x 68, 84 x 84, 104 x 68) are resized by OpenCV on
+  the host, as the reference does, when OpenCV is installed.  Without OpenCV, or with ``--device-resize``, they are
+  uploaded at their own size and resized on the device (``torch.ops.m2s.preprocess_frames_resize``, the same
+  fixed-point rule as ``cv2.resize``).  ``--frame-interp area`` / ``--frame-norm unit`` (additive) present the frames
+  in the training convention (mri2speech_code/preprocess_rtmri_data.py:99-113) and always take the device path.
 * ``run`` hands the whole clip to ONE ``torch.ops.m2s.pipeline_forward`` call when both loaded
   modules are the m2s plug-ins: CNN -> BiLSTM -> head -> de-normalise -> dB -> ln -> generator stay on
   the device, with no host round trip between the mel and the waveform.  Any other plug-in module
@@ -57,11 +62,18 @@ TARGET = (256, 256)
 class FrameStream:
     """Chunked decode (worker thread) -> pinned staging -> H2D + device normalisation (side stream)."""
 
-    def __init__(self, path: Path, device: torch.device, max_frames=None, chunk: int = 64, target=TARGET):
+    def __init__(self, path: Path, device: torch.device, max_frames=None, chunk: int = 64, target=TARGET,
+                 device_resize: bool = False, interp: str = "linear", norm: str = "zscore"):
         self.path, self.device, self.max_frames, self.chunk, self.target = Path(path), device, max_frames, chunk, target
+        if interp not in ("linear", "area") or norm not in ("zscore", "unit"):
+            raise ValueError(f"unknown frame convention ({interp}, {norm})")
+        self.interp, self.norm = interp, norm
+        # frames no larger than the target are resized on the device; "area" / "unit" exist only there
+        self.device_resize = bool(device_resize) or cv2 is None or (interp, norm) != ("linear", "zscore")
 
     def _host_chunks(self):
-        """uint8 frame arrays at the target size, `chunk` frames at a time."""
+        """uint8 frame arrays, `chunk` frames at a time: at the target size, or at their own (smaller) size where
+        the device resizes them."""
         limit = self.max_frames if self.max_frames is not None else 1 << 62
         if self.path.suffix.lower() == ".npy":
             stack = np.load(self.path, mmap_mode="r", allow_pickle=False)
@@ -95,10 +107,19 @@ class FrameStream:
             raise ValueError(f"expected 8-bit frames, got {f.dtype}")
         if f.shape[:2][::-1] == tuple(self.target):
             return f
+        if self.device_resize and f.shape[1] <= self.target[0] and f.shape[0] <= self.target[1]:
+            return f  # native size: the front end kernel greys, resizes and normalises it
         if cv2 is None:
             raise ValueError(f"frame of size {f.shape[:2]} needs a resize to {self.target} and OpenCV is missing")
         g = cv2.cvtColor(f, cv2.COLOR_BGR2GRAY) if f.ndim == 3 else f  # the reference resizes the grey frame
-        return cv2.resize(g, self.target, interpolation=cv2.INTER_LINEAR)
+        return cv2.resize(g, self.target, interpolation=cv2.INTER_AREA if self.interp == "area" else cv2.INTER_LINEAR)
+
+    def _to_model_input(self, chunk: torch.Tensor) -> torch.Tensor:
+        """One uint8 device chunk -> (n,H,W) fp32 model input."""
+        size = (self.target[1], self.target[0])  # `target` is (width, height), as cv2.resize takes it
+        if tuple(chunk.shape[1:3]) == size and (self.interp, self.norm) == ("linear", "zscore"):
+            return runtime.preprocess_frames(chunk)
+        return runtime.preprocess_frames(chunk, size, self.interp, self.norm)
 
     def read(self) -> torch.Tensor:
         """All frames as one (T,H,W) fp32 device tensor in [0, 1], on the current stream."""
@@ -125,7 +146,7 @@ class FrameStream:
             if isinstance(item, BaseException):
                 raise item
             with torch.cuda.stream(side):  # the pinned block stays reserved until this copy completes
-                parts.append(runtime.preprocess_frames(item.to(self.device, non_blocking=True)))
+                parts.append(self._to_model_input(item.to(self.device, non_blocking=True)))
         torch.cuda.current_stream(self.device).wait_stream(side)
         if not parts:
             raise ValueError(f"no frames could be read from {self.path}")
@@ -134,9 +155,11 @@ class FrameStream:
         return parts[0] if len(parts) == 1 else torch.cat(parts)
 
 
-def load_video_frames(video_path: Path, target_size=TARGET, max_frames=None) -> torch.Tensor:
+def load_video_frames(video_path: Path, target_size=TARGET, max_frames=None, device_resize: bool = False,
+                      interp: str = "linear", norm: str = "zscore") -> torch.Tensor:
     """(T,H,W) fp32 frames in [0, 1] on the host (the Grad-CAM tool moves them itself)."""
-    return FrameStream(Path(video_path), torch.device("cuda"), max_frames, target=target_size).read().cpu()
+    return FrameStream(Path(video_path), torch.device("cuda"), max_frames, target=target_size,
+                       device_resize=device_resize, interp=interp, norm=norm).read().cpu()
 
 
 def frames_to_tensor(frames: torch.Tensor, use_channel: bool = True) -> torch.Tensor:
@@ -272,6 +295,16 @@ def parse_args(argv=None):
                    help="push the clip through the streaming path N frames at a time (m2s.stream.SpeechStream: mel "
                         "rows per push, audio once a row's 7 successors exist); implies --window (default 4), since the "
                         "whole-clip BiLSTM cannot stream; same output files; default 0: one call over the clip")
+    p.add_argument("--device-resize", action="store_true",
+                   help="upload frames no larger than 256x256 at their own size and resize them on the device (the "
+                        "same fixed-point rule as cv2.resize); always so where OpenCV is missing; default: cv2.resize "
+                        "on the host, as the reference")
+    p.add_argument("--frame-interp", choices=["linear", "area"], default="linear",
+                   help="resize interpolation: linear (cv2.INTER_LINEAR, the reference's inference convention) or area "
+                        "(cv2.INTER_AREA, its training convention; implies the device path)")
+    p.add_argument("--frame-norm", choices=["zscore", "unit"], default="zscore",
+                   help="frame normalisation: zscore (per-frame z-score + min-max, the reference's inference "
+                        "convention) or unit (/ 255, its training convention; implies the device path)")
     args = p.parse_args(argv)
     if args.stream < 0:
         p.error("--stream must be >= 1 frames per push")
@@ -298,7 +331,8 @@ def main(argv=None):
 
     model = build_mri_model(args, device)
     gen, h = load_hifigan(Path(args.hifigan_config), Path(args.hifigan_checkpoint), device, args.dtype)
-    frames = FrameStream(video, device, args.max_frames, chunk=args.decode_chunk).read()
+    frames = FrameStream(video, device, args.max_frames, chunk=args.decode_chunk, device_resize=args.device_resize,
+                         interp=args.frame_interp, norm=args.frame_norm).read()
     res = run(model, gen, frames, mean, std, args.window, args.window_merge, args.stream)
     paths = write_outputs(res, Path(args.output_dir), video.stem, int(h.sampling_rate))
     print(f"[m2s] {frames.shape[0]} frames -> mel {res['mel_db'].shape} -> {res['audio'].shape[0]} samples "
