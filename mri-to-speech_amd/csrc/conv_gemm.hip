@@ -152,7 +152,10 @@ __device__ __forceinline__ int swz(int row, int chunk) { return row * ROW + ((ch
 // each K step DMAs both halves into two planes of the slot and runs the three MFMA terms
 // hi*hi + hi*lo + lo*hi (the dropped lo*lo term is below 2^-16 of the product).
 // SP = 2: e4m3 operands over bf16 storage (conv_igemm.hpp launch_conv_gemm, a.wscale).
-template <int BM, int BN, int MT, int NT, int S, int KIND, int XF, int SP>
+// EP = 1 (split 128 x 128 2-D conv, launch_conv_gemm_er: the stride-2 EdgeResidual block): the tile's BN mid channels
+// go through bias + SiLU + split4 into LDS instead of memory, and the block's 1x1 conv_pwl (ab.a[1]: w, bias, y,
+// cs_out <= 64, kp = BN) runs on them as an epilogue GEMM; only its output is stored.
+template <int BM, int BN, int MT, int NT, int S, int KIND, int XF, int SP, int EP = 0>
 __global__ void __launch_bounds__(256, (BN >= 256 || (BM >= 256 && BN >= 128) ? 2 : 1)) conv_gemm_kernel(const ConvBatch ab, int n_tiles, int se_imgs,
                                                                                                       float* __restrict__ kpart) {
   // KIND_CONV1D launches may batch convs of one shape over grid.z (launch_conv_gemm_batch)
@@ -540,6 +543,98 @@ __global__ void __launch_bounds__(256, (BN >= 256 || (BM >= 256 && BN >= 128) ? 
     return;
   }
 
+  if constexpr (EP == 1) {
+    // ---- fused conv_pwl (EdgeResidual): the mid tile never leaves the CU ------------------------------
+    // After the K loop the ring is idle: the tile's bias + SiLU + split4 values (what the unfused launch stores)
+    // go into it as four K-step planes [kk][hi | lo][BM rows of 64 B], swizzled like the ring's rows, and
+    // conv_pwl reads from them the fragments a KIND_GEMM launch would DMA from the stored map.  Same k-steps,
+    // same three terms in the same order, so the block's output equals the two launches' bit for bit.
+    static_assert(KIND == KIND_CONV2D && SP == 1 && XF == IN_NONE && BM == 128 && BN == 128 && MT == 4 && NT == 4,
+                  "the fused conv_pwl epilogue is built for the split 128 x 128 2-D tile");
+    static_assert((BN / 32) * 2 * BM * ROW <= S * SLOT, "the mid tile fits the ring");
+    constexpr int KS2 = BN / 32, NT2 = 2;  // conv_pwl: K = BN mid channels, 64 outputs over the WN = 2 wave columns
+    const bf16_t* __restrict__ W2 = static_cast<const bf16_t*>(ab.a[1].w);  // rows [hi kp | lo kp], kp = BN
+    const float* __restrict__ bias2 = ab.a[1].bias;
+    bf16_t* __restrict__ Y2 = static_cast<bf16_t*>(ab.a[1].y);
+    const int cs2 = ab.a[1].cs_out;
+    // the lane's weight fragments come straight from L2 (32 KB in all), one K step ahead of their MFMAs: the first
+    // step's are in flight while the mid tile is activated (all four at once cost 64 registers and, with the main
+    // loop's, the second workgroup per CU)
+    bf16x8 wh[2][NT2], wl[2][NT2];
+    auto load_w2 = [&](int kk) {
+#pragma unroll
+      for (int ni = 0; ni < NT2; ++ni) {
+        const bf16_t* p = W2 + (size_t)(wn * NT2 * 16 + ni * 16 + r16) * (2 * BN) + kk * 32 + g * 8;
+        wh[kk & 1][ni] = *reinterpret_cast<const bf16x8*>(p);
+        wl[kk & 1][ni] = *reinterpret_cast<const bf16x8*>(p + BN);
+      }
+    };
+    load_w2(0);
+    __syncthreads();  // every wave has read its last K step: the ring is free
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi)
+#pragma unroll
+      for (int ni = 0; ni < NT; ++ni) {
+        const int row = wm * MT * 16 + mi * 16 + r16, n4 = wn * NT * 16 + ni * 16 + 4 * g;
+        const float4 bb = *reinterpret_cast<const float4*>(a.bias + n4);
+        float v[4] = {acc[ni][mi][0] + bb.x, acc[ni][mi][1] + bb.y, acc[ni][mi][2] + bb.z, acc[ni][mi][3] + bb.w};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = silu(v[j]);
+        // the rounded product, as the unfused epilogue splits it: side by side in one block, SiLU's last multiply
+        // and split4's v - hi would contract into fma(x, 1 / (1 + e), -hi), a lo half off by the product's rounding
+        asm volatile("" : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]));
+        uint2 hi, lo;
+        split4(v, hi, lo);
+        // channel n4 = K step n4 / 32, 16-byte chunk (n4 % 32) / 8, its first or second 8 bytes
+        char* d = smem + (n4 >> 5) * 2 * BM * ROW + swz(row, (n4 >> 3) & 3) + (n4 & 4) * 2;
+        *reinterpret_cast<uint2*>(d) = hi;
+        *reinterpret_cast<uint2*>(d + BM * ROW) = lo;
+      }
+    __syncthreads();
+    f32x4 acc2[NT2][MT];
+#pragma unroll
+    for (int ni = 0; ni < NT2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MT; ++mi) acc2[ni][mi] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int kk = 0; kk < KS2; ++kk) {
+      const char* P = smem + kk * 2 * BM * ROW;
+      if (kk + 1 < KS2) load_w2(kk + 1);
+      bf16x8 bx[MT], bxl[MT];
+#pragma unroll
+      for (int mi = 0; mi < MT; ++mi) {
+        bx[mi] = *reinterpret_cast<const bf16x8*>(P + swz(wm * MT * 16 + mi * 16 + r16, g));
+        bxl[mi] = *reinterpret_cast<const bf16x8*>(P + BM * ROW + swz(wm * MT * 16 + mi * 16 + r16, g));
+      }
+#pragma unroll
+      for (int ni = 0; ni < NT2; ++ni)
+#pragma unroll
+        for (int mi = 0; mi < MT; ++mi) {
+          acc2[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wl[kk & 1][ni], bx[mi], acc2[ni][mi], 0, 0, 0);
+          acc2[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[kk & 1][ni], bxl[mi], acc2[ni][mi], 0, 0, 0);
+          acc2[ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wh[kk & 1][ni], bx[mi], acc2[ni][mi], 0, 0, 0);
+        }
+    }
+#pragma unroll
+    for (int mi = 0; mi < MT; ++mi) {
+      const int m = m0 + wm * MT * 16 + mi * 16 + r16;
+      if (m >= a.M) continue;
+#pragma unroll
+      for (int ni = 0; ni < NT2; ++ni) {
+        const int n4 = wn * NT2 * 16 + ni * 16 + 4 * g;
+        if (n4 >= cs2) continue;
+        const float4 bb = *reinterpret_cast<const float4*>(bias2 + n4);
+        const float v[4] = {acc2[ni][mi][0] + bb.x, acc2[ni][mi][1] + bb.y, acc2[ni][mi][2] + bb.z, acc2[ni][mi][3] + bb.w};
+        uint2 hi, lo;
+        split4(v, hi, lo);
+        bf16_t* yo = Y2 + (size_t)m * cs2 * 2 + n4;
+        *reinterpret_cast<uint2*>(yo) = hi;
+        *reinterpret_cast<uint2*>(yo + cs2) = lo;
+      }
+    }
+    return;
+  }
+
   // ---- epilogue: 4 consecutive channels of one position per lane ------------------------------
   bf16_t* __restrict__ Y = static_cast<bf16_t*>(a.y);
   const bf16_t* __restrict__ Rs = static_cast<const bf16_t*>(a.res);
@@ -781,6 +876,27 @@ const char* kname(int k) {
 // rows of SE gates a tile needs: the images its BM rows touch
 inline int se_images(int BM, int OH) { return BM % OH == 0 ? BM / OH : OH % BM == 0 ? 1 : (BM + OH - 1) / OH + 1; }
 
+// Split K where the tiles fill under half a round of the chip's workgroup slots (one clip, the 8 x 4 acoustic
+// batch: a few dozen tiles walking 20..88 K steps each): nks K ranges of >= 4 steps, up to a full round and at
+// most 8 (the partial sums' round trip grows with nks: same-box A/B at one clip / configs[1], M2S_KSPLIT_MAX 4 / 8
+// / 16: 2.378 / 2.286 / 2.300 ms and 1.106 / 1.107 / 1.119 ms, gpurun_out/r06d/ab.txt).
+// M2S_KSPLIT=n forces n ranges (A/B, tests; 1 = never split).
+// tiles: workgroups of the unsplit launch; nst: its K steps; lds: bytes per workgroup.
+int plan_ksplit(int tiles, int nst, size_t lds) {
+  const int slots = device_cus() * std::max(1, std::min(2, (int)(160 * 1024 / lds)));
+  const char* fe = getenv("M2S_KSPLIT");  // read per launch: tests switch it between engines of one process
+  const int force = fe ? atoi(fe) : 0;
+  int nks = 1;
+  if (force > 0)
+    nks = std::min(force, std::max(1, nst));
+  else if (2 * tiles <= slots && nst >= 8) {
+    const char* mx = getenv("M2S_KSPLIT_MAX");  // A/B of the split count (tools/ab_env.py)
+    const char* ms = getenv("M2S_KSPLIT_MINST");
+    nks = std::max(1, std::min({slots / tiles, nst / (ms ? std::max(1, atoi(ms)) : 4), mx ? std::max(1, atoi(mx)) : 8}));
+  }
+  return nks;
+}
+
 template <int BM, int BN, int MT, int NT, int KIND, int XF, int SP, int SF = 0>
 void launch_tile(const ConvBatch& b, hipStream_t s, int phases, double flops, double bytes) {
   const ConvArgs& a = b.a[0];
@@ -797,25 +913,9 @@ void launch_tile(const ConvBatch& b, hipStream_t s, int phases, double flops, do
   }
   const size_t lds = (size_t)S * (R * (BM + BN) + 16) * ROW + (size_t)se_imgs * a.cs_in * sizeof(float);
   M2S_CHECK(lds <= 160 * 1024, "conv_gemm: LDS budget");
-  // Split K where the tiles fill under half a round of the chip's workgroup slots (one clip, the 8 x 4 acoustic
-  // batch: a few dozen tiles walking 20..88 K steps each): nks K ranges of >= 4 steps, up to a full round and at
-  // most 8 (the partial sums' round trip grows with nks: same-box A/B at one clip / configs[1], M2S_KSPLIT_MAX 4 / 8
-  // / 16: 2.378 / 2.286 / 2.300 ms and 1.106 / 1.107 / 1.119 ms, gpurun_out/r06d/ab.txt).
-  // M2S_KSPLIT=n forces n ranges (A/B, tests; 1 = never split).
   int nst = 0;
   for (int i = 0; i < (KIND == KIND_CONV1D ? phases : 1); ++i) nst = std::max(nst, b.a[i].kp / 32);
-  const int tiles = m_tiles * n_tiles * phases;
-  const int slots = device_cus() * std::max(1, std::min(2, (int)(160 * 1024 / lds)));
-  const char* fe = getenv("M2S_KSPLIT");  // read per launch: tests switch it between engines of one process
-  const int force = fe ? atoi(fe) : 0;
-  int nks = 1;
-  if (force > 0)
-    nks = std::min(force, std::max(1, nst));
-  else if (2 * tiles <= slots && nst >= 8) {
-    const char* mx = getenv("M2S_KSPLIT_MAX");  // A/B of the split count (tools/ab_env.py)
-    const char* ms = getenv("M2S_KSPLIT_MINST");
-    nks = std::max(1, std::min({slots / tiles, nst / (ms ? std::max(1, atoi(ms)) : 4), mx ? std::max(1, atoi(mx)) : 8}));
-  }
+  int nks = plan_ksplit(m_tiles * n_tiles * phases, nst, lds);
   const size_t part_bytes = (size_t)phases * nks * a.M * a.cs_out * sizeof(float);
   if (nks > 1 && part_bytes > ((size_t)256 << 20)) nks = 1;
   float* kpart = nks > 1 ? ksplit_scratch(s, part_bytes) : nullptr;
@@ -936,6 +1036,39 @@ void launch_conv_gemm_batch(const ConvArgs* as, int n, hipStream_t s, double flo
   }
   if (a.M <= 0) return;
   launch_kind<KIND_CONV1D, 1>(a, s, n, flops, bytes, &b);
+  M2S_HIP(hipGetLastError());
+}
+
+namespace {
+constexpr int ER_BM = 128, ER_BN = 128, ER_S = 2;  // launch_kind_xf's tile and launch_tile's stages for this conv
+constexpr size_t ER_LDS = (size_t)ER_S * (2 * (ER_BM + ER_BN) + 16) * ROW;
+}  // namespace
+
+bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q) {
+  const bool exp_ok = e.kind == KIND_CONV2D && e.ks == 3 && e.ntaps == 9 && e.cs_in >= 32 && e.cs_in % 32 == 0 &&
+                      e.kp % 32 == 0 && e.kp >= 9 * e.cs_in && e.cs_out == ER_BN && e.n_pad >= ER_BN && e.act == ACT_SILU &&
+                      !e.res && !e.accum && e.in_xform == IN_NONE && !e.wscale && e.M > 0 && e.OH > 0 && e.OW > 0 &&
+                      (double)(e.M / (e.OH * e.OW)) * e.IH * e.IW * e.cs_in * 2 < 2147483647.0;
+  const bool pwl_ok = q.kind == KIND_GEMM && q.cs_in == ER_BN && q.kp == ER_BN && q.cs_out % 4 == 0 && q.cs_out <= 64 &&
+                      q.n_pad >= 64 && q.act == ACT_NONE && !q.res && !q.accum && q.in_xform == IN_NONE && !q.wscale &&
+                      q.M == e.M;
+  // only where conv_gemm would run conv_exp unsplit: a split-K launch leaves partial sums, not the mid tile
+  return exp_ok && pwl_ok && plan_ksplit(ceil_div(e.M, ER_BM), e.kp / 32, ER_LDS) == 1;
+}
+
+void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, hipStream_t s, double flops, double bytes) {
+  M2S_CHECK(conv_gemm_er_supported(e, q), "conv_gemm_er: unsupported block");
+  M2S_CHECK(e.x && e.w && e.bias && q.w && q.bias && q.y && q.y != e.x, "conv_gemm_er: operand pointers");
+  ConvBatch b;
+  std::memset(&b, 0, sizeof(b));
+  b.a[0] = e;
+  b.a[1] = q;
+  auto* fn = &conv_gemm_kernel<ER_BM, ER_BN, 4, 4, ER_S, KIND_CONV2D, IN_NONE, 1, 1>;
+  allow_lds(reinterpret_cast<const void*>(fn));
+  char name[96];  // the instance's name: the roofline's MFMA aggregate matches kernels by prefix
+  snprintf(name, sizeof(name), "conv_gemm_kernel<%d, %d, 4, 4, %d, %d, %d, 1, 1>", ER_BM, ER_BN, ER_S, KIND_CONV2D, IN_NONE);
+  ProfScope ps(name, flops, bytes, s);
+  hipLaunchKernelGGL(fn, dim3(ceil_div(e.M, ER_BM), 1, 1), dim3(256), ER_LDS, s, b, 1, 0, static_cast<float*>(nullptr));
   M2S_HIP(hipGetLastError());
 }
 

@@ -74,6 +74,14 @@ void launch_conv(const ConvArgs& a, hipStream_t s, double flops = 0.0, double by
 // w / wscale[n], the activation fragments are rounded to e4m3 after the LDS read, the products run
 // on v_mfma_f32_16x16x32_fp8_fp8 and the epilogue multiplies by wscale[n].
 void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops, double bytes);
+// Split-fp32 stride-2 EdgeResidual block (blocks.2.0: 32 -> 128 -> 56 channels) in one launch: `e` is the 3x3
+// conv_exp (+ bn1 + SiLU) exactly as launch_conv_gemm would take it (e.y unused), `q` the 1x1 conv_pwl (+ bn2) as
+// a KIND_GEMM conv (q.x unused).  The 128 x 128 conv_exp tile's SiLU'd, split mid channels stay in LDS and conv_pwl
+// runs on them as an epilogue GEMM: the same MFMAs in the same order as the two launches, without the mid map's
+// round trip through memory.  Supported where conv_exp would run unsplit (no split K: M2S_KSPLIT, small grids) on
+// 128 mid channels with at most 64 (padded) outputs; callers fall back to the two launches otherwise.
+bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q);
+void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, hipStream_t s, double flops, double bytes);
 // n (1..CONV_BATCH) split-fp32 KIND_CONV1D convs of one shape in one launch; put the longest K first
 // (blocks dispatch in z order, so the longest tiles start first and the short ones fill the tail).
 void launch_conv_gemm_batch(const ConvArgs* a, int n, hipStream_t s, double flops, double bytes);

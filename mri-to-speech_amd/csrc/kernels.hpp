@@ -81,9 +81,11 @@ bool se_ws_supported(int P, int cs_in, int cs_out);
 // Every FULL / FREE wait is bounded by rep.spin_max polls; a timeout is reported through rep.err and the
 // consumer's tiles from then on are stored as NaN.
 // x_f32: x holds plain fp32 rows [M][cs_in] (ir_ws's fm32 output) instead of the interleaved split layout.
+// rev: the workgroups walk their tiles from the last row tile down (the rows a forward-walking producer wrote last
+// are read first); every tile's result is independent of the order.
 void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias, const void* gate,
                   const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes, AsyncReport rep = {},
-                  bool x_f32 = false);
+                  bool x_f32 = false, bool rev = false);
 
 // fp8 engines: launch_se_gemm_f8's operation (e4m3 x8 / w8, bf16 gate / res / y) on the same warp-specialised
 // flag ring.  (se_ws.hip)

@@ -48,7 +48,8 @@ Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int d
            {"M2S_F8_ER2", &f8_er2_},       {"M2S_SE_Y8", &se_y8_},         {"M2S_SE_FUSED", &se_fused_},
            {"M2S_ER_FUSED", &er_fused_},   {"M2S_SE_WS", &se_ws_},         {"M2S_LSTM_PERSISTENT", &lstm_persistent_},
            {"M2S_LSTM_MID", &lstm_mid_},   {"M2S_LSTM_X3", &lstm_x3_},     {"M2S_LSTM_X3G", &lstm_x3g_},
-           {"M2S_SE_SP", &se_sp_},         {"M2S_ER_MRG", &er_mrg_},       {"M2S_IR_S2BAND", &ir_s2band_}})
+           {"M2S_SE_SP", &se_sp_},         {"M2S_ER_MRG", &er_mrg_},       {"M2S_IR_S2BAND", &ir_s2band_},
+           {"M2S_ER_S2_FUSED", &er_s2_fused_}, {"M2S_SEWS_REV", &sews_rev_}})
     env_flag(name, *v);
   env_int("M2S_IRWS_MIN", irws_min_);
   env_int("M2S_SEWS_MIN", sews_min_cus_);
@@ -250,13 +251,20 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
   } else {
     ConvArgs a = conv2d_args(p, b.c1, cur, M);
     a.act = ACT_SILU;
-    run_conv<T>(a, b.c1, s);
     ConvArgs q = conv_args(b.c2);
     q.x = M;
     q.y = nxt;
     q.M = nc * nh * nw;
     q.OH = nh * nw;
     q.res = b.skip ? cur : nullptr;
+    if (std::is_same<T, sp_t>::value && er_s2_fused_ && b.stride == 2 && conv_gemm_er_supported(a, q)) {
+      // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the expanded map stays in LDS (M is not touched);
+      // compulsory bytes = the block's input and output maps and both convs' weights
+      launch_conv_gemm_er(a, q, s, 2.0 * px * b.mid * (9.0 * b.cin + b.cout),
+                          4.0 * ((double)nc * oh * ow * b.cin + px * b.cout + (9.0 * b.cin + b.cout) * b.mid));
+      return;
+    }
+    run_conv<T>(a, b.c1, s);
     run_conv<T>(q, b.c2, s);
   }
 }
@@ -425,7 +433,7 @@ void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
     launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,
                  chan_stride(b.cout), s, 2.0 * rows * b.mid * b.cout,
                  4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
-                 ws_report(), mid_f32);
+                 ws_report(), mid_f32, sews_rev_);
   } else if (SPL && se_sp_ && se_gemm_sp_supported(nh * nw, cs, chan_stride(b.cout))) {
     const double rows = (double)nc * nh * nw, co = chan_stride(b.cout);
     launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, b.skip ? cur : nullptr, nxt,

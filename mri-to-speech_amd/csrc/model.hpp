@@ -285,6 +285,11 @@ class Acoustic {
   bool er_mrg_ = true;      // split EdgeResidual blocks.1: merged W_hi / W_lo ring stages (env M2S_ER_MRG=0: one per
                             // slot; 2088 vs 2164 us per launch, gpurun_out r03er)
   bool ir_s2band_ = true;   // blocks.3.0: fused banded conv_pw + stride-2 depthwise (env M2S_IR_S2BAND=0: unfused)
+  bool er_s2_fused_ = true;  // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the 128-channel map stays in LDS
+                             // (conv_gemm.hip EP = 1; env M2S_ER_S2_FUSED=0: the two conv_gemm launches)
+  bool sews_rev_ = true;     // se_ws walks its tiles newest-first, behind ir_ws's forward walk: the end of the expanded
+                             // map is still in the Infinity Cache (env M2S_SEWS_REV=0: forward; bit-identical results;
+                             // 6.83 -> 6.58 ms of se_ws per 1920 frames)
   bool lstm_persistent_ = true;  // one-launch BiLSTM recurrence (env M2S_LSTM_PERSISTENT=0: a launch per step)
   bool lstm_mid_ = true;         // 4 < B <= 16: granule-exchange recurrence (env M2S_LSTM_MID=0: counter barrier)
   bool lstm_x3_ = true;          // B > 4, non-fp32 engines: split-bf16 MFMA recurrence (env M2S_LSTM_X3=0: lstm_mid / f32)

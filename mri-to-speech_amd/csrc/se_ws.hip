@@ -110,7 +110,12 @@ __device__ __forceinline__ int gate4_f8(int d, const float* s) {
 // a K step's 32 channels are still one 128-byte row, a fragment's 8 channels its chunks 2g, 2g + 1 (the e4m3 rows'
 // swizzle), and the gating multiplies the fp32 value before the one split -- no hi + lo sum, and ir_ws's consumers
 // store one 16-byte vector per 4 channels instead of splitting them.
-template <int WM, int WN, int NT, int NL, int NS, int IF, bool F8, bool XF = false>
+// REV: a workgroup walks its tiles from the far end, tile = n_tiles_m - 1 - (blockIdx.x + it * gridDim.x): the rows the
+// producer (ir_ws, walking forward) wrote last are read first, while the Infinity Cache may still hold them.  Every
+// workgroup keeps its tile count and, the half tiles being the last 2 rem <= gridDim.x indices either way, its one
+// half tile at most: the same rows per workgroup as the forward walk.  (A template flag, not an argument: the
+// 16 x 16 variants sit at the register limit, and one more live scalar moved their spills.)
+template <int WM, int WN, int NT, int NL, int NS, int IF, bool REV, bool F8, bool XF = false>
 __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeWsArgs a) {
   static_assert(!(F8 && XF), "fp32 activations: split engine");
   constexpr int NC = WM * WN;                       // consumer waves
@@ -139,6 +144,10 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
     m0 = tile < a.full_tiles ? tile * BM : a.full_tiles * BM + (tile - a.full_tiles) * (BM / 2);
     mend = min(m0 + (tile < a.full_tiles ? BM : BM / 2), a.M);
   };
+  auto walk = [&](int it) -> int {  // the workgroup's it-th tile
+    const int t = blockIdx.x + it * gridDim.x;
+    return REV ? n_tiles - 1 - t : t;
+  };
 
   if (tid <= 2 * NS) flags[tid] = 0u;  // FULL, FREE and the loaders' poison word
   __syncthreads();  // the only workgroup barrier
@@ -154,7 +163,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
     const int wrow_b = F8 ? a.kp : a.cs_in * 4, wlo = a.cs_in * 2, xrow_b = F8 ? a.cs_in : a.cs_in * 4;
     int s = 0;
     for (int it = 0; it < my_tiles; ++it) {
-      const int tile = blockIdx.x + it * gridDim.x;
+      const int tile = walk(it);
       int m0, mend;
       tile_rows(tile, m0, mend);
       const uint8_t* xt = a.x + (size_t)m0 * xrow_b;
@@ -231,7 +240,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
   bool bad = false;  // a FULL wait (or a loader's FREE wait) timed out: this wave's tiles are stored as NaN from then on
   int s = 0;
   for (int it = 0; it < my_tiles; ++it) {
-    const int tile = blockIdx.x + it * gridDim.x;
+    const int tile = walk(it);
     int m0, mend;
     tile_rows(tile, m0, mend);
     // a half tile's upper waves have no rows: they keep the flag protocol (FULL before their FREE, so no wave gets a
@@ -484,11 +493,11 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
   }
 }
 
-template <int WM, int WN, int NT, int NL, int NS, int IF, bool F8 = false, bool XF = false>
+template <int WM, int WN, int NT, int NL, int NS, int IF, bool F8 = false, bool XF = false, bool REV = false>
 void launch_cfg(SeWsArgs& a, hipStream_t s, double flops, double bytes) {
   static_assert(IF <= 3, "tail waits");
   constexpr int BM = 64 * WM, BN = 16 * NT * WN;
-  const void* fn = reinterpret_cast<const void*>(&se_ws_kernel<WM, WN, NT, NL, NS, IF, F8, XF>);
+  const void* fn = reinterpret_cast<const void*>(&se_ws_kernel<WM, WN, NT, NL, NS, IF, REV, F8, XF>);
   allow_lds(fn);
   const int nimg = BM / a.P > 0 ? BM / a.P : 1;
   const int gimg = ((F8 ? a.cs_in * 2 : a.cs_in * 4) + 1023) / 1024 * 1024;
@@ -510,13 +519,15 @@ void launch_cfg(SeWsArgs& a, hipStream_t s, double flops, double bytes) {
   a.n_tiles_m = halve ? full + 2 * rem : tiles;
   const dim3 grid(G);
   char name[72];
-  if (XF)
+  if (REV)  // (the forward instances keep the names of the records made before the order flag)
+    snprintf(name, sizeof(name), "se_ws_kernel<%d, %d, %d, %d, %d, %d, true, false%s>", WM, WN, NT, NL, NS, IF, XF ? ", true" : "");
+  else if (XF)
     snprintf(name, sizeof(name), "se_ws_kernel<%d, %d, %d, %d, %d, %d, false, true>", WM, WN, NT, NL, NS, IF);
   else
     snprintf(name, sizeof(name), "se_ws_kernel<%d, %d, %d, %d, %d, %d, %s>", WM, WN, NT, NL, NS, IF,
              F8 ? "true" : "false");  // rocprof's symbol
   ProfScope ps(name, flops, bytes, s);
-  hipLaunchKernelGGL((se_ws_kernel<WM, WN, NT, NL, NS, IF, F8, XF>), grid, dim3(64 * (WM * WN + NL)), lds, s, a);
+  hipLaunchKernelGGL((se_ws_kernel<WM, WN, NT, NL, NS, IF, REV, F8, XF>), grid, dim3(64 * (WM * WN + NL)), lds, s, a);
   M2S_HIP(hipGetLastError());
 }
 
@@ -528,7 +539,7 @@ bool se_ws_supported(int P, int cs_in, int cs_out) {
 
 void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias, const void* gate,
                   const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes, AsyncReport rep,
-                  bool x_f32) {
+                  bool x_f32, bool rev) {
   M2S_CHECK(se_ws_supported(P, cs_in, cs_out) && M % P == 0 && cs_out % 4 == 0, "se_ws: unsupported shape");
   M2S_CHECK(x && w && bias && gate && y && y != res && y != x, "se_ws: operand pointers");
   M2S_CHECK((double)M * cs_in * 4 < 2147483647.0 * 2, "se_ws: input too large");
@@ -555,10 +566,17 @@ void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_p
   if (x_f32) {  // fp32 activations (ir_ws fm32): the default tiles only
     if (cs_out <= 128) {
       M2S_CHECK(n_pad >= 128, "se_ws: weight rows");
+      if (rev) return launch_cfg<4, 1, 8, 4, 3, 2, false, true, true>(a, s, flops, bytes);
       return launch_cfg<4, 1, 8, 4, 3, 2, false, true>(a, s, flops, bytes);
     }
     M2S_CHECK(n_pad >= 224, "se_ws: weight rows");
+    if (rev) return launch_cfg<2, 2, 7, 4, 3, 2, false, true, true>(a, s, flops, bytes);
     return launch_cfg<2, 2, 7, 4, 3, 2, false, true>(a, s, flops, bytes);
+  }
+  if (rev && cfg == 0) {  // the default tiles, walked newest-first
+    M2S_CHECK(n_pad >= (cs_out <= 128 ? 128 : 224), "se_ws: weight rows");
+    if (cs_out <= 128) return launch_cfg<4, 1, 8, 4, 3, 2, false, false, true>(a, s, flops, bytes);
+    return launch_cfg<2, 2, 7, 4, 3, 2, false, false, true>(a, s, flops, bytes);
   }
   if (cs_out <= 128) {
     M2S_CHECK(n_pad >= 128, "se_ws: weight rows");
