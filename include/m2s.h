@@ -36,6 +36,12 @@
  *                          meldataset.py:57-93, as inference.py:25-26 and train.py:228-252 call it; and
  *                          pre_emphasis + compute_mel_db up to the dB map (the caller supplies the mel basis)
  *                          mri2speech_code/preprocess_rtmri_data.py:37-43,121-147
+ *   m2s_*_pairs         the model on every training pair of a clip: the windows pass3_save_pairs cuts
+ *                          mri2speech_code/preprocess_rtmri_data.py:198-259, as OTNLikeTrainer.validate() feeds them
+ *                          to the model   mri2speech_code/train_mri_acoustic_model.py:349-384
+ *   m2s_mel_metrics     the weighted MaskedMSEMAE criterion and the band MAEs of validate()
+ *                          train_mri_acoustic_model.py:57-167,263-277; eval_mel.py's MaskedMSEMAE, mcd_like and
+ *                          evaluation loop   mri2speech_code/eval_mel.py:19-32,39-82,104-155
  */
 #ifndef M2S_H_
 #define M2S_H_
@@ -123,7 +129,8 @@ int m2s_acoustic_set_ws_spin_limit(m2s_acoustic* m, unsigned polls);
  *     passed the call.  What an engine keeps across calls (the BiLSTM hand-off tags) it owns itself.
  *   - The size a query reports is sufficient, and it is exact to its 256-byte granule for the call the query is named
  *     after (m2s_acoustic_forward, m2s_vocoder_forward, m2s_pipeline_forward, their *_ragged forms,
- *     m2s_cam_backbone, m2s_bilstm_train_backward, m2s_gradcam_forward, m2s_bilstm_train_backward_multi): 256 bytes less is refused with M2S_E_ARG, nothing outside the
+ *     m2s_cam_backbone, m2s_bilstm_train_backward, m2s_gradcam_forward, m2s_bilstm_train_backward_multi,
+ *     m2s_acoustic_forward_pairs, m2s_bilstm_pairs with H = W = 0, m2s_mel_metrics): 256 bytes less is refused with M2S_E_ARG, nothing outside the
  *     caller's buffers is written, and the engine stays usable.  The calls without a query of their own take the
  *     enclosing call's and use a part of it: m2s_effnet_forward / m2s_effnet_probe on N frames that of
  *     m2s_acoustic_workspace_bytes(m, N, 1, H, W); m2s_bilstm_summerge that of (m, B, T, H, W) for any valid frame
@@ -275,6 +282,74 @@ int m2s_bilstm_windowed(m2s_acoustic* m, const float* feats, const int* lengths,
 int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const int* lengths, const int* context, int B,
                                   int rows, int H, int W, int window, int merge, float* mel_norm, void* ws,
                                   size_t ws_bytes, void* stream);
+
+/* -------------------------------------------------------- validation: pair outputs ---- */
+/* The training pairs of the reference (preprocess_rtmri_data.py:198-259) are every window of `window` consecutive
+ * frames of a clip, stride 1.  These ADDITIVE calls give the model's output on every row of every pair, which a
+ * loss over pairs needs (LATEST keeps one row per window, MEAN averages them), with the CNN run once per frame row.
+ * Inputs are packed exactly as in the *_windowed calls.  P = sum(lengths[b] - window + 1); pair p = pbase_b + i is
+ * the window on rows i .. i + window - 1 of clip b, pairs in clip order, windows ascending within a clip (the order
+ * pass3_save_pairs writes them); row s of pair p is M(x_b[i .. i + window - 1])[s], M as defined above.  The route is
+ * MEAN's (same window table, same step launches, every step's h kept); lstm_window_pairs_kernel then writes the
+ * sum-merged rows and the head runs on P * window rows.  Row window - 1 of a pair is bit-identical to LATEST's row
+ * of the same frame.
+ * M2S_E_ARG, before any launch: window outside 1..16, a lengths[b] < window (the reference skips such clips, so the
+ * caller must too), rnn_hidden != 640, and the ragged calls' argument errors.  M2S_E_STATE if `stream` is capturing.
+ * The workspace contract above applies as written. */
+/* Exact size for m2s_acoustic_forward_pairs on (H, W) frames; with H = W = 0 the exact size for m2s_bilstm_pairs
+ * alone.  0 for arguments the calls would reject. */
+size_t m2s_acoustic_pairs_workspace_bytes(const m2s_acoustic* m, const int* lengths, int B, int H, int W, int window);
+/* feats (rows,208) -> y (P,window,rnn_hidden) (may be NULL) and mel_norm (P,window,n_mels) (may be NULL). */
+int m2s_bilstm_pairs(m2s_acoustic* m, const float* feats, const int* lengths, int B, int rows, int window, float* y,
+                     float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+/* frames (rows,H,W) fp32 in [0,1] -> mel_norm (P,window,n_mels). */
+int m2s_acoustic_forward_pairs(m2s_acoustic* m, const float* frames, const int* lengths, int B, int rows, int H, int W,
+                               int window, float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------- validation: fused mel metrics ---- */
+/* The reference's validation numbers of one batch of (B,T,M) predictions in two launches and no host sync
+ * (DESIGN.md §24): the weighted MaskedMSEMAE criterion and band MAEs of OTNLikeTrainer.validate(), eval_mel.py's
+ * masked MSE / MAE and its MCD-like.  pred / target (B,T,M) standardised dB mels, mask (B,T) floats or NULL = ones;
+ * every array argument is device memory except `bands`.
+ * Groups: sequences fall into consecutive groups of `group` sequences (0 or >= B: one group; the last may be
+ * short).  A group is one batch of the reference: every loss is computed per group and summed over the groups, and
+ * GROUPS counts them, so the reference's tot / cnt is a division on the host.
+ * With diff = pred - target, w[b,t,m] = freq_w[m] time_w[t] mask[b,t], sums over one group:
+ *   MSE     sum diff^2 w / max(sum w, 1e-6);  MAE likewise with |diff|
+ *   DELTA   d = diff[t] - diff[t-1], t >= 1, weight freq_w[m] time_w[t] mask[t] mask[t-1] (the LATER row's time
+ *           weight): sum d^2 w / max(sum w, 1e-6); 0 when T = 1
+ *   ACCEL   a = diff[t+1] - 2 diff[t] + diff[t-1], weight freq_w[m] time_w[t] mask[t+1] mask[t] mask[t-1] (the MIDDLE
+ *           row's time weight); 0 when T <= 2
+ *   LATEST  row T - 1, NOT masked, not time-weighted: sum diff^2 freq_w / max(group size * sum freq_w, 1e-6)
+ *   LOSS    MSE + delta_coeff DELTA + accel_coeff ACCEL + latest_coeff LATEST
+ *   BANDk   the plain (unmasked) mean of |diff| over all b, t and bands[2k] <= m < min(bands[2k+1], M); a band
+ *           that is empty after clipping adds nothing
+ *   EVAL_*  eval_mel.py:24-32: e = diff mask; EVAL_MSE = sum e^2 / max(sum mask, 1) (frames, not frames x M; the
+ *           mask is squared with the difference), EVAL_MAE = sum |e| / the same, EVAL_LOSS = 0.8 MSE + 0.2 MAE
+ *   MCD     per sequence over its rows with mask != 0 (mean and std non-NULL): db = x std + mean;
+ *           x' = max(max(db, -100), max over the sequence's masked rows and all mels of that - 80), the maximum
+ *           taken separately for pred and target (power_to_db(db_to_power(.)), ref 1, amin 1e-10, top_db 80);
+ *           c_k = s_k sum_m x'_m cos(pi k (2m + 1) / 2M), k < n_mfcc, s_0 = sqrt(1/M), s_k = sqrt(2/M);
+ *           value = (10 / ln 10) sqrt(2) mean over rows of |c_pred - c_tgt|_2.  A sequence without a masked row or
+ *           with a non-finite value is skipped.  MCD_SUM / MCD_COUNT: the values' sum and count.
+ * `acc` (M2S_METRICS_SLOTS doubles) is ADDED to; `out` (M2S_METRICS_SLOTS floats) holds this call alone; `per_seq`
+ * (B,3) holds a sequence's masked squared-difference sum, absolute sum and MCD-like (NaN where skipped).  Each may
+ * be NULL.  One workgroup per sequence writes its partial sums to the workspace (fp32 lanes, fixed-order tree); one
+ * workgroup reduces them per group in ascending sequence order in double.  No atomics, no waits: a call is
+ * bit-reproducible and a sequence's per_seq row does not depend on what else is in the batch.
+ * M2S_E_ARG, before any launch: B, T or M < 1, M > 256, n_bands outside 0..8, a null bands with n_bands > 0, only one
+ * of mean / std, n_mfcc < 1 or > M with MCD on, n_mfcc > 64, an undersized workspace.  Stateless: can be captured. */
+enum m2s_metrics_slot {
+  M2S_MET_LOSS = 0, M2S_MET_MSE, M2S_MET_MAE, M2S_MET_DELTA, M2S_MET_ACCEL, M2S_MET_LATEST,
+  M2S_MET_BAND0, M2S_MET_BAND1, M2S_MET_BAND2, M2S_MET_BAND3, M2S_MET_BAND4, M2S_MET_BAND5, M2S_MET_BAND6,
+  M2S_MET_BAND7, M2S_MET_EVAL_LOSS, M2S_MET_EVAL_MSE, M2S_MET_EVAL_MAE, M2S_MET_GROUPS, M2S_MET_MCD_SUM,
+  M2S_MET_MCD_COUNT, M2S_METRICS_SLOTS
+};
+size_t m2s_mel_metrics_workspace_bytes(int B);
+int m2s_mel_metrics(const float* pred, const float* target, const float* mask, int B, int T, int M, int group,
+                    const float* freq_w, const float* time_w, float delta_coeff, float accel_coeff, float latest_coeff,
+                    const int* bands, int n_bands, const float* mean, const float* std_, int n_mfcc, double* acc,
+                    float* out, float* per_seq, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------ streaming vocoder ---- */
 /* The generator of this reference has causal resblocks; it looks ahead only through conv_pre's and conv_post's right

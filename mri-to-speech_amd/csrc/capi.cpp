@@ -330,6 +330,63 @@ int m2s_acoustic_forward_windowed(m2s_acoustic* m, const float* frames, const in
   });
 }
 
+size_t m2s_acoustic_pairs_workspace_bytes(const m2s_acoustic* m, const int* lengths, int B, int H, int W, int window) {
+  return size_query(m, [&] { return m->impl.pairs_workspace_bytes(lengths, B, H, W, window); });
+}
+
+int m2s_bilstm_pairs(m2s_acoustic* m, const float* feats, const int* lengths, int B, int rows, int window, float* y,
+                     float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && feats && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.bilstm_pairs(feats, lengths, B, rows, window, y, mel_norm, w, S(stream));
+  });
+}
+
+int m2s_acoustic_forward_pairs(m2s_acoustic* m, const float* frames, const int* lengths, int B, int rows, int H, int W,
+                               int window, float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(m && frames && mel_norm && ws, "null argument");
+    no_pending_error(m->impl);
+    DeviceGuard g(m->impl.device());
+    m2s::Workspace w(ws, ws_bytes);
+    m->impl.forward_pairs(frames, lengths, B, rows, H, W, window, mel_norm, w, S(stream));
+  });
+}
+
+size_t m2s_mel_metrics_workspace_bytes(int B) {
+  if (B < 1) return 0;
+  return m2s::Workspace::bytes([&](m2s::Workspace& w) { w.take<float>((size_t)B * m2s::MET_PART); });
+}
+
+int m2s_mel_metrics(const float* pred, const float* target, const float* mask, int B, int T, int M, int group,
+                    const float* freq_w, const float* time_w, float delta_coeff, float accel_coeff, float latest_coeff,
+                    const int* bands, int n_bands, const float* mean, const float* std_, int n_mfcc, double* acc,
+                    float* out, float* per_seq, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(pred && target && freq_w && time_w && ws, "null argument");
+    M2S_CHECK(B >= 1 && T >= 1 && M >= 1 && M <= 256, "mel_metrics: B, T >= 1 and 1 <= M <= 256");
+    M2S_CHECK(group >= 0, "mel_metrics: group must be >= 0");
+    M2S_CHECK(n_bands >= 0 && n_bands <= 8 && (bands || n_bands == 0), "mel_metrics: n_bands outside 0..8 or null bands");
+    M2S_CHECK((mean == nullptr) == (std_ == nullptr), "mel_metrics: mean and std go together");
+    if (mean) M2S_CHECK(n_mfcc >= 1 && n_mfcc <= M && n_mfcc <= 64, "mel_metrics: n_mfcc outside 1..min(M, 64)");
+    m2s::Workspace w(ws, ws_bytes);
+    m2s::MelMetricsArgs a{};
+    a.part = w.take<float>((size_t)B * m2s::MET_PART);
+    a.pred = pred, a.target = target, a.mask = mask;
+    a.B = B, a.T = T, a.M = M, a.group = group;
+    a.freq_w = freq_w, a.time_w = time_w;
+    a.coeff[0] = delta_coeff, a.coeff[1] = accel_coeff, a.coeff[2] = latest_coeff;
+    a.n_bands = n_bands;
+    for (int i = 0; i < 2 * n_bands; ++i) a.bands[i] = bands[i];
+    a.mean = mean, a.sd = std_, a.n_mfcc = mean ? n_mfcc : 0;
+    a.acc = acc, a.out = out, a.per_seq = per_seq;
+    m2s::launch_mel_metrics(a, S(stream));
+  });
+}
+
 size_t m2s_vocoder_ragged_workspace_bytes(const m2s_vocoder* v, const int* lengths, int B) {
   return size_query(v, [&] { return v->impl.ragged_workspace_bytes(lengths, B); });
 }

@@ -179,6 +179,8 @@ __global__ void __launch_bounds__(256) lstm_step_kernel(const float* __restrict_
 
 // ---------------------------------------------------------------------------------------------
 constexpr int HEAD_W = 16;  // waves of a mel_head workgroup (the K split)
+// MERGED: hs is one plane of rows that already hold h_fwd + h_bwd (the pair rows); the same sums from there on
+template <bool MERGED>
 __global__ void __launch_bounds__(64 * HEAD_W) mel_head_kernel(const float* __restrict__ hs, int rows, int H,
                                                               const float* __restrict__ wt, const float* __restrict__ b,
                                                               int n_mels, float* __restrict__ out) {
@@ -189,7 +191,8 @@ __global__ void __launch_bounds__(64 * HEAD_W) mel_head_kernel(const float* __re
   float* part = ys + H;
   const int row = blockIdx.x;
   const long plane = (long)rows * H;
-  for (int k = threadIdx.x; k < H; k += 64 * HEAD_W) ys[k] = hs[(long)row * H + k] + hs[plane + (long)row * H + k];
+  for (int k = threadIdx.x; k < H; k += 64 * HEAD_W)
+    ys[k] = MERGED ? hs[(long)row * H + k] : hs[(long)row * H + k] + hs[plane + (long)row * H + k];
   __syncthreads();
   const int q = threadIdx.x >> 6;
   const int k0 = q * H / HEAD_W, k1 = (q + 1) * H / HEAD_W;
@@ -394,10 +397,13 @@ void launch_lstm_step(const float* pre, const float* whh, float* hs, float* cst,
 }
 
 void launch_mel_head(const float* hs, int rows, int H, const float* wt, const float* b, int n_mels, float* out,
-                     hipStream_t s) {
+                     hipStream_t s, bool merged) {
   M2S_CHECK(n_mels >= 1 && H >= 4, "mel_head: shape");
-  hipLaunchKernelGGL(mel_head_kernel, dim3(rows), dim3(64 * HEAD_W), (H + HEAD_W * 64) * sizeof(float), s, hs, rows, H, wt, b,
-                     n_mels, out);
+  const size_t lds = (H + HEAD_W * 64) * sizeof(float);
+  if (merged)
+    hipLaunchKernelGGL(mel_head_kernel<true>, dim3(rows), dim3(64 * HEAD_W), lds, s, hs, rows, H, wt, b, n_mels, out);
+  else
+    hipLaunchKernelGGL(mel_head_kernel<false>, dim3(rows), dim3(64 * HEAD_W), lds, s, hs, rows, H, wt, b, n_mels, out);
   M2S_HIP(hipGetLastError());
 }
 

@@ -315,9 +315,30 @@ void launch_lstm_window_step(const float* pre, const float* wperm, const int2* w
 void launch_lstm_window_mean(const float* hf, const int* tab, int B, int W, int S, long N, int max_len, float* hm,
                              hipStream_t s);
 
+// pair rows: hf [2][W][S][H] of S full windows -> y (S, W, H), y[p][s] = hf[fwd][s][p] + hf[rev][W - 1 - s][p];
+// y2 (may be null) receives the same rows
+void launch_lstm_window_pairs(const float* hf, int W, int S, float* y, float* y2, hipStream_t s);
+
+// validation metrics (metrics.hip; m2s.h "fused mel metrics"): MET_PART floats of partial sums per sequence, then the
+// per-group reduction
+constexpr int MET_PART = 32;
+struct MelMetricsArgs {
+  const float *pred, *target, *mask;
+  int B, T, M, group;
+  const float *freq_w, *time_w;
+  float coeff[3];  // delta, accel, latest
+  int bands[16], n_bands;
+  const float *mean, *sd;
+  int n_mfcc;
+  double* acc;
+  float *out, *per_seq, *part;
+};
+void launch_mel_metrics(const MelMetricsArgs& a, hipStream_t s);
+
 // head: y = hs[0] + hs[1] (sum merge); out = y W^T + b.  wt (H, n_mels) transposed weight.
+// merged: hs is one plane of rows that are already sum-merged (the pair rows)
 void launch_mel_head(const float* hs, int rows, int H, const float* wt, const float* b, int n_mels,
-                     float* out, hipStream_t s);
+                     float* out, hipStream_t s, bool merged = false);
 
 // mel glue: db = x*std + mean; ln = log(clamp(10^(db/10), 1e-5)).  Any output may be null.
 // ln_t (rows, cs) T channel-last copy feeds the vocoder.

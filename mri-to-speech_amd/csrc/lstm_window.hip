@@ -268,6 +268,23 @@ __global__ void __launch_bounds__(160) lstm_window_mean_kernel(const float4* __r
   hm[(N + row) * q + u] = make_float4(r.x / n, r.y / n, r.z / n, r.w / n);
 }
 
+// Pair rows: output row (pair p, local step s) = the forward h of window p at step s + its reverse h at step
+// W - 1 - s (the reverse direction reaches frame s of the window at that step): the sum merge of M(x[p .. p + W - 1])[s].
+// hf [dir][step][S][640], every window full (k = W); y (S, W, 640), y2 the same rows again (may be null).  One
+// workgroup per output row, 160 float4 lanes: coalesced reads and writes, nothing shared between workgroups.
+__global__ void __launch_bounds__(160) lstm_window_pairs_kernel(const float4* __restrict__ hf, int W, int S,
+                                                                float4* __restrict__ y, float4* __restrict__ y2) {
+  const int p = blockIdx.x, s = blockIdx.y;
+  const int q = LW_H / 4, u = threadIdx.x;
+  const long plane = (long)S * q;
+  const float4 a = hf[(long)s * plane + (long)p * q + u];
+  const float4 d = hf[((long)W + (W - 1 - s)) * plane + (long)p * q + u];
+  const float4 o = make_float4(a.x + d.x, a.y + d.y, a.z + d.z, a.w + d.w);
+  const long row = (long)p * W + s;
+  y[row * q + u] = o;
+  if (y2) y2[row * q + u] = o;
+}
+
 }  // namespace
 
 bool lstm_window_supported(int H) { return H == LW_H; }
@@ -325,6 +342,13 @@ void launch_lstm_window_mean(const float* hf, const int* tab, int B, int W, int 
   M2S_CHECK(B >= 1 && B <= 65535 && max_len >= 1, "lstm_window_mean: shape");
   hipLaunchKernelGGL(lstm_window_mean_kernel, dim3(max_len, B), dim3(160), 0, s, reinterpret_cast<const float4*>(hf),
                      tab, B, W, S, N, reinterpret_cast<float4*>(hm));
+  M2S_HIP(hipGetLastError());
+}
+
+void launch_lstm_window_pairs(const float* hf, int W, int S, float* y, float* y2, hipStream_t s) {
+  M2S_CHECK(S >= 1 && W >= 1 && W <= 16, "lstm_window_pairs: shape");
+  hipLaunchKernelGGL(lstm_window_pairs_kernel, dim3(S, W), dim3(160), 0, s, reinterpret_cast<const float4*>(hf), W, S,
+                     reinterpret_cast<float4*>(y), reinterpret_cast<float4*>(y2));
   M2S_HIP(hipGetLastError());
 }
 

@@ -788,7 +788,7 @@ Acoustic::WindowBufs Acoustic::window_bufs(Workspace& ws, const WindowPlan& p) c
     if (p.W > 2) b.hop[1] = ws.take<float>(dirs * S * H);
     b.c = ws.take<float>(dirs * S * H);
   }
-  b.hm = ws.take<float>((size_t)2 * p.R * H);
+  b.hm = ws.take<float>((size_t)(p.pairs ? 1 : 2) * p.R * H);  // pairs: the merged rows, one plane
   if (p.mean) b.hf = ws.take<float>((size_t)2 * p.W * S * H);
   return b;
 }
@@ -808,16 +808,12 @@ size_t Acoustic::windowed_workspace_bytes(const int* lengths, const int* context
   });
 }
 
-void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window,
-                               int merge, float* y, float* mel_norm, Workspace& ws, hipStream_t s) {
-  M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
-  const WindowPlan p = window_plan(lengths, context, B, N, window, merge);
-  ragged_check_stream(s);
-  const int H = hidden_, W = p.W, S = (int)p.S, dirs = p.mean ? 2 : 1;
+// the clip table, the projection and the W step launches of a plan: what latest, mean and the pair outputs share
+void Acoustic::window_steps(const float* feats, const WindowPlan& p, const WindowBufs& b, hipStream_t s) {
+  const int H = hidden_, W = p.W, S = (int)p.S, dirs = p.mean ? 2 : 1, B = p.B;
+  const long N = p.N;
   const bool split = dtype_ != M2S_DT_F32;
-  const WindowBufs b = window_bufs(ws, p);
   rtab_.upload_ints(p.tab.data(), p.tab.size(), b.tab, s);
-  StageTag tag("bilstm");
   // the projection, once per FRAME row; one K order for every row count (kwave stays 0: a row's bits must not
   // depend on how many rows the call holds, or a stream's chunking would show)
   ConvArgs a = conv_args(p_.lstm_ih);
@@ -849,6 +845,17 @@ void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int
                  (split ? 3.0 : 2.0) * 4.0 * H * H * p.active[j], 4.0 * dirs * 4 * H * H + 4.0 * p.active[j] * H * 8.0, s);
     launch_lstm_window_step(b.pre, wperm, b.win, S, j, dirs, split, hin, hout, b.c, hf, (long)((size_t)W * plane), s);
   }
+}
+
+void Acoustic::bilstm_windowed(const float* feats, const int* lengths, const int* context, int B, long N, int window,
+                               int merge, float* y, float* mel_norm, Workspace& ws, hipStream_t s) {
+  M2S_CHECK(lstm_window_supported(hidden_), "windowed: rnn_hidden must be 640");
+  const WindowPlan p = window_plan(lengths, context, B, N, window, merge);
+  ragged_check_stream(s);
+  const int H = hidden_, W = p.W, S = (int)p.S;
+  const WindowBufs b = window_bufs(ws, p);
+  StageTag tag("bilstm");
+  window_steps(feats, p, b, s);
   if (p.mean) {
     double contrib = 0.0;  // (window, step, direction) rows read: every valid one once
     for (int j = 0; j < W; ++j) contrib += p.active[j];
@@ -872,6 +879,66 @@ void Acoustic::forward_windowed(const float* frames, const int* lengths, const i
   float* feats = feats_buf(ws, (size_t)N);
   effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
   bilstm_windowed(feats, lengths, context, B, N, window, merge, nullptr, mel_norm, ws, s);
+}
+
+// ------------------------------------------------------------------------------------------
+// Pair outputs: every row of every training window (m2s.h "pair outputs")
+WindowPlan pairs_plan(const int* lengths, int B, long rows, int window) {
+  WindowPlan p = window_plan(lengths, nullptr, B, rows, window, M2S_WINDOW_MEAN);
+  for (int b = 0; b < B; ++b)
+    M2S_CHECK(lengths[b] >= window, "pairs: lengths[" + std::to_string(b) + "] = " + std::to_string(lengths[b]) +
+                                        " is shorter than the window of " + std::to_string(window) +
+                                        " (the reference skips such clips: leave them out)");
+  M2S_CHECK((double)p.S * window <= 2147483647.0, "pairs: P x window out of range");
+  p.pairs = true;
+  p.R = p.S * window;
+  return p;
+}
+
+size_t Acoustic::pairs_workspace_bytes(const int* lengths, int B, int H, int W, int window) const {
+  long n = 0;
+  for (int b = 0; lengths && b < B; ++b) n += lengths[b];
+  M2S_CHECK(lstm_window_supported(hidden_), "pairs: rnn_hidden must be 640");
+  const WindowPlan p = pairs_plan(lengths, B, n, window);
+  return Workspace::bytes([&](Workspace& ws) {
+    if (H != 0 || W != 0) {
+      feats_buf(ws, (size_t)p.N);
+      effnet_ws(ws, (int)p.N, H, W);
+    }
+    window_bufs(ws, p);
+  });
+}
+
+void Acoustic::bilstm_pairs(const float* feats, const int* lengths, int B, long N, int window, float* y,
+                            float* mel_norm, Workspace& ws, hipStream_t s) {
+  M2S_CHECK(lstm_window_supported(hidden_), "pairs: rnn_hidden must be 640");
+  const WindowPlan p = pairs_plan(lengths, B, N, window);
+  ragged_check_stream(s);
+  const int H = hidden_, W = p.W, S = (int)p.S;
+  const WindowBufs b = window_bufs(ws, p);
+  StageTag tag("bilstm");
+  window_steps(feats, p, b, s);
+  {
+    // every (window, step, direction) row read once, every merged row written once (twice with y)
+    ProfScope ps("lstm_window_pairs_kernel", (double)p.R * H, 4.0 * H * p.R * (y ? 4.0 : 3.0), s);
+    launch_lstm_window_pairs(b.hf, W, S, b.hm, y, s);
+  }
+  if (mel_norm) {
+    StageTag head("head");
+    ProfScope ps("mel_head_kernel", 2.0 * p.R * H * n_mels_, 4.0 * p.R * (H + n_mels_), s);
+    launch_mel_head(b.hm, (int)p.R, H, static_cast<const float*>(arena_.ptr(p_.head_wt)),
+                    static_cast<const float*>(arena_.ptr(p_.head_b)), n_mels_, mel_norm, s, true);
+  }
+}
+
+void Acoustic::forward_pairs(const float* frames, const int* lengths, int B, long N, int H, int W, int window,
+                             float* mel_norm, Workspace& ws, hipStream_t s) {
+  M2S_CHECK(lstm_window_supported(hidden_), "pairs: rnn_hidden must be 640");
+  pairs_plan(lengths, B, N, window);  // before the CNN launches
+  ragged_check_stream(s);
+  float* feats = feats_buf(ws, (size_t)N);
+  effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
+  bilstm_pairs(feats, lengths, B, N, window, nullptr, mel_norm, ws, s);
 }
 
 // ------------------------------------------------------------------------------------------

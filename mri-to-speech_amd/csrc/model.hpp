@@ -140,7 +140,7 @@ class RaggedTable {
 // active[j]: window-directions that run a cell update at global step j (the algorithmic work of that launch).
 struct WindowPlan {
   int B = 0, W = 0, max_windows = 0, max_len = 0;
-  bool mean = false;
+  bool mean = false, pairs = false;  // pairs: the mean route, every row of every window kept unmerged
   long N = 0, S = 0, R = 0;
   std::vector<int> tab;
   double active[16] = {};
@@ -148,6 +148,8 @@ struct WindowPlan {
 // M2S_E_ARG, before any launch: window outside 1..16, an unknown merge, a context with mean, a context entry outside
 // 0..min(W - 1, len - 1), and the ragged calls' own argument errors
 WindowPlan window_plan(const int* lengths, const int* context, int B, long rows, int window, int merge);
+// the mean plan of clips that are all at least `window` long (M2S_E_ARG otherwise): S = P pairs, R = P * window rows
+WindowPlan pairs_plan(const int* lengths, int B, long rows, int window);
 
 // ---- packed plans: what the packers produce beside the arena bytes (offsets until the engine resolves them) ----
 // One block of the tf_efficientnetv2_b2 backbone as pack.hpp's for_each_backbone_block yields it: block `index`
@@ -317,6 +319,13 @@ class Acoustic {
                        float* y, float* mel_norm, Workspace& ws, hipStream_t s);
   void forward_windowed(const float* frames, const int* lengths, const int* context, int B, long N, int H, int W,
                         int window, int merge, float* mel_norm, Workspace& ws, hipStream_t s);
+  // Pair outputs (m2s.h "pair outputs"): every row of every full window, y (P, window, hidden) / mel_norm
+  // (P, window, n_mels), on the mean route's window table and step launches.
+  size_t pairs_workspace_bytes(const int* lengths, int B, int H, int W, int window) const;
+  void bilstm_pairs(const float* feats, const int* lengths, int B, long N, int window, float* y, float* mel_norm,
+                    Workspace& ws, hipStream_t s);
+  void forward_pairs(const float* frames, const int* lengths, int B, long N, int H, int W, int window, float* mel_norm,
+                     Workspace& ws, hipStream_t s);
 
  private:
   struct WindowBufs {
@@ -326,6 +335,7 @@ class Acoustic {
     void* hop[2] = {nullptr, nullptr};
   };
   WindowBufs window_bufs(Workspace& ws, const WindowPlan& p) const;
+  void window_steps(const float* feats, const WindowPlan& p, const WindowBufs& b, hipStream_t s);
   template <typename T>
   struct EffBufs {  // one CNN pass of pass_frames(N) frames
     T *A, *B, *M, *M2, *se_mean, *se_hid, *scale;  // ... SE means, hidden (rd <= 64), gates

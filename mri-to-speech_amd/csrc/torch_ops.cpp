@@ -17,6 +17,10 @@
 //   preprocess_frames  _preprocess_frame after the host decode         run_mri_video_inference.py:34-54
 //   preprocess_frames_resize  the same with cv2.resize on the device, and the training convention
 //                      (INTER_AREA, / 255)                            mri2speech_code/preprocess_rtmri_data.py:99-113
+//   *_pairs            the model on every training pair of a clip   mri2speech_code/preprocess_rtmri_data.py:198-259,
+//                      train_mri_acoustic_model.py:349-384
+//   mel_metrics        MaskedMSEMAE, band MAEs, eval_mel's losses and MCD-like   train_mri_acoustic_model.py:57-167,
+//                      263-277, mri2speech_code/eval_mel.py:19-82,104-155
 //   *_ragged           the same forward passes over clips of different lengths, packed (include/m2s.h)
 //   hifigan_forward_chunk  Generator.forward on spans of a stream, emitting the rows that are final (include/m2s.h)
 //   cam_backbone       backbone(x) in train() (batch-statistics BN)    mri_gradcam_formant.py:153-160,221-225
@@ -265,6 +269,88 @@ at::Tensor acoustic_forward_windowed(int64_t h, const at::Tensor& frames, at::In
                                    out.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
      "acoustic_forward_windowed");
   return out;
+}
+
+// Pair outputs (include/m2s.h): every row of every window of `window` frames, P = sum(lengths[b] - window + 1) pairs
+int64_t pair_count(const std::vector<int>& l, int64_t window) {
+  int64_t p = 0;
+  for (int v : l) p += std::max<int64_t>(0, (int64_t)v - window + 1);
+  return p;
+}
+
+// feats (N,208) -> (y (P,window,hidden), mel_norm (P,window,n_mels))
+std::tuple<at::Tensor, at::Tensor> bilstm_pairs(int64_t h, const at::Tensor& feats, at::IntArrayRef lengths,
+                                                int64_t window, int64_t hidden, int64_t n_mels) {
+  TORCH_CHECK(feats.dim() == 2 && feats.size(1) == 208, "bilstm_pairs: feats must be packed (N,208)");
+  const Guard g(feats.device());
+  const at::Tensor x = f32_on_device(feats, "feats");
+  const std::vector<int> l = host_lengths(lengths, "bilstm_pairs");
+  const int N = x.size(0), B = (int)l.size();
+  const int64_t P = pair_count(l, window), Wd = std::max<int64_t>(window, 0);
+  at::Tensor y = at::empty({P, Wd, hidden}, x.options());
+  at::Tensor m = at::empty({P, Wd, n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_pairs_workspace_bytes(A(h), l.data(), B, 0, 0, (int)window), x);
+  ok(m2s_bilstm_pairs(A(h), x.data_ptr<float>(), l.data(), B, N, (int)window, y.data_ptr<float>(), m.data_ptr<float>(),
+                      ws.data_ptr(), ws.numel(), S()),
+     "bilstm_pairs");
+  return {y, m};
+}
+
+// frames (N,H,W) -> mel_norm (P,window,n_mels)
+at::Tensor acoustic_forward_pairs(int64_t h, const at::Tensor& frames, at::IntArrayRef lengths, int64_t window,
+                                  int64_t n_mels) {
+  TORCH_CHECK(frames.dim() == 3, "acoustic_forward_pairs: frames must be packed (N,H,W)");
+  const Guard g(frames.device());
+  const at::Tensor x = f32_on_device(frames, "frames");
+  const std::vector<int> l = host_lengths(lengths, "acoustic_forward_pairs");
+  const int N = x.size(0), H = x.size(1), W = x.size(2), B = (int)l.size();
+  at::Tensor out = at::empty({pair_count(l, window), std::max<int64_t>(window, 0), n_mels}, x.options());
+  at::Tensor ws = workspace(m2s_acoustic_pairs_workspace_bytes(A(h), l.data(), B, H, W, (int)window), x);
+  ok(m2s_acoustic_forward_pairs(A(h), x.data_ptr<float>(), l.data(), B, N, H, W, (int)window, out.data_ptr<float>(),
+                                ws.data_ptr(), ws.numel(), S()),
+     "acoustic_forward_pairs");
+  return out;
+}
+
+// Fused validation metrics (include/m2s.h): pred / target (B,T,M), mask (B,T) or None -> (out (M2S_METRICS_SLOTS)
+// fp32 of this call, per_seq (B,3)); acc (M2S_METRICS_SLOTS) float64 is added to in place.  coeffs = delta, accel,
+// latest; bands = flat {start, end} pairs; mean / std None: no MCD-like.
+std::tuple<at::Tensor, at::Tensor> mel_metrics(const at::Tensor& pred, const at::Tensor& target,
+                                               const c10::optional<at::Tensor>& mask, int64_t group,
+                                               const at::Tensor& freq_w, const at::Tensor& time_w,
+                                               at::ArrayRef<double> coeffs, at::IntArrayRef bands,
+                                               const c10::optional<at::Tensor>& mean,
+                                               const c10::optional<at::Tensor>& std_, int64_t n_mfcc, at::Tensor acc) {
+  TORCH_CHECK(pred.dim() == 3 && pred.sizes() == target.sizes(), "mel_metrics: pred and target must be equal (B,T,M)");
+  TORCH_CHECK(coeffs.size() == 3 && bands.size() % 2 == 0, "mel_metrics: three coefficients, {start,end} band pairs");
+  TORCH_CHECK(mean.has_value() == std_.has_value(), "mel_metrics: mean and std go together");
+  const Guard g(pred.device());
+  const at::Tensor p = f32_on_device(pred, "pred"), t = f32_on_device(target, "target");
+  const at::Tensor fw = f32_on_device(freq_w, "freq_w"), tw = f32_on_device(time_w, "time_w");
+  const int B = p.size(0), T = p.size(1), M = p.size(2);
+  TORCH_CHECK(fw.numel() == M && tw.numel() == T, "mel_metrics: freq_w must have M entries and time_w T");
+  at::Tensor mk, mu, sd;
+  if (mask.has_value()) {
+    mk = f32_on_device(*mask, "mask");
+    TORCH_CHECK(mk.dim() == 2 && mk.size(0) == B && mk.size(1) == T, "mel_metrics: mask must be (B,T)");
+  }
+  if (mean.has_value()) {
+    mu = f32_on_device(*mean, "mean"), sd = f32_on_device(*std_, "std");
+    TORCH_CHECK(mu.numel() == M && sd.numel() == M, "mel_metrics: mean and std must have M entries");
+  }
+  TORCH_CHECK(acc.is_cuda() && acc.scalar_type() == at::kDouble && acc.is_contiguous() && acc.numel() == M2S_METRICS_SLOTS,
+              "mel_metrics: acc must be a contiguous float64 device tensor of ", (int)M2S_METRICS_SLOTS, " entries");
+  at::Tensor out = at::empty({M2S_METRICS_SLOTS}, p.options());
+  at::Tensor per_seq = at::empty({B, 3}, p.options());
+  std::vector<int> bd(bands.begin(), bands.end());
+  at::Tensor ws = workspace(m2s_mel_metrics_workspace_bytes(B), p);
+  ok(m2s_mel_metrics(p.data_ptr<float>(), t.data_ptr<float>(), mk.defined() ? mk.data_ptr<float>() : nullptr, B, T, M,
+                     (int)group, fw.data_ptr<float>(), tw.data_ptr<float>(), (float)coeffs[0], (float)coeffs[1],
+                     (float)coeffs[2], bd.data(), (int)(bd.size() / 2), mu.defined() ? mu.data_ptr<float>() : nullptr,
+                     sd.defined() ? sd.data_ptr<float>() : nullptr, (int)n_mfcc, acc.data_ptr<double>(),
+                     out.data_ptr<float>(), per_seq.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "mel_metrics");
+  return {out, per_seq};
 }
 
 // mel (N,num_mels) packed layout 1 -> wav (N*hop)
@@ -651,6 +737,10 @@ TORCH_LIBRARY(m2s, m) {
         " int n_mels) -> (Tensor, Tensor)");
   m.def("acoustic_forward_windowed(int handle, Tensor frames, int[] lengths, int[] context, int window, int merge,"
         " int n_mels) -> Tensor");
+  m.def("bilstm_pairs(int handle, Tensor feats, int[] lengths, int window, int hidden, int n_mels) -> (Tensor, Tensor)");
+  m.def("acoustic_forward_pairs(int handle, Tensor frames, int[] lengths, int window, int n_mels) -> Tensor");
+  m.def("mel_metrics(Tensor pred, Tensor target, Tensor? mask, int group, Tensor freq_w, Tensor time_w, float[] coeffs,"
+        " int[] bands, Tensor? mean, Tensor? std, int n_mfcc, Tensor(a!) acc) -> (Tensor, Tensor)");
   m.def("hifigan_forward_chunk(int handle, Tensor mel, int[] lengths, int[] context, int[] hold, int hop) -> Tensor");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
   m.def("preprocess_frames_resize(Tensor frames, int out_h, int out_w, int interp, int norm) -> Tensor");
@@ -684,6 +774,9 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("pipeline_forward_ragged", &pipeline_forward_ragged);
   m.impl("bilstm_windowed", &bilstm_windowed);
   m.impl("acoustic_forward_windowed", &acoustic_forward_windowed);
+  m.impl("bilstm_pairs", &bilstm_pairs);
+  m.impl("acoustic_forward_pairs", &acoustic_forward_pairs);
+  m.impl("mel_metrics", &mel_metrics);
   m.impl("hifigan_forward_chunk", &hifigan_forward_chunk);
   m.impl("preprocess_frames", &preprocess_frames);
   m.impl("preprocess_frames_resize", &preprocess_frames_resize);

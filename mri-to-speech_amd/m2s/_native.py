@@ -21,6 +21,9 @@ DTYPES = {"fp32": F32, "float32": F32, "f32": F32, "bf16": BF16, "bfloat16": BF1
           "fp8": FP8, "e4m3": FP8}
 ELEM_F32, ELEM_I64 = 0, 1
 ABI_VERSION = 6  # include/m2s.h M2S_ABI_VERSION
+# enum m2s_metrics_slot (include/m2s.h): the slots of m2s_mel_metrics' `acc` / `out`, in order
+METRICS_SLOTS = ("loss", "mse", "mae", "delta", "accel", "latest", "band0", "band1", "band2", "band3", "band4", "band5",
+                 "band6", "band7", "eval_loss", "eval_mse", "eval_mae", "groups", "mcd_sum", "mcd_count")
 
 
 class M2SError(RuntimeError):
@@ -108,6 +111,13 @@ def lib():
         "m2s_acoustic_windowed_workspace_bytes": (sz, [vp, C.POINTER(i), C.POINTER(i), i, i, i, i, i]),
         "m2s_bilstm_windowed": (i, [vp, fp, C.POINTER(i), C.POINTER(i), i, i, i, i, fp, fp, vp, sz, vp]),
         "m2s_acoustic_forward_windowed": (i, [vp, fp, C.POINTER(i), C.POINTER(i), i, i, i, i, i, i, fp, vp, sz, vp]),
+        # pair outputs (every row of every training window) and the fused validation metrics; `bands` is a host array
+        "m2s_acoustic_pairs_workspace_bytes": (sz, [vp, C.POINTER(i), i, i, i, i]),
+        "m2s_bilstm_pairs": (i, [vp, fp, C.POINTER(i), i, i, i, fp, fp, vp, sz, vp]),
+        "m2s_acoustic_forward_pairs": (i, [vp, fp, C.POINTER(i), i, i, i, i, i, fp, vp, sz, vp]),
+        "m2s_mel_metrics_workspace_bytes": (sz, [i]),
+        "m2s_mel_metrics": (i, [fp, fp, fp, i, i, i, i, fp, fp, C.c_float, C.c_float, C.c_float, C.POINTER(i), i, fp, fp,
+                                i, fp, fp, fp, vp, sz, vp]),
         "m2s_cam_create": (i, [C.POINTER(Tensor), i, i, C.POINTER(vp)]),
         "m2s_cam_destroy": (None, [vp]),
         "m2s_cam_bn_layers": (i, [vp]),
@@ -173,7 +183,9 @@ def exported_symbols() -> List[str]:
                         "m2s_acoustic_forward_ragged", "m2s_vocoder_ragged_workspace_bytes",
                         "m2s_vocoder_forward_ragged", "m2s_pipeline_ragged_workspace_bytes",
                         "m2s_pipeline_forward_ragged", "m2s_acoustic_windowed_workspace_bytes", "m2s_bilstm_windowed",
-                        "m2s_acoustic_forward_windowed", "m2s_vocoder_reach", "m2s_vocoder_set_chunk_cone",
+                        "m2s_acoustic_forward_windowed", "m2s_acoustic_pairs_workspace_bytes", "m2s_bilstm_pairs",
+                        "m2s_acoustic_forward_pairs", "m2s_mel_metrics_workspace_bytes", "m2s_mel_metrics",
+                        "m2s_vocoder_reach", "m2s_vocoder_set_chunk_cone",
                         "m2s_vocoder_chunk_workspace_bytes", "m2s_vocoder_forward_chunk", "m2s_cam_create",
                         "m2s_cam_destroy", "m2s_cam_bn_layers",
                         "m2s_cam_bn_channels", "m2s_cam_workspace_bytes", "m2s_cam_backbone",

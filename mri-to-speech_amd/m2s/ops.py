@@ -27,6 +27,11 @@ RAGGED_OPS = ("bilstm_summerge_ragged", "acoustic_forward_ragged", "hifigan_forw
 # 1 = mean; `context` = leading history rows per clip that get no output row, [] = none)
 WINDOWED_OPS = ("bilstm_windowed", "acoustic_forward_windowed")
 WINDOW_MERGES = {"latest": 0, "mean": 1}
+# validation: the model on every training pair (window of `window` frames, stride 1) of packed clips, P =
+# sum(lengths[b] - window + 1) pairs, and the reference's validation numbers of a (B,T,M) batch in two launches
+# (include/m2s.h "pair outputs", "fused mel metrics"; m2s/metrics.py)
+PAIR_OPS = ("bilstm_pairs", "acoustic_forward_pairs")
+METRIC_OPS = ("mel_metrics",)
 # streaming vocoder: the generator on spans of a stream, emitting only the rows that are final (packed like the ragged
 # ops; `context` / `hold` = leading / trailing rows per clip that are read but get no output)
 STREAM_OPS = ("hifigan_forward_chunk",)
@@ -173,6 +178,24 @@ def _register_fakes():
     @f("m2s::acoustic_forward_windowed")
     def _acoustic_windowed(handle, frames, lengths, context, window, merge, n_mels):
         return frames.new_empty((frames.shape[0] - sum(context), n_mels), dtype=torch.float32)
+
+    def _pairs(lengths, window):
+        return sum(max(0, n - window + 1) for n in lengths)
+
+    @f("m2s::bilstm_pairs")
+    def _bilstm_pairs(handle, feats, lengths, window, hidden, n_mels):
+        p = _pairs(lengths, window)
+        return (feats.new_empty((p, window, hidden), dtype=torch.float32),
+                feats.new_empty((p, window, n_mels), dtype=torch.float32))
+
+    @f("m2s::acoustic_forward_pairs")
+    def _acoustic_pairs(handle, frames, lengths, window, n_mels):
+        return frames.new_empty((_pairs(lengths, window), window, n_mels), dtype=torch.float32)
+
+    @f("m2s::mel_metrics")
+    def _mel_metrics(pred, target, mask, group, freq_w, time_w, coeffs, bands, mean, std, n_mfcc, acc):
+        return (pred.new_empty((acc.shape[0],), dtype=torch.float32),
+                pred.new_empty((pred.shape[0], 3), dtype=torch.float32))
 
     @f("m2s::hifigan_forward_chunk")
     def _hifigan_chunk(handle, mel, lengths, context, hold, hop):

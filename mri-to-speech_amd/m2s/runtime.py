@@ -181,6 +181,30 @@ class AcousticEngine:
         x, lengths = _packed(frames, lengths, self.device, 2)
         return self.ops.acoustic_forward_windowed(self.handle, x, lengths, context, window, merge, self.n_mels)
 
+    # ---- pair outputs (include/m2s.h "pair outputs"): the model on every training pair, i.e. every window of
+    # `window` consecutive frames of a clip, stride 1, with all `window` rows of each kept: what a loss over the
+    # reference's pairs_ref{window} needs.  The CNN still runs once per frame row.
+    def bilstm_pairs(self, feats, lengths=None, window: int = 4):
+        """packed feats (N,208) (one clip if ``lengths`` is None) or a list of (T_b,208) -> (merged BiLSTM output
+        (P,window,H), head output (P,window,n_mels)), P = sum(T_b - window + 1): pairs in clip order, windows
+        ascending within a clip.  Every clip must have at least ``window`` rows."""
+        if lengths is None and not isinstance(feats, (list, tuple)):
+            lengths = [int(feats.shape[0])]
+        x, lengths = _packed(feats, lengths, self.device, 1)
+        return self.ops.bilstm_pairs(self.handle, x, lengths, int(window), self.rnn_hidden, self.n_mels)
+
+    def forward_pairs(self, frames, lengths=None, window: int = 4):
+        """packed frames (N,[1,]H,W) (one clip if ``lengths`` is None) or a list of per-clip tensors -> normalised
+        mel (P,window,n_mels) of every training pair."""
+        if isinstance(frames, (list, tuple)):
+            frames = [f[:, 0] if f.dim() == 4 else f for f in frames]
+        elif frames.dim() == 4:
+            frames = frames[:, 0]
+        if lengths is None and not isinstance(frames, (list, tuple)):
+            lengths = [int(frames.shape[0])]
+        x, lengths = _packed(frames, lengths, self.device, 2)
+        return self.ops.acoustic_forward_pairs(self.handle, x, lengths, int(window), self.n_mels)
+
 
 class VocoderEngine:
     def __init__(self, state_dict: Dict, h, dtype: str = "bf16x3", device=None):
@@ -353,3 +377,41 @@ class Pipeline:
         db, ln = mel_glue(mn, self.mean, self.std)
         wav = self.voc.forward_ragged(ln, lengths)
         return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": wav}
+
+    def forward_pairs(self, frames, lengths=None, window: int = 4):
+        """The acoustic model on every training pair of the clips (AcousticEngine.forward_pairs): normalised mel
+        (P,window,n_mels).  No vocoder leg: the pairs are what the validation losses are taken on."""
+        return self.ac.forward_pairs(frames, lengths, window)
+
+    def validate(self, frames, lengths, mel_db, mask=None, mean=None, std=None, window: int = 4, select=None,
+                 group: int = 8, metrics=None):
+        """The reference's validation numbers (OTNLikeTrainer.validate, eval_mel.py) of packed clips, on the device.
+
+        ``frames`` packed (N,[1,]H,W) or a list of per-clip tensors, ``mel_db`` the packed (N,n_mels) dB mels of the
+        same rows (what save_sample writes), ``mask`` packed (N,) floats or None = ones; ``mean`` / ``std`` the
+        scaler (default: the pipeline's).  Runs ``forward_pairs``, standardises the target ``(mel_db - mean) / std``
+        and cuts target and mask into the same (P,window,.) pairs, keeps the pairs ``select`` names (an index
+        tensor into the P pairs, in the order the groups are to be formed), and updates ``metrics`` (a
+        ``m2s.metrics.MelMetrics``; a new one if None) with groups of ``group`` pairs.  Every clip must have at least
+        ``window`` rows.  No host synchronisation; returns the MelMetrics, whose ``compute()`` downloads."""
+        from .metrics import MelMetrics, pair_index
+        if isinstance(frames, (list, tuple)):
+            lengths = [int(f.shape[0]) for f in frames] if lengths is None else lengths
+        elif lengths is None:
+            lengths = [int(frames.shape[0])]
+        lengths = [int(n) for n in lengths]
+        mean = self.mean if mean is None else torch.as_tensor(mean, dtype=torch.float32).to(self.device)
+        std = self.std if std is None else torch.as_tensor(std, dtype=torch.float32).to(self.device)
+        pred = self.ac.forward_pairs(frames, lengths, window)
+        tgt = (_as_f32(mel_db, self.device) - mean) / std
+        if tgt.shape[0] != sum(lengths):
+            raise N.M2SError(f"mel_db has {tgt.shape[0]} rows, lengths give {sum(lengths)}")
+        idx = pair_index(lengths, window, self.device)  # (P, window) packed row of every pair row
+        if select is not None:
+            sel = torch.as_tensor(select, dtype=torch.long).to(self.device)
+            pred, idx = pred.index_select(0, sel), idx.index_select(0, sel)
+        mk = None if mask is None else _as_f32(mask, self.device)[idx]
+        if metrics is None:
+            metrics = MelMetrics(self.ac.n_mels, mean, std, device=self.device)
+        metrics.update(pred, tgt[idx], mk, group=group)
+        return metrics

@@ -311,6 +311,30 @@ class OTNLikeCNNBiLSTM(nn.Module):
         out = self._engine(x.device).forward_windowed(x.reshape(B * T, *x.shape[-2:]), [T] * B, window, merge)
         return out.view(B, T, -1)
 
+    def forward_pairs(self, x, window: int = 4) -> torch.Tensor:
+        """(B,T,1,H,W) or (B,T,H,W) -> (B, T - window + 1, window, n_mels): the model on every training pair of
+        every clip, i.e. on each window of ``window`` consecutive frames from zero state, with all its rows kept
+        (eval only; m2s.runtime.AcousticEngine.forward_pairs).  What a validation loss over the reference's
+        pairs_ref{window} is taken on, with the CNN run once per frame.  A list of per-clip (T_b,[1,]H,W) tensors
+        of different lengths gives the packed (P, window, n_mels), P = sum(T_b - window + 1), in clip order."""
+        if self.training:
+            raise NotImplementedError("forward_pairs is an inference mode: call model.eval() first")
+        if isinstance(x, (list, tuple)):  # clips of different lengths: (T_b,[1,]H,W) each -> packed (P, window, n_mels)
+            self._check_grad(x[0])
+            return self._engine(x[0].device).forward_pairs(list(x), None, window)
+        self._check_grad(x)
+        if x.dim() == 5:
+            if x.size(2) != 1:
+                raise ValueError("expected a single grey channel")
+            x = x[:, :, 0]
+        if x.dim() != 4:
+            raise ValueError(f"expected (B,T,[1,]H,W) frames, got {tuple(x.shape)}")
+        B, T = x.shape[0], x.shape[1]
+        if T < window:
+            raise ValueError(f"clips of {T} frames are shorter than the window of {window}")
+        out = self._engine(x.device).forward_pairs(x.reshape(B * T, *x.shape[-2:]), [T] * B, window)
+        return out.view(B, T - window + 1, window, -1)
+
 
 def build_acoustic_model(n_mels: int = 64, cnn_pretrained: bool = False, rnn_hidden: int = 640,
                          dropout: float = 0.5, use_checkpoint: bool = False, ckpt_segments: int = 2,
