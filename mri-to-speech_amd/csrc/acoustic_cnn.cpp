@@ -1,0 +1,484 @@
+// Execution plan of the acoustic model's CNN (tf_efficientnetv2_b2 backbone + GAP): which kernel runs for which
+// block, shape and switch, and the scratch of a pass.  The weights are packed by pack_acoustic.cpp (host code); the
+// constructor here reads the switches, packs, uploads the arena and resolves device pointers.
+#include <algorithm>
+#include <initializer_list>
+#include <utility>
+
+#include "plan_util.hpp"
+#include "prof.hpp"
+
+namespace m2s {
+
+Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int device)
+    : dtype_(dtype), device_(device), n_mels_(n_mels), hidden_(hidden) {
+  // (the last row: A/B and tests only)
+  for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
+           {"M2S_IR_FUSED", &ir_fused_},   {"M2S_IR_WS", &ir_ws_},         {"M2S_IR_WS_S2", &ir_ws_s2_},
+           {"M2S_IRWS_F32", &irws_f32_},   {"M2S_STEM_FUSED", &stem_fused_}, {"M2S_F8_EXPAND", &f8_expand_},
+           {"M2S_F8_S2", &f8_s2_},         {"M2S_F8_ER", &f8_er_},         {"M2S_ER8_X8", &er8_x8_},
+           {"M2S_F8_ER2", &f8_er2_},       {"M2S_SE_Y8", &se_y8_},         {"M2S_SE_FUSED", &se_fused_},
+           {"M2S_ER_FUSED", &er_fused_},   {"M2S_SE_WS", &se_ws_},         {"M2S_LSTM_PERSISTENT", &lstm_persistent_},
+           {"M2S_LSTM_MID", &lstm_mid_},   {"M2S_LSTM_X3", &lstm_x3_},     {"M2S_LSTM_X3G", &lstm_x3g_},
+           {"M2S_SE_SP", &se_sp_},         {"M2S_ER_MRG", &er_mrg_},       {"M2S_IR_S2BAND", &ir_s2band_},
+           {"M2S_ER_S2_FUSED", &er_s2_fused_}, {"M2S_SEWS_REV", &sews_rev_}})
+    env_flag(name, *v);
+  env_int("M2S_IRWS_MIN", irws_min_);
+  env_int("M2S_SEWS_MIN", sews_min_cus_);
+  pack_acoustic(sd, n_mels, hidden, dtype, arena_, p_);
+  arena_.upload(device);
+  for (auto& b : p_.blocks) {
+    b.c1.resolve(arena_);
+    if (b.type != 0) b.c2.resolve(arena_);
+    if (b.type == 2) {
+      b.se1.resolve(arena_);
+      b.se2.resolve(arena_);
+    }
+  }
+  p_.lstm_ih.resolve(arena_);
+  M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&err_host_), sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
+  *err_host_ = 0;
+  M2S_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&err_dev_), err_host_, 0));
+  M2S_HIP(hipMalloc(&gsync_, std::max(lstm_small_sync_bytes(), lstm_x3g_sync_bytes())));
+}
+
+Acoustic::~Acoustic() {
+  if (err_host_) (void)hipHostFree(err_host_);
+  if (gsync_) (void)hipFree(gsync_);
+}
+
+unsigned Acoustic::take_async_error() { return __atomic_exchange_n(err_host_, 0u, __ATOMIC_ACQ_REL); }
+
+void Acoustic::effnet_dims(int H, int W, size_t* io, size_t* mid, size_t* se) const {
+  size_t mio = 0, mmid = 0, mse = 0;
+  for_each_backbone_map(H, W, [&](const BlockDef& d, const BlockMap& m) {
+    if (d.type == 1) mmid = std::max(mmid, (size_t)m.oh * m.ow * chan_stride(d.mid));
+    if (d.type == 2) {
+      mmid = std::max(mmid, (size_t)m.ih * m.iw * chan_stride(d.mid));
+      mse = std::max(mse, (size_t)dw_pixel_blocks(m.oh, m.ow) * chan_stride(d.mid));
+      if (d.stride == 2 && m.oh % 4 == 0) mse = std::max(mse, (size_t)ir_s2band_bands(m.oh) * chan_stride(d.mid));
+    }
+    // every map a block reads or writes (block 0 reads the stem's output)
+    mio = std::max({mio, (size_t)m.ih * m.iw * chan_stride(d.cin), (size_t)m.oh * m.ow * chan_stride(d.cout)});
+  });
+  *io = mio;
+  *mid = mmid;
+  *se = mse;
+}
+
+size_t Acoustic::effnet_x8(int H, int W) const {
+  if (dtype_ != M2S_DT_FP8 || (!f8_expand_ && !f8_er_)) return 0;
+  size_t mx = 0;
+  for_each_backbone_map(H, W, [&](const BlockDef& d, const BlockMap& m) {
+    const Block& b = p_.blocks[d.index];
+    if (b.f8_pw && f8_expand_) mx = std::max(mx, (size_t)m.ih * m.iw * b.f8x_kp);  // the block input's map
+    if (b.er8 && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 32);              // er8_fused x8 / y8 (N, H, W, 32)
+    if (b.er8w && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 64);             // er8w_fused x8 / y8 (N, H, W, 64)
+  });
+  return round_up((int)mx, 256);
+}
+
+// Frames per CNN pass: `chunk`, or, where one pass fewer of at most chunk + chunk / 16 frames covers N, that
+// (8 x 1000 frames: 4 passes of 2000 instead of 4 x 1920 + a 320-frame tail, which fills the persistent
+// kernels' one-workgroup-per-CU grids for under two of their rounds).  Every pass is exact (per-frame work), so
+// the split never changes a result (test_effnet_chunking_is_exact).
+int Acoustic::pass_frames(int N) const {
+  if (N <= chunk) return N;
+  const int n = ceil_div(N, chunk), even = ceil_div(N, n - 1);
+  return even <= chunk + chunk / 16 ? even : chunk;
+}
+
+template <typename T>
+Acoustic::EffBufs<T> Acoustic::effnet_bufs(Workspace& ws, int N, int H, int W) const {
+  size_t io, mid, se;
+  effnet_dims(H, W, &io, &mid, &se);
+  const size_t nc = pass_frames(N), R = Elem<T>::R;  // split fp32: hi + lo planes
+  EffBufs<T> b{};
+  b.A = ws.take<T>(nc * io * R);
+  b.B = ws.take<T>(nc * io * R);
+  b.M = ws.take<T>(nc * mid * R);
+  b.M2 = ws.take<T>(nc * mid * R);
+  b.sums = ws.take<float>(nc * se);
+  b.se_mean = ws.take<T>(nc * p_.max_mid_cs * R);
+  b.se_hid = ws.take<T>(nc * SE_RD_MAX * R);
+  b.scale = ws.take<T>(nc * p_.max_mid_cs * R);
+  if (const size_t x8b = effnet_x8(H, W))
+    for (uint8_t*& x : b.X8) x = ws.take<uint8_t>(nc * x8b);
+  return b;
+}
+
+void Acoustic::effnet_ws(Workspace& ws, int N, int H, int W) const {
+  dispatch_act(dtype_, [&](auto t) { effnet_bufs<typename decltype(t)::type>(ws, N, H, W); });
+}
+
+float* Acoustic::feats_buf(Workspace& ws, size_t rows) const { return ws.take<float>(rows * EFF_OUT); }
+
+float* Acoustic::cnn_feats(const float* frames, long N, int H, int W, Workspace& ws, hipStream_t s) {
+  float* feats = feats_buf(ws, (size_t)N);
+  effnet(frames, (int)N, H, W, feats, -1, nullptr, nullptr, ws, s);
+  return feats;
+}
+
+void Acoustic::effnet(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe,
+                      int* probe_dims, Workspace& ws, hipStream_t s) {
+  StageTag tag("cnn");
+  dispatch_act(dtype_, [&](auto t) {
+    effnet_t<typename decltype(t)::type>(frames, N, H, W, feats, stop_after, probe, probe_dims, ws, s);
+  });
+}
+
+template <class Pass>  // a k x k conv of the pass's block: input oh x ow, output nh x nw
+static ConvArgs conv2d_args(const Pass& p, const PConv& pc, const void* x, void* y) {
+  ConvArgs a = conv_args(pc);
+  a.x = x;
+  a.y = y;
+  a.IH = p.oh;
+  a.IW = p.ow;
+  a.OH = p.nh;
+  a.OW = p.nw;
+  a.pad_t = p.qt;
+  a.pad_l = p.ql;
+  a.M = p.nc * p.nh * p.nw;
+  return a;
+}
+
+template <typename T>
+void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
+  const Block& b = p_.blocks[k];
+  ConvArgs a = conv2d_args(p, b.c1, p.cur, p.nxt);
+  a.act = ACT_SILU;
+  a.res = b.skip ? p.cur : nullptr;
+  run_conv<T>(a, b.c1, p.s);
+}
+
+template <typename T>
+void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
+  const Block& b = p_.blocks[k];
+  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  T *const cur = p.cur, *const nxt = p.nxt;
+  hipStream_t s = p.s;
+  const int co = chan_stride(b.cout);
+  const double px = (double)nc * nh * nw, flops = 2.0 * px * b.mid * (9.0 * b.cin + b.cout);
+  // no fused kernel takes the block: conv_exp and conv_pwl as two convs, the expanded map in M
+  auto unfused = [&] {
+    ConvArgs a = conv2d_args(p, b.c1, cur, p.b.M);
+    a.act = ACT_SILU;
+    ConvArgs q = pw_args(b.c2, p.b.M, nxt, nc * nh * nw, nh * nw);
+    q.res = b.skip ? cur : nullptr;
+    if (kSplit<T> && er_s2_fused_ && b.stride == 2 && conv_gemm_er_supported(a, q)) {
+      // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the expanded map stays in LDS (M is not touched);
+      // compulsory bytes = the block's input and output maps and both convs' weights
+      launch_conv_gemm_er(a, q, s, flops,
+                          4.0 * ((double)nc * oh * ow * b.cin + px * b.cout + (9.0 * b.cin + b.cout) * b.mid));
+    } else {
+      run_conv<T>(a, b.c1, s);
+      run_conv<T>(q, b.c2, s);
+    }
+  };
+  if constexpr (kSplit<T>) {
+    if (er_fused_ && b.er_sp && er_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
+      launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt, flops,
+                   4.0 * px * (b.c1.cs_in + co), s, er_mrg_);
+    } else if (er_fused_ && b.ers_sp && b.stride == 2 && ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
+      launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_wexp), b.c1.b,
+                     arena_.ptr(b.er_wpwl), b.c2.b, nxt, flops, 4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co), s);
+    } else {
+      unfused();
+    }
+  } else if constexpr (std::is_same<T, bf16_t>::value) {
+    uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
+    const Block* const nb = k + 1 < p_.blocks.size() ? &p_.blocks[k + 1] : nullptr;
+    // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
+    // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
+    // er8_fused to its in-kernel conversion)
+    uint8_t* const er8_next = X8[0] && f8_er_ && nb && ((er8_x8_ && nb->er8) || (f8_er2_ && nb->er8w))
+                                  ? (cur8 == X8[0] ? X8[1] : X8[0])
+                                  : nullptr;
+    if (er_fused_ && f8_er_ && b.er8 && er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
+      uint8_t* y8 = cur8 && er8_next && er8_fused_supported(nh, nw, b.cout, b.mid, b.cout) ? er8_next : nullptr;
+      launch_er8_fused(cur, nc, nh, nw, arena_.at<uint8_t>(b.er8_wexp), arena_.at<float>(b.er8_sexp), b.c1.b,
+                       arena_.at<uint8_t>(b.er8_wpwl), arena_.at<float>(b.er8_spwl), b.c2.b, nxt, flops,
+                       2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, cur8, y8);
+      next8 = y8;
+    } else if (er_fused_ && b.er_frag && er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+      launch_er_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt,
+                      flops, 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
+    } else if (er_fused_ && f8_er_ && f8_er2_ && b.er8w && cur8 &&
+               er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
+      uint8_t* y8 = er8_next && nb->er8w ? er8_next : nullptr;
+      launch_er8w_fused(cur, cur8, nc, nh, nw, arena_.at<uint8_t>(b.er8w_w), arena_.at<float>(b.er8w_sexp), b.c1.b,
+                        arena_.at<float>(b.er8w_spwl), b.c2.b, nxt, y8, flops,
+                        // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
+                        px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
+      next8 = y8;
+    } else if (er_fused_ && b.er_frag && er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+      launch_er2_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, b.c2.b, nxt, flops,
+                       2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
+    } else if (er_fused_ && b.er_frag && b.stride == 2 &&
+               ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, co, b.c1.kp, b.c2.kp)) {
+      // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
+      uint8_t* y8 = er8_next && ((co == 32 && nb->er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
+                                 (co == 64 && nb->er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
+                        ? er8_next
+                        : nullptr;
+      launch_ers2_fused(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.at<bf16_t>(b.er_wexp), b.c1.b,
+                        arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt, flops,
+                        2.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co) + (y8 ? px * 32 : 0.0), s, y8);
+      next8 = y8;
+    } else {
+      unfused();
+    }
+  } else {
+    unfused();
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
+  const Block& b = p_.blocks[k];
+  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  T *const cur = p.cur, *const M = p.b.M, *const M2 = p.b.M2, *const se_mean = p.b.se_mean;
+  float* const sums = p.b.sums;
+  uint8_t *&cur8 = p.cur8, *const *const X8 = p.b.X8;
+  hipStream_t s = p.s;
+  const int cs = chan_stride(b.mid);
+  constexpr bool SPL = kSplit<T>, FUSABLE = kNotF32<T>;
+  p.f8 = p.mid_f32 = false;
+  bool &f8 = p.f8, &mid_f32 = p.mid_f32;  // fp8 engine: e4m3 depthwise output -> the e4m3 SE GEMM
+  const float *const dw_w = arena_.at<float>(b.dw_w), *const dw_b = arena_.at<float>(b.dw_b);
+  // bf16 feeds the fused kernel bf16 depthwise taps (dword halves), split fp32 the fp32 taps
+  const void* wdw = SPL ? dw_w : arena_.ptr(b.dw_w2);
+  const bool big = nc >= irws_min_;  // persistent ir_ws only where its one-image workgroups fill the chip
+  // the SE-gated conv_pwl runs on se_ws (effnet_ir_pwl): then ir_ws hands it the expanded map as plain fp32 rows
+  // (one 16-byte store per 4 channels, no split; se_ws gates the fp32 value before its one split)
+  const bool sews = p.sews = SPL && se_ws_ && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
+                             // se_ws runs one persistent workgroup per tile (256 rows; 128 at 8 x 8) up to one per CU:
+                             // below a full round of tiles the split-K conv_gemm SE GEMM fills the chip instead
+                             ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sews_min_cus_ * device_cus();
+  // the persistent front half on an ih x iw input map (stride 2: down to nh x nw, passed with its pads)
+  auto ir_ws = [&](int ih, int iw, int stride, int OH, int OW, int pad_t, int pad_l) {
+    const double Pi = (double)ih * iw, Po = (double)nh * nw;
+    launch_ir_ws(cur, nc, ih, iw, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, dw_w, dw_b, M2, se_mean,
+                 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
+                 // algorithmic bytes on the real channel counts (split fp32: 4 B an element): compulsory = the
+                 // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
+                 // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
+                 4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), stride,
+                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, mid_f32 = sews && irws_f32_);
+  };
+  // fp8, the expand on e4m3: x8 of the block input (rows of P pixels an image), or null where the expand stays bf16
+  auto input8 = [&](bool f8x, int P) -> const uint8_t* {
+    if (!f8x) return nullptr;
+    if (!cur8) {  // no e4m3 producer wrote this input: convert it
+      cur8 = X8[0];
+      launch_rows_e4m3(cur, (long)nc * P, b.c1.cs_in, cur8, b.f8x_kp, s);
+    }
+    return cur8;
+  };
+  if (SPL && b.stride == 1 && ir_fused_ && ir_ws_ && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
+    ir_ws(nh, nw, 1, 0, 0, 0, 0);
+  } else if (FUSABLE && b.stride == 1 && ir_fused_ && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
+    const double P = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    f8 = b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    // the expand on e4m3 (x8 of the block input)
+    const uint8_t* const x8 = input8(f8 && f8_expand_ && b.f8_pw && X8[0], nh * nw);
+    launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, nh, nw, cs, M2, se_mean, SPL,
+                   2.0 * nc * P * b.mid * (b.c1.cin + 9), nc * P * ((x8 ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid),
+                   s, f8, x8, x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
+  } else if (SPL && b.stride == 2 && ir_fused_ && ir_ws_ && ir_ws_s2_ && big &&
+             ir_ws_s2_supported(oh, ow, b.c1.cs_in, b.c1.kp, cs, nh, nw, qt, ql)) {
+    ir_ws(oh, ow, 2, nh, nw, qt, ql);
+  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
+             nh * nw <= 64) {
+    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    // fp8 engines (blocks.5.0): e4m3 depthwise output for the e4m3 SE GEMM, the expand on e4m3 as for stride 1
+    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    const uint8_t* const x8 = input8(f8 && f8_expand_ && b.f8_pw && X8[0], oh * ow);
+    launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, oh, ow, nh, nw, qt, ql, cs, M2, se_mean,
+                      SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
+                      nc * ((x8 ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8, x8,
+                      x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
+  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_s2band_ &&
+             ir_s2band_supported(oh, ow, nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
+    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+    // fp8 engines (blocks.3.0): e4m3 depthwise output for the e4m3 SE GEMM (the expand stays bf16)
+    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, dw_w, dw_b, nh, nw, qt, ql, cs, M2, sums, SPL,
+                     2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
+                     nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
+    ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * ir_s2band_bands(nh) + es * nc * cs, s);
+    launch_se_mean<T>(sums, nc, ir_s2band_bands(nh), cs, 1.0f / (float)(nh * nw), se_mean, s);
+  } else {
+    ConvArgs e = pw_args(b.c1, cur, M, nc * oh * ow, oh * ow);
+    e.act = ACT_SILU;
+    run_conv<T>(e, b.c1, s);
+    {
+      ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
+                   kStoreBytes<T> * (double)nc * (oh * ow + nh * nw) * b.mid, s);
+      launch_dwconv<T>(M, nc, oh, ow, nh, nw, b.stride, qt, ql, b.mid, cs, dw_w, dw_b, M2, sums, s);
+    }
+    {
+      ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * dw_pixel_blocks(nh, nw) + kStoreBytes<T> * (double)nc * cs, s);
+      launch_se_mean<T>(sums, nc, dw_pixel_blocks(nh, nw), cs, 1.0f / (float)(nh * nw), se_mean, s);
+    }
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
+  const Block& b = p_.blocks[k];
+  const int nc = p.nc, cs = chan_stride(b.mid);
+  T *const se_mean = p.b.se_mean, *const se_hid = p.b.se_hid, *const scale = p.b.scale;
+  hipStream_t s = p.s;
+  if (kNotF32<T> && se_fused_ && se_excite_supported(b.rd, b.se2.kp, cs)) {
+    launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
+                     kSplit<T>, s);
+  } else {
+    ConvArgs r1 = pw_args(b.se1, se_mean, se_hid, nc, 1);  // conv_reduce + SiLU, all images of the chunk at once
+    r1.act = ACT_SILU;
+    run_conv<T>(r1, b.se1, s);
+    ConvArgs r2 = pw_args(b.se2, se_hid, scale, nc, 1);  // conv_expand + sigmoid -> per-(image, channel) gates
+    r2.act = ACT_SIGMOID;
+    run_conv<T>(r2, b.se2, s);
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
+  const Block& b = p_.blocks[k];
+  const int nc = p.nc, nh = p.nh, nw = p.nw, cs = chan_stride(b.mid), co = chan_stride(b.cout);
+  T *const cur = p.cur, *const nxt = p.nxt, *const M2 = p.b.M2, *const scale = p.b.scale;
+  uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
+  hipStream_t s = p.s;
+  const bool f8 = p.f8, sews = p.sews, mid_f32 = p.mid_f32;
+  const Block* const nb = k + 1 < p_.blocks.size() ? &p_.blocks[k + 1] : nullptr;
+  // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
+  // ir_pwdw_s2, whose input map is this block's nh x nw output)
+  const bool want8 = X8[0] && f8_expand_ && nb && nb->f8_pw &&
+                     (nb->stride == 1 ||
+                      (f8_s2_ && ir_fused_s2_supported(nh, nw, nb->c1.cs_in, chan_stride(nb->mid), false)));
+  // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
+  const int ld8 = want8 ? nb->f8x_kp : 0;
+  if (f8 && want8 && se_y8_) next8 = cur8 == X8[0] ? X8[1] : X8[0];
+  const double rows = (double)nc * nh * nw;
+  const void* const res = b.skip ? cur : nullptr;
+  if (f8 && se_ws_ && se_ws_f8_supported(nh * nw, cs, co)) {
+    launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
+                    arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
+                    rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
+                        (next8 ? rows * b.cout : 0.0),
+                    next8, ld8, ws_report());
+  } else if (f8) {
+    launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
+                      arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
+                      rows * cs + 2.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + (double)b.f8_npad * b.f8_kp +
+                          2.0 * nc * cs + (next8 ? rows * ld8 : 0.0),
+                      next8, ld8);
+  } else if (sews) {
+    launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
+                 2.0 * rows * b.mid * b.cout,
+                 4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
+                 ws_report(), mid_f32, sews_rev_);
+  } else if (kSplit<T> && se_sp_ && se_gemm_sp_supported(nh * nw, cs, co)) {
+    launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
+                      2.0 * rows * b.mid * b.cout,
+                      4.0 * rows * cs + 4.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
+                          4.0 * nc * cs);
+  } else {
+    ConvArgs q = pw_args(b.c2, M2, nxt, nc * nh * nw, nh * nw);
+    q.in_xform = IN_SE_SCALE;
+    q.in_scale = scale;
+    q.res = res;
+    run_conv<T>(q, b.c2, s);
+  }
+}
+
+template <typename T>
+void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe,
+                        int* probe_dims, Workspace& ws, hipStream_t s) {
+  M2S_CHECK(N > 0 && H >= 32 && W >= 32, "effnet: bad input size");
+  const int nc_max = pass_frames(N);
+  EffPass<T> p{};
+  p.b = effnet_bufs<T>(ws, N, H, W);
+  p.s = s;
+  T* const A = p.b.A;
+  int &oh = p.oh, &ow = p.ow;
+  T*& cur = p.cur;
+  const float *const stem_w = arena_.at<float>(p_.stem_w), *const stem_b = arena_.at<float>(p_.stem_b);
+  for (int n0 = 0; n0 < N; n0 += nc_max) {
+    const int nc = std::min(nc_max, N - n0);
+    p.nc = nc;
+    p.n0 = n0;
+    int pt, pl;
+    same_pad(H, 3, 2, &oh, &pt);
+    same_pad(W, 3, 2, &ow, &pl);
+    // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
+    constexpr bool SPL = kSplit<T>;
+    const bool front = kNotF32<T> && stem_fused_ && !(probe && stop_after >= 0 && stop_after < 2) &&
+                       p_.blocks.size() >= 2 && p_.blocks[0].type == 0 && p_.blocks[0].stride == 1 && !p_.blocks[0].skip &&
+                       p_.blocks[0].cout == 16 && p_.blocks[0].c1.cs_in == 32 && p_.blocks[0].c1.kp == 288 &&
+                       p_.blocks[1].type == 0 && p_.blocks[1].stride == 1 && p_.blocks[1].skip && p_.blocks[1].cout == 16 &&
+                       p_.blocks[1].c1.cs_in == 16 && p_.blocks[1].c1.kp == 160 && chan_stride(16) == 16;
+    cur = A;
+    p.nxt = p.b.B;
+    p.cur8 = nullptr;
+    int cc = EFF_STEM;
+    int bi = 0;
+    if (front) {
+      const double px = (double)nc * oh * ow;
+      launch_stem_b0(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, stem_w, stem_b, p_.blocks[0].c1.w,
+                     p_.blocks[0].c1.b, p_.blocks[0].c1.kp, p_.blocks[1].c1.w, p_.blocks[1].c1.b, p_.blocks[1].c1.kp, A, SPL,
+                     2.0 * px * (EFF_STEM * 9 + 16 * 9 * 32 + 16 * 9 * 16), 4.0 * nc * H * W + (SPL ? 4.0 : 2.0) * px * 16, s);
+      cc = 16;
+      bi = 2;
+    } else {
+      ProfScope ps(std::is_same<T, bf16_t>::value ? std::string("stem32_kernel") : tname<T>("stem_kernel"), 2.0 * nc * oh * ow * EFF_STEM * 27, 4.0 * nc * H * W + kStoreBytes<T> * (double)nc * oh * ow * 32, s);
+      launch_stem<T>(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, stem_w, stem_b, EFF_STEM,
+                     chan_stride(EFF_STEM), A, s);
+    }
+    auto tap = [&](int done) {
+      if (stop_after == done && probe) {
+        launch_unpad<T>(cur, (long)nc * oh * ow, cc, chan_stride(cc), probe + (size_t)n0 * oh * ow * cc, s);
+        if (probe_dims) {
+          probe_dims[0] = oh;
+          probe_dims[1] = ow;
+          probe_dims[2] = cc;
+        }
+        return true;
+      }
+      return false;
+    };
+    if (tap(bi)) continue;  // bi = 0, or 2 after the fused front
+    bool stopped = false;
+    for (size_t k = front ? 2 : 0; k < p_.blocks.size(); ++k) {
+      const Block& b = p_.blocks[k];
+      p.next8 = nullptr;  // the e4m3 copy of this block's output, if the block wrote one
+      same_pad(oh, 3, b.stride, &p.nh, &p.qt);
+      same_pad(ow, 3, b.stride, &p.nw, &p.ql);
+      if (b.type == 0) {
+        effnet_cn(p, k);
+      } else if (b.type == 1) {
+        effnet_er(p, k);
+      } else {
+        effnet_ir_front(p, k);
+        effnet_ir_se(p, k);
+        effnet_ir_pwl(p, k);
+      }
+      std::swap(cur, p.nxt);
+      p.cur8 = p.next8;
+      oh = p.nh;
+      ow = p.nw;
+      cc = b.cout;
+      ++bi;
+      if (tap(bi)) {
+        stopped = true;
+        break;
+      }
+    }
+    if (stopped || !feats) continue;
+    ProfScope ps(tname<T>("gap_kernel"), (double)nc * oh * ow * cc, kStoreBytes<T> * (double)nc * oh * ow * cc, s);
+    launch_gap<T>(cur, nc, oh * ow, cc, chan_stride(cc), feats + (size_t)n0 * EFF_OUT, s);
+  }
+}
+
+}  // namespace m2s

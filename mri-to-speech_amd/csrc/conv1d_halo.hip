@@ -255,7 +255,7 @@ void launch_c(const ConvBatch& b, int n, int B, int L, hipStream_t s, double flo
 // the MRF sum in registers, rounded to hi + lo of its split between pairs as the stored sum is.
 // Same MFMAs in the same order per output as the two launches: bit-identical to them.  C = 128 (8 waves, one
 // workgroup per CU) measured level with conv_gemm's batches for its stage (2.18 vs 2.19 ms), so only C = 64 is
-// routed here by default (model.cpp, M2S_MRF_PAIR128).
+// routed here by default (vocoder.cpp, M2S_MRF_PAIR128).
 constexpr int H2_BM = 112;
 constexpr int H2_HALO = H1_BM - H2_BM;  // 16 rows of the intermediate ahead of the tile
 

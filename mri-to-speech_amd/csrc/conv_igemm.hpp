@@ -48,11 +48,11 @@ struct ConvArgs {
   int in_xform; float in_slope;
   int accum;            // 0: y = v ; 1: y = y_prev + v ; 2: y = (y_prev + v) / accum_div
   float accum_div;
-  // split conv_gemm only (the pre-activated MRF chain, model.cpp Vocoder::run_t):
+  // split conv_gemm only (the pre-activated MRF chain, vocoder.cpp Vocoder::run_t):
   float res_unslope;    // != 0: res holds lrelu(x); x = r > 0 ? r : r * res_unslope (slope 0.1 -> 10)
   int act_after_res;    // act applied after the residual add (y = lrelu(v + x)) instead of before it
   // fp32 conv_igemm only: the four waves of a workgroup split the K chunks of one wave's rows (the BiLSTM input
-  // projection of a small pass, model.cpp)
+  // projection of a small pass, acoustic_rnn.cpp)
   int kwave;
 };
 

@@ -1,6 +1,6 @@
 // InvertedResidual middle: depthwise 3x3 + BN + SiLU with the SE squeeze (timm conv_dw / bn2 /
 // se.*; mri_acoustic_model.py:28-34 builds them).  The SE excitation itself (conv_reduce -> SiLU
-// -> conv_expand -> sigmoid over all images at once) runs as two GEMMs on MFMA (model.cpp); this
+// -> conv_expand -> sigmoid over all images at once) runs as two GEMMs on MFMA (acoustic_cnn.cpp); this
 // file provides the depthwise conv and the squeeze (channel means) that feeds them.
 #include "kernels.hpp"
 

@@ -34,6 +34,10 @@ class Arena {
   }
   void upload(int device);
   void* ptr(size_t off) const { return static_cast<char*>(dev_) + off; }
+  template <class T>
+  const T* at(size_t off) const {  // ptr(off) as the packed array's element type
+    return static_cast<const T*>(ptr(off));
+  }
   size_t bytes() const { return bytes_; }                  // staged so far (kept across upload)
   const uint8_t* host() const { return host_.data(); }     // the staged bytes, until upload()
   ~Arena();
@@ -59,8 +63,8 @@ struct PConv {
   const float* wscale = nullptr;   // [n_pad] when fp8
   void resolve(const Arena& a) {
     w = a.ptr(w_off);
-    b = static_cast<const float*>(a.ptr(b_off));
-    wscale = fp8 ? static_cast<const float*>(a.ptr(ws_off)) : nullptr;
+    b = a.at<float>(b_off);
+    wscale = fp8 ? a.at<float>(ws_off) : nullptr;
   }
 };
 
@@ -220,6 +224,23 @@ struct RB {
     const float* bp = nullptr;
   };
   std::vector<F8> q1, q2;
+  void resolve(const Arena& a) {
+    for (auto* cv : {&c1, &c2})
+      for (PConv& c : *cv) c.resolve(a);
+    auto frags = [&](const std::vector<size_t>& off, std::vector<const bf16_t*>& v) {
+      for (size_t o : off) v.push_back(a.at<bf16_t>(o));
+    };
+    frags(f1_off, f1);
+    frags(f2_off, f2);
+    frags(h1_off, h1);
+    frags(h2_off, h2);
+    for (auto* qv : {&q1, &q2})
+      for (F8& f : *qv) {
+        f.wp = a.ptr(f.w);
+        f.sp = a.at<float>(f.s);
+        f.bp = a.at<float>(f.b);
+      }
+  }
 };
 
 struct VocoderPlan {
@@ -335,6 +356,8 @@ class Acoustic {
     void* hop[2] = {nullptr, nullptr};
   };
   WindowBufs window_bufs(Workspace& ws, const WindowPlan& p) const;
+  // the size query of a windowed or pairs plan: with the CNN's scratch in front unless H = W = 0
+  size_t window_query(const WindowPlan& p, int H, int W) const;
   void window_steps(const float* feats, const WindowPlan& p, const WindowBufs& b, hipStream_t s);
   template <typename T>
   struct EffBufs {  // one CNN pass of pass_frames(N) frames
@@ -348,6 +371,12 @@ class Acoustic {
   EffBufs<T> effnet_bufs(Workspace& ws, int N, int H, int W) const;
   void effnet_ws(Workspace& ws, int N, int H, int W) const;  // effnet_bufs of the engine's dtype
   float* feats_buf(Workspace& ws, size_t rows) const;         // precedes the CNN in the forward* calls
+  // the forward* calls' CNN leg: feats_buf, then the GAP features of N frames in it
+  float* cnn_feats(const float* frames, long N, int H, int W, Workspace& ws, hipStream_t s);
+  // the BiLSTM input projection (lstm_ih GEMM) of `rows` feature rows; kwave: ConvArgs::kwave, the caller's choice
+  void project(const float* feats, float* pre, long rows, int kwave, hipStream_t s);
+  // the mel head on `rows` rows of h under stage "head": [fwd | bwd] planes, or merged rows (one plane)
+  void head(const float* h, long rows, bool merged, float* mel_norm, hipStream_t s);
   struct LstmBufs {
     float *pre, *hs, *cst;
     void* sync;

@@ -1,5 +1,5 @@
 // Host-side packing helpers shared by the packers (pack_acoustic.cpp, pack_vocoder.cpp), the model plans
-// (model.cpp) and the Grad-CAM path (cam.cpp):
+// (acoustic_cnn.cpp, acoustic_rnn.cpp, vocoder.cpp) and the Grad-CAM path (cam.cpp):
 //   * state-dict lookup, host bf16 / split / e4m3 conversions, per-channel e4m3 scales (channel_scales);
 //   * the MFMA operand fragment writers, the one definition of each lane order: frag_bf16 (plain K),
 //     frag_bf16_pwl (er_fused.hip's permuted K) and frag_e4m3, with the emit policy Plane (bf16 / hi / lo);

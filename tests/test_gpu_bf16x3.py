@@ -203,7 +203,7 @@ def test_er_sp_merged_ring_stages_are_bit_identical(rt, ac_state, monkeypatch):
 @pytest.mark.parametrize("B,T", [(1, 5), (3, 17), (4, 40)])
 def test_vocoder_bf16x3_mrf_batched(rt, monkeypatch, B, T):
     """The batched split MRF stages (one launch per pair for every resblock, grid.z = resblock;
-    LeakyReLU applied once by the producer and inverted for the residual: model.cpp
+    LeakyReLU applied once by the producer and inverted for the residual: vocoder.cpp
     mrf_stage_batched) against the oracle at the fp32 bar, the C = 64 / 128 halo-staged convs
     (conv1d_halo.hip) against the same batches through conv_gemm, and against the per-conv launches.
     T = 5 gives clips shorter than a 128-row tile at C = 128, T = 40 ragged tiles."""

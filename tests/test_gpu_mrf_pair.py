@@ -1,4 +1,4 @@
-"""The fused ResBlock1 pair of the split-fp32 C = 64 MRF stage (conv1d_halo.hip conv1d_halo_pair_kernel; model.cpp
+"""The fused ResBlock1 pair of the split-fp32 C = 64 MRF stage (conv1d_halo.hip conv1d_halo_pair_kernel; vocoder.cpp
 mrf_stage_batched, engine switch M2S_MRF_PAIR) against the launch-per-conv path it replaces (M2S_MRF_PAIR=0).
 
 Both convs of a pair keep their stage order and the tensor between them is the split4 value the c1 launch stores, so
