@@ -5,7 +5,12 @@ Tolerances (fp32 path; the reference runs fp32 on CPU):
   * BiLSTM / head          max |dy|    <= 2e-5 / 5e-5
   * CNN features / taps    max |d| / max|ref| <= 1e-4 (relative to the tensor's scale)
   * mel_norm end to end    max |d|     <= 1e-4 ; mel_log <= 5e-4 (x ln10/10 * std amplification)
-bf16 path (compute dtype of configs[1]): waveform SNR >= 25 dB, mel cosine >= 0.999 / max |d| <= 5e-2.
+bf16 path (compute dtype of configs[1]), aggregate bars only:
+  * vocoder waveform       SNR >= 25 dB vs the oracle (the fused MRF within 1.5 dB of the per-conv path)
+  * CNN taps / features    cosine >= 0.999 vs the oracle; fused vs unfused kernels max |d| / max|ref| <= 2e-2 per tap
+                           and cosine >= 0.99999 on the pooled features
+  * end to end             mel_norm max |d| <= 5e-2, waveform SNR >= 20 dB
+The bf16 early-CNN kernels are held element by element in tests/test_gpu_lowprec.py.
 """
 import json
 import os
