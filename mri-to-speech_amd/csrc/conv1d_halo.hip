@@ -27,12 +27,11 @@
 
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
-
-__device__ __attribute__((aligned(16))) uint4 g_h1_zero[4];
 
 constexpr int H1_BM = 128;               // output rows per tile
 constexpr int H1_HIST = 64;              // history rows: (k - 1) d <= 64
@@ -50,18 +49,6 @@ constexpr int h1_slots() {  // weight ring depth: stages in flight = slots - 1 (
 template <int C>
 constexpr int h1_lds() {
   return 2 * (C / 8) * H1_PLANE + h1_slots<C>() * h1_stage<C>();
-}
-
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(lds_wave_base)
-               : "memory");
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 template <int C>
@@ -90,8 +77,7 @@ __global__ void __launch_bounds__(64 * h1_waves<C>(), 2) conv1d_halo_sp_kernel(c
   const int Q = a.ntaps * KC;  // weight stages
   const bf16_t* __restrict__ X = static_cast<const bf16_t*>(a.x);
   const char* W = static_cast<const char*>(a.w);
-  const char* zp = reinterpret_cast<const char*>(g_h1_zero);
-  asm volatile("" : "+s"(zp));
+  const char* zp = zero_page();
   const uint32_t img0 = (uint32_t)(uintptr_t)img, ring0 = (uint32_t)(uintptr_t)ring;
 
   // ---- the epilogue's residual and MRF-sum operands, fetched first: read at the end of the tile they
@@ -128,14 +114,14 @@ __global__ void __launch_bounds__(64 * h1_waves<C>(), 2) conv1d_halo_sp_kernel(c
       const void* src = tt >= 0 && tt < L
                             ? static_cast<const void*>(X + ((size_t)clip * L + tt) * (2 * a.cs_in) + half * a.cs_in + ch * 8)
                             : static_cast<const void*>(zp);
-      dma16(src, __builtin_amdgcn_readfirstlane(img0 + (uint32_t)(p * H1_PLANE + rb * 1024)));
+      dma16_asm(src, __builtin_amdgcn_readfirstlane(img0 + (uint32_t)(p * H1_PLANE + rb * 1024)));
     }
   }
   auto issue = [&](int q) {  // weight stage q -> slot q % SLOTS: this wave's PPW pieces
     const char* src = W + (size_t)q * STAGE + (wave * PPW) * 1024 + lane * 16;
     const uint32_t dst = ring0 + (uint32_t)((q % SLOTS) * STAGE + wave * PPW * 1024);
 #pragma unroll
-    for (int j = 0; j < PPW; ++j) dma16(q < Q ? static_cast<const void*>(src + j * 1024) : static_cast<const void*>(zp), dst + j * 1024);
+    for (int j = 0; j < PPW; ++j) dma16_asm(q < Q ? static_cast<const void*>(src + j * 1024) : static_cast<const void*>(zp), dst + j * 1024);
   };
 #pragma unroll
   for (int q = 0; q < SLOTS - 1; ++q) issue(q);
@@ -282,8 +268,7 @@ __global__ void __launch_bounds__(64 * h1_waves<C>(), 2) conv1d_halo_pair_kernel
   const int wr = wave & 3, ntb = (wave >> 2) * NTW;
   const int clip = blockIdx.x / tiles, tile = blockIdx.x - clip * tiles;
   const int L = pb.L, t0 = tile * H2_BM;
-  const char* zp = reinterpret_cast<const char*>(g_h1_zero);
-  asm volatile("" : "+s"(zp));
+  const char* zp = zero_page();
   const uint32_t img0 = (uint32_t)(uintptr_t)img, ring0 = (uint32_t)(uintptr_t)ring;
   const int njobs = pb.chain ? pb.n : 1;
 
@@ -343,7 +328,7 @@ __global__ void __launch_bounds__(64 * h1_waves<C>(), 2) conv1d_halo_pair_kernel
         const void* src = tt >= 0 && tt < L
                               ? static_cast<const void*>(X + ((size_t)clip * L + tt) * (2 * C) + half * C + ch * 8)
                               : static_cast<const void*>(zp);
-        dma16(src, __builtin_amdgcn_readfirstlane(img0 + (uint32_t)(p * H1_PLANE + rb * 1024)));
+        dma16_asm(src, __builtin_amdgcn_readfirstlane(img0 + (uint32_t)(p * H1_PLANE + rb * 1024)));
       }
     }
     auto issue = [&](int q) {  // weight stage q of the pair -> slot q % SLOTS
@@ -352,7 +337,7 @@ __global__ void __launch_bounds__(64 * h1_waves<C>(), 2) conv1d_halo_pair_kernel
       const uint32_t dst = ring0 + (uint32_t)((q % SLOTS) * STAGE + wave * PPW * 1024);
 #pragma unroll
       for (int j = 0; j < PPW; ++j)
-        dma16(q < Q ? static_cast<const void*>(src + j * 1024) : static_cast<const void*>(zp), dst + j * 1024);
+        dma16_asm(q < Q ? static_cast<const void*>(src + j * 1024) : static_cast<const void*>(zp), dst + j * 1024);
     };
 #pragma unroll
     for (int q = 0; q < SLOTS - 1; ++q) issue(q);

@@ -18,21 +18,16 @@
 
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
 
-__device__ __attribute__((aligned(16))) uint4 g_halo_zero[4];  // DMA source for padding pixels
-
 constexpr int ROWB = 64;  // bytes per LDS row (32 bf16 = one k-step of one pixel)
 constexpr int TW = 16;    // output tile width (one MFMA position subtile = one tile row)
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * ROWB + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
 
 __device__ __forceinline__ void ld4f(const bf16_t* p, float* v) {
   const uint2 u = *reinterpret_cast<const uint2*>(p);
@@ -83,10 +78,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const HaloArgs a) {
   const int mstride = gridDim.x / a.n_tiles;
   int mt = blockIdx.x / a.n_tiles;
 
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_halo_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   // ---- weights of this N tile -> LDS, once ----------------------------------------------------
   for (int blk = wave; blk < nsteps * BN / 16; blk += 4) {
     const int row = blk * 16 + lrow, st = row / BN, n = n0 + (row - st * BN);
@@ -118,7 +110,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const HaloArgs a) {
   };
 
   if (mt < a.m_tiles) issue_halo(mt, hbuf0);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  wait_vm<0>();
   __builtin_amdgcn_s_barrier();
 
   for (int it = 0; mt < a.m_tiles; mt += mstride, ++it) {
@@ -172,7 +164,7 @@ __global__ void __launch_bounds__(256) conv_halo_kernel(const HaloArgs a) {
         }
     }
     // the next halo has landed (it had the whole K loop) and every wave is done with this one
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __builtin_amdgcn_s_barrier();
 
     // ---- epilogue: 4 consecutive channels of one position per lane ----------------------------

@@ -7,11 +7,6 @@
 namespace m2s {
 namespace {
 
-template <typename T>
-__device__ __forceinline__ float silu_t(float v) {
-  return sizeof(T) == 4 ? silu_exact(v) : silu(v);
-}
-
 // ---------------------------------------------------------------------------------------------
 // Depthwise.  Workgroup = 256 channels (512 contiguous bytes of every pixel row in bf16) x
 // DW_PIX output pixels: DW_PIX / P whole images when an image is smaller, else one pixel block of

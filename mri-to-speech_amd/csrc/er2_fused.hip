@@ -14,15 +14,14 @@
 #include <cstdio>
 #include <type_traits>
 
+#include "er_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
 
-__device__ __attribute__((aligned(16))) uint4 g_er2_zero[4];
-
-constexpr int E2_TW = 16, E2_HW = 18, E2_HPIX = E2_HW * E2_HW;
+constexpr int E2_TW = 16, E2_HW = 18;
 constexpr int E2_PLANE = 384 * 16;          // 6 pieces of 64 pixels
 constexpr int E2_BUF = 8 * E2_PLANE;        // 64 channels = 8 planes (48 KB)
 constexpr int E2_STAGE = 16 * 1024;         // 16 pieces
@@ -39,24 +38,6 @@ struct Er2Args {
   int N, H, W, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-// LDS reads the compiler does not see: an ordinary ds_read after an LDS-DMA gets a conservative
-// s_waitcnt vmcnt(0), which would drain the ring's prefetch.  These wait only for themselves.
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-__device__ __forceinline__ uint2 lds_u2(const void* p) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_off(p)));
-  return r;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 __global__ void __launch_bounds__(512, 1) er2_fused_kernel(const Er2Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* ring = smem;                                              // 3 x 16 KB
@@ -67,10 +48,7 @@ __global__ void __launch_bounds__(512, 1) er2_fused_kernel(const Er2Args a) {
   const int g = lane >> 4, r16 = lane & 15;
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
 
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_er2_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto stage_dma = [&](int ls, int slot) {  // 2 pieces per wave
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -79,18 +57,8 @@ __global__ void __launch_bounds__(512, 1) er2_fused_kernel(const Er2Args a) {
     }
   };
   auto halo_dma = [&](int tile, char* buf) {  // 6 pieces per wave: 8 planes x 6 pixel blocks
-    const int n = tile / tpi, tr = tile - n * tpi;
-    const int ty0 = (tr / a.tiles_x) * E2_TW - 1, tx0 = (tr - (tr / a.tiles_x) * a.tiles_x) * E2_TW - 1;
-    const bf16_t* xi = a.x + (size_t)n * a.H * a.W * 64;
-#pragma unroll
-    for (int j = 0; j < 6; ++j) {
-      const int piece = wave * 6 + j, c = piece / 6, pb = piece - c * 6;
-      const int p = pb * 64 + lane, hy = p / E2_HW, hx = p - hy * E2_HW;
-      const int iy = ty0 + hy, ix = tx0 + hx;
-      const void* src = zpage;
-      if (p < E2_HPIX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) src = xi + ((size_t)iy * a.W + ix) * 64 + c * 8;
-      dma16(src, buf + c * E2_PLANE + pb * 1024);
-    }
+    const TilePos t = tile_pos<E2_TW, E2_TW>(tile, tpi, a.tiles_x);
+    halo_planes_dma<E2_TW, 64, 6>(a.x + (size_t)t.n * a.H * a.W * 64, a.H, a.W, t, wave, lane, zpage, buf);
   };
 
   for (int i = tid; i < E2_MID; i += 512) bexp_l[i] = a.bexp[i];
@@ -108,8 +76,8 @@ __global__ void __launch_bounds__(512, 1) er2_fused_kernel(const Er2Args a) {
   for (int it = 0, tile = blockIdx.x; tile < ntiles; tile += gridDim.x, ++it) {
     const bool has_next = tile + (int)gridDim.x < ntiles;
     const char* hb = hbuf + (it & 1) * E2_BUF;
-    const int n = tile / tpi, tr = tile - n * tpi;
-    const int oy0 = (tr / a.tiles_x) * E2_TW, ox = (tr - (tr / a.tiles_x) * a.tiles_x) * E2_TW + r16;
+    const TilePos t = tile_pos<E2_TW, E2_TW>(tile, tpi, a.tiles_x);
+    const int n = t.n, oy0 = t.y0, ox = t.x0 + r16;
 
     f32x4 acc[2][E2_NT];
 #pragma unroll

@@ -28,17 +28,12 @@
 // LDS-DMA makes hipcc drain the DMA in flight), the conv_exp weight fragments three deep.
 #include <algorithm>
 
+#include "er_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int E8M0_ONE = 0x7f7f7f7f;
-
-__device__ __attribute__((aligned(16))) uint4 g_er8_zero[4];  // DMA source for padding pixels
 
 constexpr int E8_TW = 16, E8_TH = 8;                        // tile: 8 rows x 16 pixels per half-workgroup
 constexpr int E8_HW = E8_TW + 2, E8_HH = E8_TH + 2;         // halo 10 x 18
@@ -71,20 +66,6 @@ struct Er8Args {
   int N, H, W, tiles_x, tiles_y;  // 8 x 16 tiles
 };
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ i32x8 cat8(u32x4 a, u32x4 b) {
-  return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-}
-
 template <bool X8, bool Y8>
 __global__ void __launch_bounds__(512, 1) er8_fused_kernel(const Er8Args a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -107,13 +88,10 @@ __global__ void __launch_bounds__(512, 1) er8_fused_kernel(const Er8Args a) {
   const int J = count(half), J0 = count(0);
 
   // this wave's 3 halo pieces of tile T: plane c, 64-pixel block pb
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_er8_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto issue_halo = [&](int T, char* buf) {
-    const int n = T / tpi, tr = T - n * tpi;
-    const int ty0 = (tr / a.tiles_x) * E8_TH - 1, tx0 = (tr - (tr / a.tiles_x) * a.tiles_x) * E8_TW - 1;
+    const TilePos t = tile_pos<E8_TH, E8_TW>(T, tpi, a.tiles_x);
+    const int n = t.n, ty0 = t.y0 - 1, tx0 = t.x0 - 1;
     const bf16_t* xi = a.x + (size_t)n * a.H * a.W * 32;
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
@@ -128,8 +106,8 @@ __global__ void __launch_bounds__(512, 1) er8_fused_kernel(const Er8Args a) {
   char* hb_half = hbuf + half * 2 * E8_BUF;
   // X8: this wave's pieces (lw, lw + 4 < 6) of tile T's e4m3 halo: plane pl, 64-pixel block pb
   auto issue_halo8 = [&](int T, char* buf) {
-    const int n = T / tpi, tr = T - n * tpi;
-    const int ty0 = (tr / a.tiles_x) * E8_TH - 1, tx0 = (tr - (tr / a.tiles_x) * a.tiles_x) * E8_TW - 1;
+    const TilePos t = tile_pos<E8_TH, E8_TW>(T, tpi, a.tiles_x);
+    const int n = t.n, ty0 = t.y0 - 1, tx0 = t.x0 - 1;
     const uint8_t* xi = a.x8 + (size_t)n * a.H * a.W * 32;
     for (int piece = lw; piece < 6; piece += 4) {
       const int pl = piece / 3, pb = piece - pl * 3;
@@ -282,8 +260,8 @@ __global__ void __launch_bounds__(512, 1) er8_fused_kernel(const Er8Args a) {
         }
       }
       // conv_pwl (one K = 128 MFMA per 16 output channels) + scale + bn2 bias + shortcut
-      const int n = T / tpi, tr = T - n * tpi;
-      const int oy0 = (tr / a.tiles_x) * E8_TH, ox = (tr - (tr / a.tiles_x) * a.tiles_x) * E8_TW + r16;
+      const TilePos t = tile_pos<E8_TH, E8_TW>(T, tpi, a.tiles_x);
+      const int n = t.n, oy0 = t.y0, ox = t.x0 + r16;
 #pragma unroll
       for (int i = 0; i < 2; ++i) {
         const int ry = 2 * lw + i, oy = oy0 + ry;

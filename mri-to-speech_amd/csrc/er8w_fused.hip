@@ -23,17 +23,12 @@
 // neither counts it nor drains it before the LDS reads).
 #include <algorithm>
 
+#include "er_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
-
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-constexpr int E8M0_ONE = 0x7f7f7f7f;
-
-__device__ __attribute__((aligned(16))) uint4 g_er8w_zero[4];  // DMA source for padding pixels
 
 constexpr int EW_T = 16, EW_HW = 18, EW_HPIX = EW_HW * EW_HW;  // 16 x 16 tile, 18 x 18 halo
 constexpr int EW_MID = 224, EW_NT = 14, EW_ON = 4, EW_QS = 5;  // mid channels, n16 tiles, out n16 tiles, K steps
@@ -63,24 +58,6 @@ struct Er8wArgs {
   int N, H, W, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(lds_wave_base)
-               : "memory");
-}
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return __builtin_amdgcn_readfirstlane((uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-__device__ __forceinline__ i32x8 cat8(u32x4 a, u32x4 b) {
-  return i32x8{(int)a[0], (int)a[1], (int)a[2], (int)a[3], (int)b[0], (int)b[1], (int)b[2], (int)b[3]};
-}
-
 template <bool Y8>
 __global__ void __launch_bounds__(512, 1) er8w_fused_kernel(const Er8wArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -89,14 +66,11 @@ __global__ void __launch_bounds__(512, 1) er8w_fused_kernel(const Er8wArgs a) {
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int r16 = lane & 15;  // (the lane group g is rebuilt per stage from an opaque lane id)
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
-  const uint32_t sm0 = lds_off(smem);
+  const uint32_t sm0 = lds_off_u(smem);
 
   // stage ls of the stream -> ring slot: conv_exp K steps 4 pieces a wave (n16 tiles 2 wave, 2 wave + 1), the
   // conv_pwl stage 2 pieces a wave
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_er8w_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto stage_dma = [&](int ls, int slot) {
     int ln = lane;
     asm volatile("" : "+v"(ln));  // rebuilt per call: hoisted lane offsets cost registers
@@ -105,20 +79,20 @@ __global__ void __launch_bounds__(512, 1) er8w_fused_kernel(const Er8wArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int piece = wave * 4 + j;
-        dma16(a.wst + ((size_t)ls * 32 + piece) * 1024 + ln * 16, dst + piece * 1024);
+        dma16_asm(a.wst + ((size_t)ls * 32 + piece) * 1024 + ln * 16, dst + piece * 1024);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const int piece = wave * 2 + j;
-        dma16(a.wst + ((size_t)EW_QS * 32 + piece) * 1024 + ln * 16, dst + piece * 1024);
+        dma16_asm(a.wst + ((size_t)EW_QS * 32 + piece) * 1024 + ln * 16, dst + piece * 1024);
       }
     }
   };
   // tile T's e4m3 halo: 2 planes x 12 pieces of 32 pixels (a lane = half a pixel), 3 pieces a wave
   auto halo_dma = [&](int T, int buf) {
-    const int n = T / tpi, tr = T - n * tpi;
-    const int ty0 = (tr / a.tiles_x) * EW_T - 1, tx0 = (tr - (tr / a.tiles_x) * a.tiles_x) * EW_T - 1;
+    const TilePos t = tile_pos<EW_T, EW_T>(T, tpi, a.tiles_x);
+    const int n = t.n, ty0 = t.y0 - 1, tx0 = t.x0 - 1;
     const uint8_t* xi = a.x8 + (size_t)n * a.H * a.W * 64;
     int ln = lane;
     asm volatile("" : "+v"(ln));
@@ -130,7 +104,7 @@ __global__ void __launch_bounds__(512, 1) er8w_fused_kernel(const Er8wArgs a) {
       const void* src = zpage;
       if (hp < EW_HPIX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W)
         src = xi + ((size_t)iy * a.W + ix) * 64 + pl * 32 + (ln & 1) * 16;
-      dma16(src, sm0 + (uint32_t)(EW_HALO0 + buf * EW_BUF + (pl ? EW_PB : 0) + pb * 1024));
+      dma16_asm(src, sm0 + (uint32_t)(EW_HALO0 + buf * EW_BUF + (pl ? EW_PB : 0) + pb * 1024));
     }
   };
 
@@ -157,8 +131,8 @@ __global__ void __launch_bounds__(512, 1) er8w_fused_kernel(const Er8wArgs a) {
     const bool hn = tile + (int)gridDim.x < ntiles;  // has a next tile (uniform)
     const int buf = it & 1;
     const uint32_t hb = sm0 + (uint32_t)(EW_HALO0 + buf * EW_BUF);
-    const int n = tile / tpi, tr = tile - n * tpi;
-    const int oy0 = (tr / a.tiles_x) * EW_T, ox = (tr - (tr / a.tiles_x) * a.tiles_x) * EW_T + r16;
+    const TilePos t = tile_pos<EW_T, EW_T>(tile, tpi, a.tiles_x);
+    const int n = t.n, oy0 = t.y0, ox = t.x0 + r16;
 
     f32x4 acc[2][EW_NT];
 #pragma unroll

@@ -17,16 +17,14 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "er_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
 
-__device__ __attribute__((aligned(16))) uint4 g_er_zero[4];  // DMA source for padding pixels
-
 constexpr int ER_TW = 16, ER_HW = 18;            // tile / halo width
-constexpr int ER_HPIX = ER_HW * ER_HW;           // 324 halo pixels
 constexpr int ER_PLANE = 384 * 16;               // 6 DMA pieces of 64 pixels per plane (24 x 256 B)
 constexpr int ER_BUF = 4 * ER_PLANE;             // 4 planes of 8 channels
 constexpr int ER_WEXP = 9 * 8 * 1024;            // conv_exp fragments: [tap][n16][lane][16 B]
@@ -41,23 +39,6 @@ struct ErArgs {
   int N, H, W, tiles_x, tiles_y;
 };
 
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-// An LDS read the compiler does not see: an ordinary ds_read after an LDS-DMA (the next tile's halo)
-// gets a conservative s_waitcnt vmcnt(0), which would also wait for this tile's stores.
-__device__ __forceinline__ uint2 lds_u2(const void* p) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)"
-               : "=v"(r)
-               : "v"((uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p));
-  return r;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 __global__ void __launch_bounds__(512, 1) er_fused_kernel(const ErArgs a) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* wl = smem;                 // conv_exp fragments
@@ -67,24 +48,11 @@ __global__ void __launch_bounds__(512, 1) er_fused_kernel(const ErArgs a) {
   const int g = lane >> 4, r16 = lane & 15;
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
 
-  // this wave's 3 halo pieces per tile: plane c, 64-pixel block pb
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_er_zero;
-  asm volatile("" : "+s"(zpage));
+  // this wave's 3 halo pieces per tile (4 planes x 6 pixel blocks over 8 waves)
+  const void* zpage = zero_page();
   auto issue_halo = [&](int tile, char* buf) {
-    const int n = tile / tpi, tr = tile - n * tpi;
-    const int ty0 = (tr / a.tiles_x) * ER_TW - 1, tx0 = (tr - (tr / a.tiles_x) * a.tiles_x) * ER_TW - 1;
-    const bf16_t* xi = a.x + (size_t)n * a.H * a.W * 32;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-      const int piece = wave * 3 + j, c = piece / 6, pb = piece - c * 6;
-      const int p = pb * 64 + lane, hy = p / ER_HW, hx = p - hy * ER_HW;
-      const int iy = ty0 + hy, ix = tx0 + hx;
-      const void* src = zpage;
-      if (p < ER_HPIX && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W) src = xi + ((size_t)iy * a.W + ix) * 32 + c * 8;
-      dma16(src, buf + c * ER_PLANE + pb * 1024);
-    }
+    const TilePos t = tile_pos<ER_TW, ER_TW>(tile, tpi, a.tiles_x);
+    halo_planes_dma<ER_TW, 32, 3>(a.x + (size_t)t.n * a.H * a.W * 32, a.H, a.W, t, wave, lane, zpage, buf);
   };
 
   // ---- once: conv_exp fragments -> LDS (9 pieces per wave); conv_pwl fragments + biases -> VGPRs -
@@ -139,8 +107,8 @@ __global__ void __launch_bounds__(512, 1) er_fused_kernel(const ErArgs a) {
     }
 
     // ---- bias + SiLU -> bf16 B fragments of conv_pwl (permuted K) -> conv_pwl -------------------
-    const int n = tile / tpi, tr = tile - n * tpi;
-    const int oy0 = (tr / a.tiles_x) * ER_TW, ox = (tr - (tr / a.tiles_x) * a.tiles_x) * ER_TW + r16;
+    const TilePos t = tile_pos<ER_TW, ER_TW>(tile, tpi, a.tiles_x);
+    const int n = t.n, oy0 = t.y0, ox = t.x0 + r16;
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
       f32x4 o[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
@@ -157,7 +125,8 @@ __global__ void __launch_bounds__(512, 1) er_fused_kernel(const ErArgs a) {
 #pragma unroll
         for (int on = 0; on < 2; ++on) o[on] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wp[on][ks], mb, o[on], 0, 0, 0);
       }
-      // + bn2 bias + shortcut (the tile's centre pixels of the halo buffer); 4 channels per lane
+      // + bn2 bias + shortcut (the tile's centre pixels of the halo buffer, read through lds_u2: an ordinary read
+      // would also wait for the next tile's halo and this tile's stores); 4 channels per lane
       const int ry = 2 * wave + i, oy = oy0 + ry;
 #pragma unroll
       for (int on = 0; on < 2; ++on) {

@@ -26,35 +26,12 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
 
-__device__ __attribute__((aligned(16))) uint4 g_ersp_zero[4];
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ uint32_t lds_off(const void* p) {
-  return (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)p;
-}
-// LDS read the compiler does not see (an ordinary ds_read after an LDS-DMA gets a conservative
-// vmcnt(0), which would drain the ring's prefetch)
-__device__ __forceinline__ uint2 lds_u2(const void* p) {
-  uint2 r;
-  asm volatile("ds_read_b64 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_off(p)));
-  return r;
-}
-__device__ __forceinline__ float4 lds_f4(const void* p) {
-  float4 r;
-  asm volatile("ds_read_b128 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=v"(r) : "v"(lds_off(p)));
-  return r;
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 __device__ __forceinline__ bf16x8 frag(const char* p) { return *reinterpret_cast<const bf16x8*>(p); }
 __device__ __forceinline__ f32x4 mfma(bf16x8 a, bf16x8 b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
@@ -101,10 +78,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 4 ? 2 : 1) er_sp_kernel(const E
   const int g = lane >> 4, r16 = lane & 15;
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
 
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_ersp_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto stage_dma = [&](int ls, int slot) {
 #pragma unroll
     for (int j = 0; j < PPW; ++j) {

@@ -15,13 +15,12 @@
 #include <algorithm>
 #include <cstdio>
 
+#include "er_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
-
-__device__ __attribute__((aligned(16))) uint4 g_es2_zero[4];  // DMA source for padding pixels
 
 constexpr int ES_TH = 8, ES_TW = 16;     // output tile rows / columns
 constexpr int ES_HR = 2 * ES_TH + 1;     // 17 halo rows
@@ -40,14 +39,6 @@ struct Es2Args {
                        // block's er8_fused operand), or null
   int N, H, W, OH, OW, pad_t, pad_l, tiles_x, tiles_y;
 };
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Y8: also store y's e4m3 bytes (a.y8).  A template parameter, so the per-tile store count the counted vmcnt wait
 // at the top of the tile loop relies on (ON, 2 ON with y8) is fixed when the kernel is compiled.
@@ -76,10 +67,7 @@ __global__ void __launch_bounds__(512, (CIN == 16 ? 2 : 1)) ers2_fused_kernel(co
   const int g = lane >> 4, r16 = lane & 15;
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
 
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_es2_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto issue_halo = [&](int tile, char* buf) {
     const int n = tile / tpi, tr = tile - n * tpi, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
     const int iy0 = 2 * ES_TH * ty - a.pad_t, ix0 = 2 * ES_TW * tx - a.pad_l;
@@ -204,13 +192,10 @@ __global__ void __launch_bounds__(512, 1) ers2_sp_kernel(const Es2Args a) {
   const int g = lane >> 4, r16 = lane & 15;
   const int tpi = a.tiles_x * a.tiles_y, ntiles = a.N * tpi;
 
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_es2_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto issue_halo = [&](int tile, char* buf) {
-    const int n = tile / tpi, tr = tile - n * tpi, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-    const int iy0 = 2 * ES_TH * ty - a.pad_t, ix0 = 2 * ES_TW * tx - a.pad_l;
+    const TilePos t = tile_pos<ES_TH, ES_TW>(tile, tpi, a.tiles_x);
+    const int n = t.n, iy0 = 2 * t.y0 - a.pad_t, ix0 = 2 * t.x0 - a.pad_l;
     const bf16_t* xi = a.x + (size_t)n * a.H * a.W * CIN * 2;
 #pragma unroll
     for (int p = wave; p < NPIECE; p += 8) {
@@ -298,8 +283,8 @@ __global__ void __launch_bounds__(512, 1) ers2_sp_kernel(const Es2Args a) {
         o[on] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wph[on][ks], mh, o[on], 0, 0, 0);
       }
     }
-    const int n = tile / tpi, tr = tile - n * tpi, ty = tr / a.tiles_x, tx = tr - ty * a.tiles_x;
-    const int oy = ty * ES_TH + wave, ox = tx * ES_TW + r16;
+    const TilePos t = tile_pos<ES_TH, ES_TW>(tile, tpi, a.tiles_x);
+    const int n = t.n, oy = t.y0 + wave, ox = t.x0 + r16;
     // every tile is whole: exactly 2 ON stores per wave per tile (the counted wait above)
 #pragma unroll
     for (int on = 0; on < ON; ++on) {

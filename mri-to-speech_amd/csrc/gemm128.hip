@@ -22,6 +22,7 @@
 // in the epilogue; the E8M0 block scales are 1.
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 #include <cstdlib>
@@ -31,39 +32,7 @@
 namespace m2s {
 namespace {
 
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int F8_ROW = 128;            // bytes per LDS row: 128 e4m3 = one K step
-constexpr int E8M0_ONE = 0x7f7f7f7f;   // 2^0 block scale in every byte
-
-__device__ __attribute__((aligned(16))) uint4 g_zero_f8[4];  // padding lanes' DMA source
-
-// Physical 16-byte chunk of logical chunk c in row r: c ^ f(r), f(r) = ((r >> 1) & 1) | (r & 4).  A
-// fragment is two ds_read_b128 (lane (g = lane >> 4, r = lane & 15) reads chunks 2g and 2g + 1 of row r);
-// with 128-byte rows a row pair spans the 64 banks, and this f puts the 16 lanes of each of ds_read_b128's
-// lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, ...; MI355X_MICROARCH.md LDS table) on 16 distinct
-// 16-byte bank quads for both reads (exhaustive check over the XOR swizzles of the row's low 4 bits).
-__device__ __forceinline__ int f8_swz(int r) { return ((r >> 1) & 1) | (r & 4); }
-// SP: a fragment reads chunks g (hi) and g + 4 (lo); f(r) = r & 6 is conflict-free for that pair (same check)
-template <bool SP>
-__device__ __forceinline__ int swz128(int r) { return SP ? (r & 6) : f8_swz(r); }
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
-// 4 e4m3 (one dword) x 4 gates -> 4 e4m3
-__device__ __forceinline__ int gate4(int d, const float* s) {
-  const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(d, false);
-  const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(d, true);
-  const int r = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0] * s[0], lo[1] * s[1], 0, false);
-  return __builtin_amdgcn_cvt_pk_fp8_f32(hi[0] * s[2], hi[1] * s[3], r, true);
-}
 
 enum { KIND_F8_SE = 0, KIND_F8_C1D = 1, KIND_SP_SE = 2 };
 
@@ -123,8 +92,7 @@ __global__ void __launch_bounds__(64 * WM * WN, 1) gemm128_kernel(const G128Args
 
   // ---- DMA roles: block b = wave + 4 j; lane -> (row lane >> 3 of the block, physical chunk lane & 7) --
   const int lrow = lane >> 3, pch = lane & 7;
-  const char* zp = reinterpret_cast<const char*>(g_zero_f8);
-  asm volatile("" : "+s"(zp));
+  const char* zp = zero_page();
   // SE: K step st = input channels [128 st, 128 st + 128) of the row.  C1D: tap t = st / gpt, channels
   // 128 (st % gpt) .. of input position l + t dil - pad_left of the row's sequence (zero outside [0, L)).
   const int tpk = !SE && a.cs_in < F8_ROW ? F8_ROW / a.cs_in : 1;  // C1D: taps a K step (C = 64: 2, C = 32: 4)

@@ -34,12 +34,11 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
-
-__device__ __attribute__((aligned(16))) uint4 g_ws_zero[4];  // DMA source of padding chunks
 
 constexpr int WS_SL = 32;  // expanded channels per slice
 constexpr int WS_BR = 8;   // output rows per band
@@ -47,32 +46,9 @@ constexpr int WS_NP = 8;   // producer waves
 constexpr int WS_NC = 8;   // consumer waves
 constexpr int WS_UMAX = 3; // producer units per wave (ws_layout bounds the band's subtiles to 12)
 
-__device__ __forceinline__ int swz_f(int x) { return (0x1320 >> (4 * x)) & 3; }
 __device__ __forceinline__ int hx_of(int r) { return ((r & 3) << 2) | swz_f((r >> 2) & 3); }
-// LDS-DMA in inline asm (cdna_hip_programming.md 'Operands and clobbers', the glds16 recipe): hipcc
-// neither sees nor counts it, so it does not drain it with vmcnt(0) before the producer's own LDS
-// reads (it did with the builtin: W(i+1)'s DMA waited for at every slice).  Completion: wait_vm0.
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(lds_wave_base)
-               : "memory");
-}
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)p);
-}
-__device__ __forceinline__ void wait_vm0() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-// vmcnt(n) for a wave-uniform n the immediate cannot take: the nearest count <= n (waiting for more is safe)
-__device__ __forceinline__ void wait_vm_le(int n) {
-  if (n >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-  else if (n == 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-  else if (n == 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-  else if (n == 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-  else if (n == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-  else if (n == 1) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
+// The producers' DMAs are dma16_asm (lds_dma.hpp): with the builtin, W(i+1)'s DMA was waited for at every slice,
+// before the producer's own LDS reads.  Completion: wait_vm<0> / wait_vm_le.
 
 struct WsLayout {
   int XR, TROWS, x_bytes, tile_bytes, w_bytes, total;
@@ -290,12 +266,12 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
     int ln = lane;  // rebuilt per call (asm barrier): hoisted lane offsets cost registers the consumers need
     asm volatile("" : "+v"(ln));
     if (par ? (wave < 2 && ln < 4) : (wave == 0 && ln < 8))  // (par: each parity's first wave its 16 biases)
-      dma16(bpw + (sl * WS_SL + (par ? 16 * wave : 0) + 4 * ln), lds_addr(bpl + (f & 1) * 32 + (par ? 16 * wave : 0)));
+      dma16_asm(bpw + (sl * WS_SL + (par ? 16 * wave : 0) + 4 * ln), lds_lo32_u(bpl + (f & 1) * 32 + (par ? 16 * wave : 0)));
     const int q = (ln & 3) ^ swz_f((ln >> 4) & 3);
     for (int j = wave; j < 4 * KS; j += WS_NP) {
       const int ks = j >> 2, plane = (j >> 1) & 1, half = j & 1;
       const int row = sl * WS_SL + half * 16 + (ln >> 2);
-      dma16(wpw + (row * CS * 2 + plane * CS + ks * 32 + q * 8), lds_addr(base + ks * 4096 + plane * 2048 + half * 1024));
+      dma16_asm(wpw + (row * CS * 2 + plane * CS + ks * 32 + q * 8), lds_lo32_u(base + ks * 4096 + plane * 2048 + half * 1024));
     }
   };
   auto issue_wd = [&](int f, Step d) {  // the slice's depthwise taps [9][32] + bias: 80 lanes of 16 B
@@ -307,16 +283,13 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
     int ln = lane;
     asm volatile("" : "+v"(ln));
     if (wave == WS_NP - 2) {
-      dma16(wdw + ((ln >> 3) * cs_mid + c0 + 4 * (ln & 7)), lds_addr(dst));
+      dma16_asm(wdw + ((ln >> 3) * cs_mid + c0 + 4 * (ln & 7)), lds_lo32_u(dst));
     } else if (wave == WS_NP - 1 && ln < 16) {
       const float* src = ln < 8 ? wdw + (8 * cs_mid + c0 + 4 * ln) : bdw + (c0 + 4 * (ln - 8));
-      dma16(src, lds_addr(dst + 256));
+      dma16_asm(src, lds_lo32_u(dst + 256));
     }
   };
-  // the zero page's address in SGPRs for the whole kernel: named directly in the DMA loops it was re-fetched from the
-  // GOT (s_getpc + s_load + s_waitcnt lgkmcnt(0), which also drains the wave's LDS reads) at every piece
-  const void* zpage = g_ws_zero;
-  asm volatile("" : "+s"(zpage));
+  const void* zpage = zero_page();
   auto issue_x = [&](int img, int band) {  // input rows of the band (+ halo rows), swizzled
     const int r0 = band * WS_BR, xr0 = max(r0 - 1, 0), xr1 = min(r0 + WS_BR + 1, H);
     const int ninstr = (xr1 - xr0) * W * CPR / 64;
@@ -327,7 +300,7 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
       const int plane = L / CPP, k8 = L - plane * CPP;
       const void* src = k8 * 8 < CS ? static_cast<const void*>(xi + (size_t)r * CS * 2 + plane * CS + k8 * 8)
                                     : zpage;
-      dma16(src, lds_addr(xs + j * 1024));
+      dma16_asm(src, lds_lo32_u(xs + j * 1024));
     }
   };
   // W ring (two slots): a producer wave counts itself done with W(f)'s slot right after its MFMAs of slice f
@@ -366,8 +339,8 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
     if (HAND_END) {
       bump(pdone_p);
     } else {  // W(f + 1) of this wave landed (younger: only the tap waves' slice-f taps), then every producer's
-      if (tap_wave) asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
-      else wait_vm0();
+      if (tap_wave) wait_vm<1>();
+      else wait_vm<0>();
       TR(f, 13);
       bump(pdone_p);
       if (JOINT) {
@@ -670,7 +643,7 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
           if (par) wait_ge(pw ? ctr + 0 : ctr + 5, NPC * (unsigned)i);
         }
         issue_x(cur.img, cur.band);
-        wait_vm0();
+        wait_vm<0>();
         bump(xrdy);
         wait_ge(xrdy, (unsigned)(WS_NP * ++bands));
       }
@@ -684,7 +657,7 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
       produce(i, cur, nxt2);
       if (HAND_END) {
         // W(i + 1) and (tap waves) slice i's taps landed: nothing else of this wave's is in flight
-        wait_vm0();
+        wait_vm<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the tile stores
         if (lane == 0) {
           asm volatile("ds_add_u32 %0, %1" ::"v"((uint32_t)(uintptr_t)wrdy_p), "v"(1u) : "memory");

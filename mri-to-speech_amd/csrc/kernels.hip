@@ -10,11 +10,6 @@ namespace m2s {
 
 namespace {
 
-template <typename T>
-__device__ __forceinline__ float act_silu(float v) {
-  return sizeof(T) == 4 ? silu_exact(v) : silu(v);
-}
-
 // ---------------------------------------------------------------------------------------------
 // stem: four lanes per output pixel, 8 channels each, so one wave's stores cover 16 whole pixel
 // rows (1 KB contiguous in bf16) instead of 64 partial ones.  A lane keeps its 8 channels' 72
@@ -55,7 +50,7 @@ __global__ void __launch_bounds__(256) stem_kernel(const float* __restrict__ fra
       float acc = 0.f;
 #pragma unroll
       for (int t = 0; t < 9; ++t) acc += w[j][t] * in[t];
-      v[j] = act_silu<T>(acc + bb[j]);
+      v[j] = silu_t<T>(acc + bb[j]);
     }
     act_st8<T>(y, p, cs_out, o0, v);
   }

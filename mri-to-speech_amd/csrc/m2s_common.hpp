@@ -236,6 +236,11 @@ __device__ __forceinline__ float silu_e4m3(float x) { return fminf(x, 448.f) * _
 // Exact-libm variants used by the fp32 parity path (the reference runs fp32 libm on CPU).
 __device__ __forceinline__ float silu_exact(float x) { return x / (1.0f + expf(-x)); }
 __device__ __forceinline__ float sigmoid_exact(float x) { return 1.0f / (1.0f + expf(-x)); }
+// SiLU of storage type T: the exact one for fp32 storage (the parity path), the fast one for bf16 and split storage
+template <typename T>
+__device__ __forceinline__ float silu_t(float v) {
+  return sizeof(T) == 4 ? silu_exact(v) : silu(v);
+}
 
 // Per-device launch attributes (device_attr.cpp), cached per (device[, kernel]) so engines on
 // different devices in one process each get their own: the current device's CU count, the 160 KB

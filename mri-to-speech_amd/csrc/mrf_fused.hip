@@ -37,6 +37,7 @@
 
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
@@ -93,14 +94,6 @@ constexpr int RB_SLOTS = 3;       // weight ring depth
 template <int C, int SP = 0>
 constexpr int rb_tg() {  // taps per weight stage
   return RB_STAGE / (C * C * 2 * (SP ? 2 : 1));
-}
-
-__device__ __forceinline__ void dma16(const void* src, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds(src, lds_wave_base, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 struct Ring {

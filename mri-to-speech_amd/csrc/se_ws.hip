@@ -34,26 +34,13 @@
 #include <cstring>
 
 #include "kernels.hpp"
+#include "lds_dma.hpp"
 #include "prof.hpp"
 
 namespace m2s {
 namespace {
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
 constexpr int ROWB = 128;            // bytes per LDS row: 32 channels [hi 32 | lo 32] bf16
-
-__device__ __attribute__((aligned(16))) uint4 g_se_ws_zero[4];  // DMA source of padding lanes
-
-
-__device__ __forceinline__ void dma16(const void* src, uint32_t lds_wave_base) {
-  unsigned keep;
-  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-               : "=&s"(keep)
-               : "v"(src), "s"(lds_wave_base)
-               : "memory");
-}
-__device__ __forceinline__ uint32_t lds_u32(const void* p) { return (uint32_t)(uintptr_t)p; }
 
 // flag poll: one ds_read (all lanes read the same dword), then a scalar copy; bounded by `spin_max` polls
 // (0: the wait fails at once, the fault injection of m2s_acoustic_set_ws_spin_limit).  false = timed out
@@ -87,20 +74,7 @@ struct SeWsArgs {
   unsigned* err;      // host-mapped error word (M2S_ASYNC_WS on a timeout) or null
 };
 
-constexpr int E8M0_ONE = 0x7f7f7f7f;  // 2^0 block scale in every byte
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-// physical 16-byte chunk of logical chunk c in LDS row r: c ^ f(r).  Split rows: a fragment reads chunks g (hi)
-// and g + 4 (lo) of row r16, f(r) = r & 6; e4m3 rows (F8): chunks 2g and 2g + 1, f(r) = ((r >> 1) & 1) | (r & 4).
-// Both are conflict-free for ds_read_b128's lane groups (gemm128.hip swz128 / f8_swz)
-template <bool F8>
-__device__ __forceinline__ int swz_k(int r) { return F8 ? (((r >> 1) & 1) | (r & 4)) : (r & 6); }
-// 4 e4m3 (one dword) x 4 gates -> 4 e4m3 (gemm128.hip gate4; the gate is in (0, 1): no new saturation)
-__device__ __forceinline__ int gate4_f8(int d, const float* s) {
-  const f32x2_t lo = __builtin_amdgcn_cvt_pk_f32_fp8(d, false);
-  const f32x2_t hi = __builtin_amdgcn_cvt_pk_f32_fp8(d, true);
-  const int r = __builtin_amdgcn_cvt_pk_fp8_f32(lo[0] * s[0], lo[1] * s[1], 0, false);
-  return __builtin_amdgcn_cvt_pk_fp8_f32(hi[0] * s[2], hi[1] * s[3], r, true);
-}
+// LDS rows are swizzled as gemm128.hip's (lds_dma.hpp swz128): split rows swz128<true>, e4m3 and XF fp32 rows f8_swz
 
 // NS ring slots; a loader keeps IF steps in flight behind the one it publishes (IF <= NS - 1).  F8: the fp8
 // engines' e4m3 form (K step = 128 e4m3 channels, v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales,
@@ -134,7 +108,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
   const int gimg = (grow + 1023) / 1024 * 1024;     // ... in LDS
   char* gbuf = smem + NS * SLOT;                    // [2][nimg][gimg]
   unsigned* flags = reinterpret_cast<unsigned*>(gbuf + 2 * nimg * gimg);  // FULL[NS], FREE[NS]
-  const uint32_t full0 = lds_u32(flags), free0 = lds_u32(flags + NS), poison = lds_u32(flags + 2 * NS);
+  const uint32_t full0 = lds_lo32(flags), free0 = lds_lo32(flags + NS), poison = lds_lo32(flags + 2 * NS);
   const int nsteps = F8 ? a.kp / 128 : a.cs_in / 32;
   const int n_tiles = a.n_tiles_m;                  // one n tile: BN covers cs_out
   const int my_tiles = (int)blockIdx.x < n_tiles ? (n_tiles - 1 - (int)blockIdx.x) / (int)gridDim.x + 1 : 0;
@@ -155,7 +129,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
   if (wave >= NC) {
     // ---------------------------------------------------------------- loaders
     const int l = wave - NC;
-    const char* zp = reinterpret_cast<const char*>(g_se_ws_zero);
+    const char* zp = reinterpret_cast<const char*>(g_zero_page);  // (not zero_page(): the loaders never pinned it)
     const int lrow = lane >> 3, pch = lane & 7;
     // this loader's blocks b = l + NL j: weight rows (b < BN / 8) or activation rows; a lane's row and
     // logical chunk follow from (b, lane) with a few integer ops per DMA (precomputed per block they were
@@ -184,14 +158,14 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
               const bool ok = e < nb && (img0 + im) * a.P < a.M;
               const void* src = ok ? static_cast<const void*>(a.gate + ((size_t)(img0 + im) * grow + e * 16))
                                    : static_cast<const void*>(zp);
-              dma16(src, lds_u32(gdst + im * gimg + o * 16));
+              dma16_asm(src, lds_lo32(gdst + im * gimg + o * 16));
             }
         }
         char* base = smem + slot * SLOT;
 #pragma unroll
         for (int j = 0; j < PER; ++j) {
           const int b = l + NL * j, r = b * 8 + lrow;
-          const int c = pch ^ ((XF && b >= BN / 8) ? swz_k<true>(r & 15) : swz_k<F8>(r & 15));
+          const int c = pch ^ ((XF && b >= BN / 8) ? f8_swz(r & 15) : swz128<!F8>(r & 15));
           const void* src;
           if (b < BN / 8) {
             src = F8 ? a.w + ((size_t)r * wrow_b + st * ROWB + c * 16)
@@ -201,10 +175,10 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
             const bool in = m < mend && (!F8 || st * ROWB + c * 16 < a.cs_in);  // F8: zeros past cs_in
             src = in ? static_cast<const void*>(xt + ((r - BN) * xrow_b + c * 16 + st * ROWB)) : static_cast<const void*>(zp);
           }
-          dma16(src, lds_u32(base + b * 1024));
+          dma16_asm(src, lds_lo32(base + b * 1024));
         }
         if (s >= IF) {  // step s - IF landed: everything but the IF younger steps' DMAs retired
-          asm volatile("s_waitcnt vmcnt(%0)" ::"n"(IF * PER) : "memory");
+          wait_vm<IF * PER>();
           bump_flag(full0 + 4 * ((s - IF) % NS), lane);
         }
       }
@@ -214,9 +188,9 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
     for (int k = IF - 1; k >= 0; --k) {
       const int q = s - 1 - k;
       if (q < 0 || q < s - IF) continue;
-      if (k == 2) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * PER) : "memory");
-      else if (k == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-      else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      if (k == 2) wait_vm<2 * PER>();
+      else if (k == 1) wait_vm<PER>();
+      else wait_vm<0>();
       bump_flag(full0 + 4 * (q % NS), lane);
     }
     return;
@@ -225,18 +199,18 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
   // ---------------------------------------------------------------- consumers
   const int wm = wave / WN, wn = wave % WN;
   const int g = lane >> 4, r16 = lane & 15;
-  const int sw = swz_k<F8>(r16);
+  const int sw = swz128<!F8>(r16);
   // a lane's two 16-byte chunks of a fragment row: split hi g / lo g + 4; F8 e4m3 2g, 2g + 1 (32 consecutive k)
   const uint32_t ch0 = (uint32_t)(((F8 ? 2 * g : g) ^ sw) << 4), ch1 = (uint32_t)(((F8 ? 2 * g + 1 : g + 4) ^ sw) << 4);
-  const uint32_t sm0 = lds_u32(smem);
+  const uint32_t sm0 = lds_lo32(smem);
   const uint32_t a_lds0 = sm0 + (uint32_t)((wn * NT * 16 + r16) * ROWB);
   const uint32_t b_lds0 = sm0 + (uint32_t)((BN + wm * 64 + r16) * ROWB);
   // XF: the activation rows' chunks (fp32 rows: chunks 2g, 2g + 1 under the e4m3 rows' swizzle), folded into the row base
   // (one register more than the split form, whose 16 x 16 variant sits at 255)
-  const uint32_t bx0 = XF ? b_lds0 + (uint32_t)(((2 * g) ^ swz_k<true>(r16)) << 4) : 0u;
-  const uint32_t bx1 = XF ? b_lds0 + (uint32_t)(((2 * g + 1) ^ swz_k<true>(r16)) << 4) : 0u;
+  const uint32_t bx0 = XF ? b_lds0 + (uint32_t)(((2 * g) ^ f8_swz(r16)) << 4) : 0u;
+  const uint32_t bx1 = XF ? b_lds0 + (uint32_t)(((2 * g + 1) ^ f8_swz(r16)) << 4) : 0u;
   const uint32_t wa0 = XF ? a_lds0 + ch0 : 0u, wa1 = XF ? a_lds0 + ch1 : 0u;  // XF: the weight chunks folded likewise
-  const uint32_t g_lds0 = lds_u32(gbuf) + (uint32_t)(g * (F8 ? 64 : 16));
+  const uint32_t g_lds0 = lds_lo32(gbuf) + (uint32_t)(g * (F8 ? 64 : 16));
   bool bad = false;  // a FULL wait (or a loader's FREE wait) timed out: this wave's tiles are stored as NaN from then on
   int s = 0;
   for (int it = 0; it < my_tiles; ++it) {
@@ -297,8 +271,8 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
           i32x8 bx;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            bx[i] = gate4_f8((int)b0[mi][i], gs + 4 * i);
-            bx[4 + i] = gate4_f8((int)b1[mi][i], gs + 16 + 4 * i);
+            bx[i] = gate4((int)b0[mi][i], gs + 4 * i);
+            bx[4 + i] = gate4((int)b1[mi][i], gs + 16 + 4 * i);
           }
           if (mi == 0) {  // every read of the slot returned: release it to the loaders
             static_assert(NT <= 8, "wait operands");
