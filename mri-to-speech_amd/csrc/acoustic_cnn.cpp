@@ -2,8 +2,6 @@
 // block, shape and switch, and the scratch of a pass.  The weights are packed by pack_acoustic.cpp (host code); the
 // constructor here reads the switches, packs, uploads the arena and resolves device pointers.
 #include <algorithm>
-#include <initializer_list>
-#include <utility>
 
 #include "plan_util.hpp"
 #include "prof.hpp"
@@ -11,20 +9,7 @@
 namespace m2s {
 
 Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int device)
-    : dtype_(dtype), device_(device), n_mels_(n_mels), hidden_(hidden) {
-  // (the last row: A/B and tests only)
-  for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
-           {"M2S_IR_FUSED", &ir_fused_},   {"M2S_IR_WS", &ir_ws_},         {"M2S_IR_WS_S2", &ir_ws_s2_},
-           {"M2S_IRWS_F32", &irws_f32_},   {"M2S_STEM_FUSED", &stem_fused_}, {"M2S_F8_EXPAND", &f8_expand_},
-           {"M2S_F8_S2", &f8_s2_},         {"M2S_F8_ER", &f8_er_},         {"M2S_ER8_X8", &er8_x8_},
-           {"M2S_F8_ER2", &f8_er2_},       {"M2S_SE_Y8", &se_y8_},         {"M2S_SE_FUSED", &se_fused_},
-           {"M2S_ER_FUSED", &er_fused_},   {"M2S_SE_WS", &se_ws_},         {"M2S_LSTM_PERSISTENT", &lstm_persistent_},
-           {"M2S_LSTM_MID", &lstm_mid_},   {"M2S_LSTM_X3", &lstm_x3_},     {"M2S_LSTM_X3G", &lstm_x3g_},
-           {"M2S_SE_SP", &se_sp_},         {"M2S_ER_MRG", &er_mrg_},       {"M2S_IR_S2BAND", &ir_s2band_},
-           {"M2S_ER_S2_FUSED", &er_s2_fused_}, {"M2S_SEWS_REV", &sews_rev_}})
-    env_flag(name, *v);
-  env_int("M2S_IRWS_MIN", irws_min_);
-  env_int("M2S_SEWS_MIN", sews_min_cus_);
+    : dtype_(dtype), device_(device), n_mels_(n_mels), hidden_(hidden), sw_(Switches::from_env()) {
   pack_acoustic(sd, n_mels, hidden, dtype, arena_, p_);
   arena_.upload(device);
   for (auto& b : p_.blocks) {
@@ -67,13 +52,13 @@ void Acoustic::effnet_dims(int H, int W, size_t* io, size_t* mid, size_t* se) co
 }
 
 size_t Acoustic::effnet_x8(int H, int W) const {
-  if (dtype_ != M2S_DT_FP8 || (!f8_expand_ && !f8_er_)) return 0;
+  if (dtype_ != M2S_DT_FP8 || (!sw_.f8_expand && !sw_.f8_er)) return 0;
   size_t mx = 0;
   for_each_backbone_map(H, W, [&](const BlockDef& d, const BlockMap& m) {
     const Block& b = p_.blocks[d.index];
-    if (b.f8_pw && f8_expand_) mx = std::max(mx, (size_t)m.ih * m.iw * b.f8x_kp);  // the block input's map
-    if (b.er8 && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 32);              // er8_fused x8 / y8 (N, H, W, 32)
-    if (b.er8w && f8_er_) mx = std::max(mx, (size_t)m.oh * m.ow * 64);             // er8w_fused x8 / y8 (N, H, W, 64)
+    if (b.f8_pw && sw_.f8_expand) mx = std::max(mx, (size_t)m.ih * m.iw * b.f8x_kp);  // the block input's map
+    if (b.er8 && sw_.f8_er) mx = std::max(mx, (size_t)m.oh * m.ow * 32);              // er8_fused x8 / y8 (N, H, W, 32)
+    if (b.er8w && sw_.f8_er) mx = std::max(mx, (size_t)m.oh * m.ow * 64);             // er8w_fused x8 / y8 (N, H, W, 64)
   });
   return round_up((int)mx, 256);
 }
@@ -148,7 +133,7 @@ void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
   ConvArgs a = conv2d_args(p, b.c1, p.cur, p.nxt);
   a.act = ACT_SILU;
   a.res = b.skip ? p.cur : nullptr;
-  run_conv<T>(a, b.c1, p.s);
+  run_conv<T>(a, b.c1, sw_.conv, p.s);
 }
 
 template <typename T>
@@ -165,21 +150,21 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
     a.act = ACT_SILU;
     ConvArgs q = pw_args(b.c2, p.b.M, nxt, nc * nh * nw, nh * nw);
     q.res = b.skip ? cur : nullptr;
-    if (kSplit<T> && er_s2_fused_ && b.stride == 2 && conv_gemm_er_supported(a, q)) {
+    if (kSplit<T> && sw_.er_s2_fused && b.stride == 2 && conv_gemm_er_supported(a, q, sw_.conv)) {
       // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the expanded map stays in LDS (M is not touched);
       // compulsory bytes = the block's input and output maps and both convs' weights
-      launch_conv_gemm_er(a, q, s, flops,
+      launch_conv_gemm_er(a, q, sw_.conv, s, flops,
                           4.0 * ((double)nc * oh * ow * b.cin + px * b.cout + (9.0 * b.cin + b.cout) * b.mid));
     } else {
-      run_conv<T>(a, b.c1, s);
-      run_conv<T>(q, b.c2, s);
+      run_conv<T>(a, b.c1, sw_.conv, s);
+      run_conv<T>(q, b.c2, sw_.conv, s);
     }
   };
   if constexpr (kSplit<T>) {
-    if (er_fused_ && b.er_sp && er_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
+    if (sw_.er_fused && b.er_sp && er_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
       launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt, flops,
-                   4.0 * px * (b.c1.cs_in + co), s, er_mrg_);
-    } else if (er_fused_ && b.ers_sp && b.stride == 2 && ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
+                   4.0 * px * (b.c1.cs_in + co), s, sw_.er_mrg);
+    } else if (sw_.er_fused && b.ers_sp && b.stride == 2 && ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
       launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_wexp), b.c1.b,
                      arena_.ptr(b.er_wpwl), b.c2.b, nxt, flops, 4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co), s);
     } else {
@@ -191,19 +176,19 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
     // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
     // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
     // er8_fused to its in-kernel conversion)
-    uint8_t* const er8_next = X8[0] && f8_er_ && nb && ((er8_x8_ && nb->er8) || (f8_er2_ && nb->er8w))
+    uint8_t* const er8_next = X8[0] && sw_.f8_er && nb && ((sw_.er8_x8 && nb->er8) || (sw_.f8_er2 && nb->er8w))
                                   ? (cur8 == X8[0] ? X8[1] : X8[0])
                                   : nullptr;
-    if (er_fused_ && f8_er_ && b.er8 && er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
+    if (sw_.er_fused && sw_.f8_er && b.er8 && er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
       uint8_t* y8 = cur8 && er8_next && er8_fused_supported(nh, nw, b.cout, b.mid, b.cout) ? er8_next : nullptr;
       launch_er8_fused(cur, nc, nh, nw, arena_.at<uint8_t>(b.er8_wexp), arena_.at<float>(b.er8_sexp), b.c1.b,
                        arena_.at<uint8_t>(b.er8_wpwl), arena_.at<float>(b.er8_spwl), b.c2.b, nxt, flops,
                        2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, cur8, y8);
       next8 = y8;
-    } else if (er_fused_ && b.er_frag && er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+    } else if (sw_.er_fused && b.er_frag && er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
       launch_er_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt,
                       flops, 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
-    } else if (er_fused_ && f8_er_ && f8_er2_ && b.er8w && cur8 &&
+    } else if (sw_.er_fused && sw_.f8_er && sw_.f8_er2 && b.er8w && cur8 &&
                er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
       uint8_t* y8 = er8_next && nb->er8w ? er8_next : nullptr;
       launch_er8w_fused(cur, cur8, nc, nh, nw, arena_.at<uint8_t>(b.er8w_w), arena_.at<float>(b.er8w_sexp), b.c1.b,
@@ -211,10 +196,10 @@ void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
                         // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
                         px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
       next8 = y8;
-    } else if (er_fused_ && b.er_frag && er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
+    } else if (sw_.er_fused && b.er_frag && er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
       launch_er2_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, b.c2.b, nxt, flops,
                        2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
-    } else if (er_fused_ && b.er_frag && b.stride == 2 &&
+    } else if (sw_.er_fused && b.er_frag && b.stride == 2 &&
                ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, co, b.c1.kp, b.c2.kp)) {
       // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
       uint8_t* y8 = er8_next && ((co == 32 && nb->er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
@@ -248,13 +233,13 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
   const float *const dw_w = arena_.at<float>(b.dw_w), *const dw_b = arena_.at<float>(b.dw_b);
   // bf16 feeds the fused kernel bf16 depthwise taps (dword halves), split fp32 the fp32 taps
   const void* wdw = SPL ? dw_w : arena_.ptr(b.dw_w2);
-  const bool big = nc >= irws_min_;  // persistent ir_ws only where its one-image workgroups fill the chip
+  const bool big = nc >= sw_.irws_min;  // persistent ir_ws only where its one-image workgroups fill the chip
   // the SE-gated conv_pwl runs on se_ws (effnet_ir_pwl): then ir_ws hands it the expanded map as plain fp32 rows
   // (one 16-byte store per 4 channels, no split; se_ws gates the fp32 value before its one split)
-  const bool sews = p.sews = SPL && se_ws_ && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
+  const bool sews = p.sews = SPL && sw_.se_ws && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
                              // se_ws runs one persistent workgroup per tile (256 rows; 128 at 8 x 8) up to one per CU:
                              // below a full round of tiles the split-K conv_gemm SE GEMM fills the chip instead
-                             ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sews_min_cus_ * device_cus();
+                             ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sw_.sews_min_cus * device_cus();
   // the persistent front half on an ih x iw input map (stride 2: down to nh x nw, passed with its pads)
   auto ir_ws = [&](int ih, int iw, int stride, int OH, int OW, int pad_t, int pad_l) {
     const double Pi = (double)ih * iw, Po = (double)nh * nw;
@@ -264,7 +249,7 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
                  // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
                  // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
                  4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), stride,
-                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, mid_f32 = sews && irws_f32_);
+                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, mid_f32 = sews && sw_.irws_f32, sw_.irws_parts);
   };
   // fp8, the expand on e4m3: x8 of the block input (rows of P pixels an image), or null where the expand stays bf16
   auto input8 = [&](bool f8x, int P) -> const uint8_t* {
@@ -275,34 +260,34 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
     }
     return cur8;
   };
-  if (SPL && b.stride == 1 && ir_fused_ && ir_ws_ && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
+  if (SPL && b.stride == 1 && sw_.ir_fused && sw_.ir_ws && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
     ir_ws(nh, nw, 1, 0, 0, 0, 0);
-  } else if (FUSABLE && b.stride == 1 && ir_fused_ && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
+  } else if (FUSABLE && b.stride == 1 && sw_.ir_fused && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
     const double P = (double)nh * nw, es = SPL ? 4.0 : 2.0;
     f8 = b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
     // the expand on e4m3 (x8 of the block input)
-    const uint8_t* const x8 = input8(f8 && f8_expand_ && b.f8_pw && X8[0], nh * nw);
+    const uint8_t* const x8 = input8(f8 && sw_.f8_expand && b.f8_pw && X8[0], nh * nw);
     launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, nh, nw, cs, M2, se_mean, SPL,
                    2.0 * nc * P * b.mid * (b.c1.cin + 9), nc * P * ((x8 ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid),
                    s, f8, x8, x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
-  } else if (SPL && b.stride == 2 && ir_fused_ && ir_ws_ && ir_ws_s2_ && big &&
+  } else if (SPL && b.stride == 2 && sw_.ir_fused && sw_.ir_ws && sw_.ir_ws_s2 && big &&
              ir_ws_s2_supported(oh, ow, b.c1.cs_in, b.c1.kp, cs, nh, nw, qt, ql)) {
     ir_ws(oh, ow, 2, nh, nw, qt, ql);
-  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
+  } else if (FUSABLE && b.stride == 2 && sw_.ir_fused && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
              nh * nw <= 64) {
     const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
     // fp8 engines (blocks.5.0): e4m3 depthwise output for the e4m3 SE GEMM, the expand on e4m3 as for stride 1
-    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-    const uint8_t* const x8 = input8(f8 && f8_expand_ && b.f8_pw && X8[0], oh * ow);
+    f8 = sw_.f8_s2 && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    const uint8_t* const x8 = input8(f8 && sw_.f8_expand && b.f8_pw && X8[0], oh * ow);
     launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, oh, ow, nh, nw, qt, ql, cs, M2, se_mean,
                       SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
                       nc * ((x8 ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8, x8,
                       x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
-  } else if (FUSABLE && b.stride == 2 && ir_fused_ && ir_s2band_ &&
+  } else if (FUSABLE && b.stride == 2 && sw_.ir_fused && sw_.ir_s2band &&
              ir_s2band_supported(oh, ow, nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
     const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
     // fp8 engines (blocks.3.0): e4m3 depthwise output for the e4m3 SE GEMM (the expand stays bf16)
-    f8 = f8_s2_ && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
+    f8 = sw_.f8_s2 && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
     launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, dw_w, dw_b, nh, nw, qt, ql, cs, M2, sums, SPL,
                      2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
                      nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
@@ -311,7 +296,7 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
   } else {
     ConvArgs e = pw_args(b.c1, cur, M, nc * oh * ow, oh * ow);
     e.act = ACT_SILU;
-    run_conv<T>(e, b.c1, s);
+    run_conv<T>(e, b.c1, sw_.conv, s);
     {
       ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
                    kStoreBytes<T> * (double)nc * (oh * ow + nh * nw) * b.mid, s);
@@ -330,16 +315,16 @@ void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
   const int nc = p.nc, cs = chan_stride(b.mid);
   T *const se_mean = p.b.se_mean, *const se_hid = p.b.se_hid, *const scale = p.b.scale;
   hipStream_t s = p.s;
-  if (kNotF32<T> && se_fused_ && se_excite_supported(b.rd, b.se2.kp, cs)) {
+  if (kNotF32<T> && sw_.se_fused && se_excite_supported(b.rd, b.se2.kp, cs)) {
     launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
                      kSplit<T>, s);
   } else {
     ConvArgs r1 = pw_args(b.se1, se_mean, se_hid, nc, 1);  // conv_reduce + SiLU, all images of the chunk at once
     r1.act = ACT_SILU;
-    run_conv<T>(r1, b.se1, s);
+    run_conv<T>(r1, b.se1, sw_.conv, s);
     ConvArgs r2 = pw_args(b.se2, se_hid, scale, nc, 1);  // conv_expand + sigmoid -> per-(image, channel) gates
     r2.act = ACT_SIGMOID;
-    run_conv<T>(r2, b.se2, s);
+    run_conv<T>(r2, b.se2, sw_.conv, s);
   }
 }
 
@@ -354,20 +339,20 @@ void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
   const Block* const nb = k + 1 < p_.blocks.size() ? &p_.blocks[k + 1] : nullptr;
   // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
   // ir_pwdw_s2, whose input map is this block's nh x nw output)
-  const bool want8 = X8[0] && f8_expand_ && nb && nb->f8_pw &&
+  const bool want8 = X8[0] && sw_.f8_expand && nb && nb->f8_pw &&
                      (nb->stride == 1 ||
-                      (f8_s2_ && ir_fused_s2_supported(nh, nw, nb->c1.cs_in, chan_stride(nb->mid), false)));
+                      (sw_.f8_s2 && ir_fused_s2_supported(nh, nw, nb->c1.cs_in, chan_stride(nb->mid), false)));
   // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
   const int ld8 = want8 ? nb->f8x_kp : 0;
-  if (f8 && want8 && se_y8_) next8 = cur8 == X8[0] ? X8[1] : X8[0];
+  if (f8 && want8 && sw_.se_y8) next8 = cur8 == X8[0] ? X8[1] : X8[0];
   const double rows = (double)nc * nh * nw;
   const void* const res = b.skip ? cur : nullptr;
-  if (f8 && se_ws_ && se_ws_f8_supported(nh * nw, cs, co)) {
+  if (f8 && sw_.se_ws && se_ws_f8_supported(nh * nw, cs, co)) {
     launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
                     arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
                     rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
                         (next8 ? rows * b.cout : 0.0),
-                    next8, ld8, ws_report());
+                    next8, ld8, ws_report(), sw_.sews_half);
   } else if (f8) {
     launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
                       arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
@@ -378,18 +363,19 @@ void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
     launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
                  2.0 * rows * b.mid * b.cout,
                  4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
-                 ws_report(), mid_f32, sews_rev_);
-  } else if (kSplit<T> && se_sp_ && se_gemm_sp_supported(nh * nw, cs, co)) {
+                 ws_report(), mid_f32, sw_.sews_rev, sw_.sews_half, sw_.se_ws_cfg);
+  } else if (kSplit<T> && sw_.se_sp && se_gemm_sp_supported(nh * nw, cs, co)) {
     launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
                       2.0 * rows * b.mid * b.cout,
                       4.0 * rows * cs + 4.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
-                          4.0 * nc * cs);
+                          4.0 * nc * cs,
+                      sw_.se_sp_waves);
   } else {
     ConvArgs q = pw_args(b.c2, M2, nxt, nc * nh * nw, nh * nw);
     q.in_xform = IN_SE_SCALE;
     q.in_scale = scale;
     q.res = res;
-    run_conv<T>(q, b.c2, s);
+    run_conv<T>(q, b.c2, sw_.conv, s);
   }
 }
 
@@ -414,7 +400,7 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     same_pad(W, 3, 2, &ow, &pl);
     // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
     constexpr bool SPL = kSplit<T>;
-    const bool front = kNotF32<T> && stem_fused_ && !(probe && stop_after >= 0 && stop_after < 2) &&
+    const bool front = kNotF32<T> && sw_.stem_fused && !(probe && stop_after >= 0 && stop_after < 2) &&
                        p_.blocks.size() >= 2 && p_.blocks[0].type == 0 && p_.blocks[0].stride == 1 && !p_.blocks[0].skip &&
                        p_.blocks[0].cout == 16 && p_.blocks[0].c1.cs_in == 32 && p_.blocks[0].c1.kp == 288 &&
                        p_.blocks[1].type == 0 && p_.blocks[1].stride == 1 && p_.blocks[1].skip && p_.blocks[1].cout == 16 &&
@@ -428,7 +414,8 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
       const double px = (double)nc * oh * ow;
       launch_stem_b0(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, stem_w, stem_b, p_.blocks[0].c1.w,
                      p_.blocks[0].c1.b, p_.blocks[0].c1.kp, p_.blocks[1].c1.w, p_.blocks[1].c1.b, p_.blocks[1].c1.kp, A, SPL,
-                     2.0 * px * (EFF_STEM * 9 + 16 * 9 * 32 + 16 * 9 * 16), 4.0 * nc * H * W + (SPL ? 4.0 : 2.0) * px * 16, s);
+                     2.0 * px * (EFF_STEM * 9 + 16 * 9 * 32 + 16 * 9 * 16), 4.0 * nc * H * W + (SPL ? 4.0 : 2.0) * px * 16, s,
+                     sw_.stem_parts);
       cc = 16;
       bi = 2;
     } else {

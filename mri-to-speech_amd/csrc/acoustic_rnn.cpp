@@ -19,7 +19,7 @@ size_t Acoustic::workspace_bytes(int B, int T, int H, int W) const {
 void Acoustic::project(const float* feats, float* pre, long rows, int kwave, hipStream_t s) {
   ConvArgs a = pw_args(p_.lstm_ih, feats, pre, (int)rows, 1);
   a.kwave = kwave;
-  run_conv<float>(a, p_.lstm_ih, s);
+  run_conv<float>(a, p_.lstm_ih, sw_.conv, s);
 }
 
 void Acoustic::head(const float* h, long rows, bool merged, float* mel_norm, hipStream_t s) {
@@ -42,22 +42,24 @@ void Acoustic::lstm_recurrence(const float* pre, float* hs, float* cst, void* sy
   // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
   const double bytes = 4.0 * 2 * 4 * H * H + 4.0 * rows * (8.0 * H + 2.0 * H);
   const double f2 = 2.0 * 2 * 4.0 * H * H * seq_steps, f3 = 3.0 * 2 * 4.0 * H * H * seq_steps;
-  if (lstm_persistent_ && lstm_small_supported(B, H)) {
+  if (sw_.lstm_persistent && lstm_small_supported(B, H, sw_.lstm_small_b)) {
     ProfScope ps("lstm_small_kernel", f2, bytes, s);
-    launch_lstm_small(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, &gsync_epoch_);
-  } else if (lstm_persistent_ && lstm_x3_ && lstm_x3g_ && dtype_ != M2S_DT_F32 && lstm_x3g_supported(B, H)) {
+    launch_lstm_small(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, sw_.lstm_small_b,
+                      &gsync_epoch_);
+  } else if (sw_.lstm_persistent && sw_.lstm_x3 && sw_.lstm_x3g && dtype_ != M2S_DT_F32 &&
+             lstm_x3g_supported(B, H)) {
     // 5..16 sequences (configs[4]'s 8 clips a GPU): the granule hand-off (lstm_persistent.hip lstm_x3g_kernel)
     ProfScope ps("lstm_x3g_kernel", f3, bytes, s);
     launch_lstm_x3g(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, &gsync_epoch_);
-  } else if (lstm_persistent_ && lstm_x3_ && dtype_ != M2S_DT_F32 && lstm_persistent_supported(H)) {
+  } else if (sw_.lstm_persistent && sw_.lstm_x3 && dtype_ != M2S_DT_F32 && lstm_persistent_supported(H)) {
     // split engines above the small-batch kernel: 4.1 / 5.2 / 9.9 us per step at B = 8 / 16 / 64 against
     // lstm_mid's 7.2 / 11.9 and the f32 counter-barrier kernel's 24 (gpurun_out lstm2, lstm3_x3small)
     ProfScope ps("lstm_x3_kernel", f3, bytes, s);
     launch_lstm_x3(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else if (lstm_persistent_ && lstm_mid_ && lstm_mid_supported(B, H)) {
+  } else if (sw_.lstm_persistent && sw_.lstm_mid && lstm_mid_supported(B, H, sw_.lstm_small_b)) {
     ProfScope ps("lstm_mid_kernel", f2, bytes, s);
-    launch_lstm_mid(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else if (lstm_persistent_ && lstm_persistent_supported(H)) {
+    launch_lstm_mid(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s, sw_.lstm_small_b, sw_.lstm_mid_ch);
+  } else if (sw_.lstm_persistent && lstm_persistent_supported(H)) {
     ProfScope ps("lstm_persistent_kernel", f2, bytes, s);
     launch_lstm_persistent(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
   } else {

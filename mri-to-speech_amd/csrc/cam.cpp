@@ -215,7 +215,7 @@ void CamBackbone::forward(const float* frames, int N, int H, int W, float* const
           a.in_xform = IN_SE_SCALE;
           a.in_scale = scale + (size_t)n0 * pc.cs_in;
         }
-        run_conv<float>(a, pc, s);
+        run_conv<float>(a, pc, ConvTune{}, s);
       }
     };
     const size_t pin = (size_t)oh * ow, pout = (size_t)nh * nw;
@@ -238,13 +238,13 @@ void CamBackbone::forward(const float* frames, int N, int H, int W, float* const
       r1.y = hid;
       r1.M = N;
       r1.act = ACT_SILU;
-      run_conv<float>(r1, b.se1, s);
+      run_conv<float>(r1, b.se1, ConvTune{}, s);
       ConvArgs r2 = conv_args(b.se2);  // conv_expand + sigmoid -> gates
       r2.x = hid;
       r2.y = gate;
       r2.M = N;
       r2.act = ACT_SIGMOID;
-      run_conv<float>(r2, b.se2, s);
+      run_conv<float>(r2, b.se2, ConvTune{}, s);
       conv(b.c2, M2, pout * csm, nxt, pout * cso, nh, nw, nh, nw, gate);
       bn(nxt, (long)N * pout, b.bn[2], cso, 0, b.skip ? cur : nullptr);
     }

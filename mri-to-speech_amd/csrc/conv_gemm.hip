@@ -862,25 +862,22 @@ inline int se_images(int BM, int OH) { return BM % OH == 0 ? BM / OH : OH % BM =
 // batch: a few dozen tiles walking 20..88 K steps each): nks K ranges of >= 4 steps, up to a full round and at
 // most 8 (the partial sums' round trip grows with nks: same-box A/B at one clip / configs[1], M2S_KSPLIT_MAX 4 / 8
 // / 16: 2.378 / 2.286 / 2.300 ms and 1.106 / 1.107 / 1.119 ms, gpurun_out/r06d/ab.txt).
-// M2S_KSPLIT=n forces n ranges (A/B, tests; 1 = never split).
+// t.ksplit = n > 0 forces n ranges (M2S_KSPLIT: A/B, tests; 1 = never split); t.ksplit_max / t.ksplit_minst are
+// the 8 and the 4 above.  t is the caller's (switches.hpp): an engine plans every launch, and the blocks.2.0 route
+// that depends on it (conv_gemm_er_supported), from the values it was created under, not from the environment.
 // tiles: workgroups of the unsplit launch; nst: its K steps; lds: bytes per workgroup.
-int plan_ksplit(int tiles, int nst, size_t lds) {
+int plan_ksplit(int tiles, int nst, size_t lds, const ConvTune& t) {
   const int slots = device_cus() * std::max(1, std::min(2, (int)(160 * 1024 / lds)));
-  const char* fe = getenv("M2S_KSPLIT");  // read per launch: tests switch it between engines of one process
-  const int force = fe ? atoi(fe) : 0;
   int nks = 1;
-  if (force > 0)
-    nks = std::min(force, std::max(1, nst));
-  else if (2 * tiles <= slots && nst >= 8) {
-    const char* mx = getenv("M2S_KSPLIT_MAX");  // A/B of the split count (tools/ab_env.py)
-    const char* ms = getenv("M2S_KSPLIT_MINST");
-    nks = std::max(1, std::min({slots / tiles, nst / (ms ? std::max(1, atoi(ms)) : 4), mx ? std::max(1, atoi(mx)) : 8}));
-  }
+  if (t.ksplit > 0)
+    nks = std::min(t.ksplit, std::max(1, nst));
+  else if (2 * tiles <= slots && nst >= 8)
+    nks = std::max(1, std::min({slots / tiles, nst / t.ksplit_minst, t.ksplit_max}));
   return nks;
 }
 
 template <int BM, int BN, int MT, int NT, int KIND, int XF, int SP, int SF = 0>
-void launch_tile(const ConvBatch& b, hipStream_t s, int phases, double flops, double bytes) {
+void launch_tile(const ConvBatch& b, const ConvTune& tune, hipStream_t s, int phases, double flops, double bytes) {
   const ConvArgs& a = b.a[0];
   // keep two workgroups' LDS per CU (128 x 256: the SE gate table too, and 256 registers a wave);
   // split operands double the slot, so they run two stages (SF: a forced stage count, A/B builds)
@@ -897,15 +894,14 @@ void launch_tile(const ConvBatch& b, hipStream_t s, int phases, double flops, do
   M2S_CHECK(lds <= 160 * 1024, "conv_gemm: LDS budget");
   int nst = 0;
   for (int i = 0; i < (KIND == KIND_CONV1D ? phases : 1); ++i) nst = std::max(nst, b.a[i].kp / 32);
-  int nks = plan_ksplit(m_tiles * n_tiles * phases, nst, lds);
+  int nks = plan_ksplit(m_tiles * n_tiles * phases, nst, lds, tune);
   const size_t part_bytes = (size_t)phases * nks * a.M * a.cs_out * sizeof(float);
   if (nks > 1 && part_bytes > ((size_t)256 << 20)) nks = 1;
   float* kpart = nks > 1 ? ksplit_scratch(s, part_bytes) : nullptr;
   if (!kpart) nks = 1;  // (a stream under graph capture with no scratch large enough)
   dim3 grid(m_tiles * n_tiles, nks, phases);
   char name[96];
-  static const bool detail = getenv("M2S_PROF_DETAIL") != nullptr;
-  if (detail)  // per-layer records for analysis: K x N and rows per launch
+  if (prof_detail())  // per-layer records for analysis: K x N and rows per launch
     snprintf(name, sizeof(name), "conv_gemm<%s,%dx%d%s> K%d N%d M%d", kname(KIND), BM, BN, SP == 1 ? ",x3" : SP == 2 ? ",e4m3" : "", a.kp, a.cs_out, a.M);
   else
     snprintf(name, sizeof(name), "conv_gemm_kernel<%d, %d, %d, %d, %d, %d, %d, %d>", BM, BN, MT, NT, S, KIND, XF, SP);
@@ -924,28 +920,27 @@ void launch_tile(const ConvBatch& b, hipStream_t s, int phases, double flops, do
 }
 
 template <int KIND, int XF, int SP>
-void launch_kind_xf(const ConvBatch& a, hipStream_t s, int phases, double flops, double bytes) {
+void launch_kind_xf(const ConvBatch& a, const ConvTune& tune, hipStream_t s, int phases, double flops, double bytes) {
   const int n = a.a[0].cs_out;
   if constexpr (SP != 0) {  // split / e4m3 operands: 16/32/64-wide tiles for narrow outputs, else 128 x 128
     if (n <= 16)
-      return launch_tile<256, 16, 4, 1, KIND, XF, SP>(a, s, phases, flops, bytes);
+      return launch_tile<256, 16, 4, 1, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
     if (n <= 32)  // (a 128 x 32 tile at three stages: 0.1 ms per step slower on the C = 32 MRF convs)
-      return launch_tile<256, 32, 4, 2, KIND, XF, SP>(a, s, phases, flops, bytes);
+      return launch_tile<256, 32, 4, 2, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
     if (n <= 64 || (n % 128 != 0 && ceil_div(n, 64) * 64 < ceil_div(n, 128) * 128)) {
       // split 64-wide outputs: 128 x 64 at three stages (77 KB, two workgroups per CU) instead of
       // 256 x 64 at two (84 KB, one per CU): the C = 64 MRF convs 3.7 -> 3.1 ms per step
-      if (SP == 1 && n <= 64) return launch_tile<128, 64, 4, 2, KIND, XF, SP>(a, s, phases, flops, bytes);
-      return launch_tile<256, 64, 4, 4, KIND, XF, SP>(a, s, phases, flops, bytes);
+      if (SP == 1 && n <= 64) return launch_tile<128, 64, 4, 2, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
+      return launch_tile<256, 64, 4, 4, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
     }
     if constexpr (SP == 1 && KIND == KIND_CONV1D && XF == IN_NONE) {  // A/B: the split MRF convs on 128 x 64 tiles
-      static const bool bn64 = getenv("M2S_CG_BN64") && atoi(getenv("M2S_CG_BN64")) == 1;  // (3 stages, 2 per CU)
-      if (bn64) return launch_tile<128, 64, 4, 2, KIND, XF, SP>(a, s, phases, flops, bytes);
+      // (3 stages, 2 per CU; M2S_CG_BN64 / M2S_CG_STAGES as the caller's engine read them: switches.hpp ConvTune)
+      if (tune.bn64) return launch_tile<128, 64, 4, 2, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
       // A/B: 3 or 4 stages at one workgroup per CU (101 / 135 KB) instead of 2 stages at two
-      static const int stg = getenv("M2S_CG_STAGES") ? atoi(getenv("M2S_CG_STAGES")) : 0;
-      if (stg == 3) return launch_tile<128, 128, 4, 4, KIND, XF, SP, 3>(a, s, phases, flops, bytes);
-      if (stg == 4) return launch_tile<128, 128, 4, 4, KIND, XF, SP, 4>(a, s, phases, flops, bytes);
+      if (tune.stages == 3) return launch_tile<128, 128, 4, 4, KIND, XF, SP, 3>(a, tune, s, phases, flops, bytes);
+      if (tune.stages == 4) return launch_tile<128, 128, 4, 4, KIND, XF, SP, 4>(a, tune, s, phases, flops, bytes);
     }
-    return launch_tile<128, 128, 4, 4, KIND, XF, SP>(a, s, phases, flops, bytes);
+    return launch_tile<128, 128, 4, 4, KIND, XF, SP>(a, tune, s, phases, flops, bytes);
   } else {
   if constexpr (KIND == KIND_GEMM || KIND == KIND_CONV2D) if (a.a[0].M >= 256 * 256 && n > 128 &&
                                                                ((n <= 256 && a.a[0].kp >= 512) || KIND == KIND_GEMM)) {
@@ -954,28 +949,29 @@ void launch_kind_xf(const ConvBatch& a, hipStream_t s, int phases, double flops,
     // b2 conv_exp 3x3 56 -> 224: 1.10 -> 0.91 ms per launch); also every wide 1x1 GEMM (the
     // stride-2 IR expansions K 64 / 128 -> 224 / 736: 526 -> 457 us per launch).  A 256x128 tile
     // for n <= 128 measured slower at every K (one wave per SIMD at 272 registers).
-    return launch_tile<128, 256, 4, 8, KIND, XF, 0>(a, s, phases, flops, bytes);
+    return launch_tile<128, 256, 4, 8, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
   }
   if constexpr (KIND == KIND_GEMM)
     if (a.a[0].M >= 256 * 256 && n > 64 && n <= 128 && a.a[0].kp >= 384) {
       // 256 rows x 128 outputs at two waves per SIMD: the weight tile (K x 128) is re-read from L2
       // once per 256 rows instead of per 128 (the SE-scaled conv_pwl of blocks.3/4: K 416..736)
-      return launch_tile<256, 128, 8, 4, KIND, XF, 0>(a, s, phases, flops, bytes);
+      return launch_tile<256, 128, 8, 4, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
     }
   if (n <= 16)
-    launch_tile<256, 16, 4, 1, KIND, XF, 0>(a, s, phases, flops, bytes);
+    launch_tile<256, 16, 4, 1, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
   else if (n <= 32)
-    launch_tile<256, 32, 4, 2, KIND, XF, 0>(a, s, phases, flops, bytes);
+    launch_tile<256, 32, 4, 2, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
   else if (n <= 64 || (n % 128 != 0 && ceil_div(n, 64) * 64 < ceil_div(n, 128) * 128))
-    launch_tile<256, 64, 4, 4, KIND, XF, 0>(a, s, phases, flops, bytes);
+    launch_tile<256, 64, 4, 4, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
   else
-    launch_tile<128, 128, 4, 4, KIND, XF, 0>(a, s, phases, flops, bytes);
+    launch_tile<128, 128, 4, 4, KIND, XF, 0>(a, tune, s, phases, flops, bytes);
   }
 }
 
 // Only the (kind, input transform) pairs the hot path uses are instantiated.
 template <int KIND, int SP>
-void launch_kind(const ConvArgs& a0, hipStream_t s, int phases, double flops, double bytes, const ConvBatch* batch = nullptr) {
+void launch_kind(const ConvArgs& a0, const ConvTune& tune, hipStream_t s, int phases, double flops, double bytes,
+                 const ConvBatch* batch = nullptr) {
   ConvBatch bl;
   if (!batch) {
     std::memset(&bl, 0, sizeof(bl));
@@ -983,13 +979,13 @@ void launch_kind(const ConvArgs& a0, hipStream_t s, int phases, double flops, do
   }
   const ConvBatch& a = batch ? *batch : bl;
   if (a0.in_xform == IN_NONE) {
-    launch_kind_xf<KIND, IN_NONE, SP>(a, s, phases, flops, bytes);
+    launch_kind_xf<KIND, IN_NONE, SP>(a, tune, s, phases, flops, bytes);
   } else if constexpr (KIND == KIND_CONV1D || KIND == KIND_CONVT) {
     M2S_CHECK(a0.in_xform == IN_LRELU, "conv_gemm: 1-D kinds take LeakyReLU inputs only");
-    launch_kind_xf<KIND, IN_LRELU, SP>(a, s, phases, flops, bytes);
+    launch_kind_xf<KIND, IN_LRELU, SP>(a, tune, s, phases, flops, bytes);
   } else if constexpr (KIND == KIND_GEMM) {
     M2S_CHECK(a0.in_xform == IN_SE_SCALE, "conv_gemm: GEMM kind takes SE-scaled inputs only");
-    launch_kind_xf<KIND, IN_SE_SCALE, SP>(a, s, phases, flops, bytes);
+    launch_kind_xf<KIND, IN_SE_SCALE, SP>(a, tune, s, phases, flops, bytes);
   } else {
     M2S_CHECK(false, "conv_gemm: 2-D convs take untransformed inputs");
   }
@@ -997,7 +993,7 @@ void launch_kind(const ConvArgs& a0, hipStream_t s, int phases, double flops, do
 
 }  // namespace
 
-void launch_conv_gemm_batch(const ConvArgs* as, int n, hipStream_t s, double flops, double bytes) {
+void launch_conv_gemm_batch(const ConvArgs* as, int n, const ConvTune& tune, hipStream_t s, double flops, double bytes) {
   M2S_CHECK(n >= 1 && n <= CONV_BATCH, "conv_gemm batch: 1..CONV_BATCH convs");
   const ConvArgs& a = as[0];
   M2S_CHECK(a.kind == KIND_CONV1D && a.cs_in >= 32 && a.cs_in % 32 == 0 && a.cs_out % 4 == 0, "conv_gemm batch: 1-D convs, cs_in % 32 == 0");
@@ -1017,7 +1013,7 @@ void launch_conv_gemm_batch(const ConvArgs* as, int n, hipStream_t s, double flo
     b.a[i] = c;
   }
   if (a.M <= 0) return;
-  launch_kind<KIND_CONV1D, 1>(a, s, n, flops, bytes, &b);
+  launch_kind<KIND_CONV1D, 1>(a, tune, s, n, flops, bytes, &b);
   M2S_HIP(hipGetLastError());
 }
 
@@ -1026,7 +1022,7 @@ constexpr int ER_BM = 128, ER_BN = 128, ER_S = 2;  // launch_kind_xf's tile and 
 constexpr size_t ER_LDS = (size_t)ER_S * (2 * (ER_BM + ER_BN) + 16) * ROW;
 }  // namespace
 
-bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q) {
+bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q, const ConvTune& tune) {
   const bool exp_ok = e.kind == KIND_CONV2D && e.ks == 3 && e.ntaps == 9 && e.cs_in >= 32 && e.cs_in % 32 == 0 &&
                       e.kp % 32 == 0 && e.kp >= 9 * e.cs_in && e.cs_out == ER_BN && e.n_pad >= ER_BN && e.act == ACT_SILU &&
                       !e.res && !e.accum && e.in_xform == IN_NONE && !e.wscale && e.M > 0 && e.OH > 0 && e.OW > 0 &&
@@ -1035,11 +1031,12 @@ bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q) {
                       q.n_pad >= 64 && q.act == ACT_NONE && !q.res && !q.accum && q.in_xform == IN_NONE && !q.wscale &&
                       q.M == e.M;
   // only where conv_gemm would run conv_exp unsplit: a split-K launch leaves partial sums, not the mid tile
-  return exp_ok && pwl_ok && plan_ksplit(ceil_div(e.M, ER_BM), e.kp / 32, ER_LDS) == 1;
+  return exp_ok && pwl_ok && plan_ksplit(ceil_div(e.M, ER_BM), e.kp / 32, ER_LDS, tune) == 1;
 }
 
-void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, hipStream_t s, double flops, double bytes) {
-  M2S_CHECK(conv_gemm_er_supported(e, q), "conv_gemm_er: unsupported block");
+void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, const ConvTune& tune, hipStream_t s, double flops,
+                         double bytes) {
+  M2S_CHECK(conv_gemm_er_supported(e, q, tune), "conv_gemm_er: unsupported block");
   M2S_CHECK(e.x && e.w && e.bias && q.w && q.bias && q.y && q.y != e.x, "conv_gemm_er: operand pointers");
   ConvBatch b;
   std::memset(&b, 0, sizeof(b));
@@ -1054,7 +1051,7 @@ void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, hipStream_t s, do
   M2S_HIP(hipGetLastError());
 }
 
-void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops, double bytes) {
+void launch_conv_gemm(const ConvArgs& a, bool split, const ConvTune& tune, hipStream_t s, double flops, double bytes) {
   M2S_CHECK(a.cs_in % 8 == 0 && a.cs_out % 4 == 0, "conv_gemm: channel strides");
   M2S_CHECK(a.cs_in >= 32 ? a.cs_in % 32 == 0 : 32 % a.cs_in == 0, "conv_gemm: channel stride vs the 32-wide K step");
   M2S_CHECK(a.ntaps <= 31, "conv_gemm: at most 31 taps");
@@ -1071,10 +1068,10 @@ void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops
   M2S_CHECK(!(split && a.wscale), "conv_gemm: e4m3 operands take bf16 storage");
   if (split) {
     switch (a.kind) {
-      case KIND_CONV2D: launch_kind<KIND_CONV2D, 1>(a, s, 1, flops, bytes); break;
-      case KIND_CONV1D: launch_kind<KIND_CONV1D, 1>(a, s, 1, flops, bytes); break;
-      case KIND_CONVT: launch_kind<KIND_CONVT, 1>(a, s, a.ct_u, flops, bytes); break;
-      case KIND_GEMM: launch_kind<KIND_GEMM, 1>(a, s, 1, flops, bytes); break;
+      case KIND_CONV2D: launch_kind<KIND_CONV2D, 1>(a, tune, s, 1, flops, bytes); break;
+      case KIND_CONV1D: launch_kind<KIND_CONV1D, 1>(a, tune, s, 1, flops, bytes); break;
+      case KIND_CONVT: launch_kind<KIND_CONVT, 1>(a, tune, s, a.ct_u, flops, bytes); break;
+      case KIND_GEMM: launch_kind<KIND_GEMM, 1>(a, tune, s, 1, flops, bytes); break;
       default: M2S_CHECK(false, "conv_gemm: bad kind");
     }
     M2S_HIP(hipGetLastError());
@@ -1082,10 +1079,10 @@ void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops
   }
   if (a.wscale) {  // e4m3 operands
     switch (a.kind) {
-      case KIND_CONV2D: launch_kind<KIND_CONV2D, 2>(a, s, 1, flops, bytes); break;
-      case KIND_CONV1D: launch_kind<KIND_CONV1D, 2>(a, s, 1, flops, bytes); break;
-      case KIND_CONVT: launch_kind<KIND_CONVT, 2>(a, s, a.ct_u, flops, bytes); break;
-      case KIND_GEMM: launch_kind<KIND_GEMM, 2>(a, s, 1, flops, bytes); break;
+      case KIND_CONV2D: launch_kind<KIND_CONV2D, 2>(a, tune, s, 1, flops, bytes); break;
+      case KIND_CONV1D: launch_kind<KIND_CONV1D, 2>(a, tune, s, 1, flops, bytes); break;
+      case KIND_CONVT: launch_kind<KIND_CONVT, 2>(a, tune, s, a.ct_u, flops, bytes); break;
+      case KIND_GEMM: launch_kind<KIND_GEMM, 2>(a, tune, s, 1, flops, bytes); break;
       default: M2S_CHECK(false, "conv_gemm: bad kind");
     }
     M2S_HIP(hipGetLastError());
@@ -1093,10 +1090,10 @@ void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops
   }
   if (conv_halo_supported(a)) return launch_conv_halo(a, s, flops, bytes);
   switch (a.kind) {
-    case KIND_CONV2D: launch_kind<KIND_CONV2D, 0>(a, s, 1, flops, bytes); break;
-    case KIND_CONV1D: launch_kind<KIND_CONV1D, 0>(a, s, 1, flops, bytes); break;
-    case KIND_CONVT: launch_kind<KIND_CONVT, 0>(a, s, a.ct_u, flops, bytes); break;
-    case KIND_GEMM: launch_kind<KIND_GEMM, 0>(a, s, 1, flops, bytes); break;
+    case KIND_CONV2D: launch_kind<KIND_CONV2D, 0>(a, tune, s, 1, flops, bytes); break;
+    case KIND_CONV1D: launch_kind<KIND_CONV1D, 0>(a, tune, s, 1, flops, bytes); break;
+    case KIND_CONVT: launch_kind<KIND_CONVT, 0>(a, tune, s, a.ct_u, flops, bytes); break;
+    case KIND_GEMM: launch_kind<KIND_GEMM, 0>(a, tune, s, 1, flops, bytes); break;
     default: M2S_CHECK(false, "conv_gemm: bad kind");
   }
   M2S_HIP(hipGetLastError());

@@ -302,10 +302,10 @@ void launch_kind(const ConvArgs& a, hipStream_t s, int phases, double flops, dou
 }  // namespace
 
 template <typename T>
-void launch_conv(const ConvArgs& a, hipStream_t s, double flops, double bytes) {
+void launch_conv(const ConvArgs& a, const ConvTune& tune, hipStream_t s, double flops, double bytes) {
   if constexpr (!std::is_same<T, float>::value) {  // bf16 / split fp32: LDS-DMA pipeline (conv_gemm.hip)
     M2S_CHECK(a.kind != KIND_CONV2D || a.ks == 3, "conv: bf16 / split 2-D convs are 3x3");
-    launch_conv_gemm(a, std::is_same<T, sp_t>::value, s, flops, bytes);
+    launch_conv_gemm(a, std::is_same<T, sp_t>::value, tune, s, flops, bytes);
   } else {  // exact f32 products: the direct-load kernel of this file
     constexpr int KC = Elem<T>::KC;
     M2S_CHECK(a.cs_in % KC == 0 || KC % a.cs_in == 0, "conv: cs_in incompatible with K chunk");
@@ -324,8 +324,8 @@ void launch_conv(const ConvArgs& a, hipStream_t s, double flops, double bytes) {
   }
 }
 
-template void launch_conv<float>(const ConvArgs&, hipStream_t, double, double);
-template void launch_conv<bf16_t>(const ConvArgs&, hipStream_t, double, double);
-template void launch_conv<sp_t>(const ConvArgs&, hipStream_t, double, double);
+template void launch_conv<float>(const ConvArgs&, const ConvTune&, hipStream_t, double, double);
+template void launch_conv<bf16_t>(const ConvArgs&, const ConvTune&, hipStream_t, double, double);
+template void launch_conv<sp_t>(const ConvArgs&, const ConvTune&, hipStream_t, double, double);
 
 }  // namespace m2s

@@ -16,6 +16,7 @@
 #pragma once
 
 #include "m2s_common.hpp"
+#include "switches.hpp"
 
 namespace m2s {
 
@@ -67,24 +68,28 @@ struct ConvBatch {
 // flops / bytes: algorithmic work of this launch, recorded by the profiler (m2s_prof_*).
 // bf16 and split fp32 (sp_t) run the LDS-DMA pipelined kernel (conv_gemm.hip); fp32 (the exact
 // f32-MFMA parity path) runs the direct-load kernel of conv_igemm.hip.
+// tune: the caller's conv_gemm tiling and split-K switches (switches.hpp; an engine passes the ones it was created
+// under, so a route decision and its launch agree).  The fp32 direct-load kernel ignores it.
 template <typename T>
-void launch_conv(const ConvArgs& a, hipStream_t s, double flops = 0.0, double bytes = 0.0);
+void launch_conv(const ConvArgs& a, const ConvTune& tune, hipStream_t s, double flops = 0.0, double bytes = 0.0);
 // split: x, w, res, y and in_scale hold [hi | lo] rows (m2s_common.hpp sp_t); w rows are 2 * kp long.
 // a.wscale set (bf16 storage only): e4m3 operands - w holds e4m3-grid values (exact in bf16) of
 // w / wscale[n], the activation fragments are rounded to e4m3 after the LDS read, the products run
 // on v_mfma_f32_16x16x32_fp8_fp8 and the epilogue multiplies by wscale[n].
-void launch_conv_gemm(const ConvArgs& a, bool split, hipStream_t s, double flops, double bytes);
+void launch_conv_gemm(const ConvArgs& a, bool split, const ConvTune& tune, hipStream_t s, double flops, double bytes);
 // Split-fp32 stride-2 EdgeResidual block (blocks.2.0: 32 -> 128 -> 56 channels) in one launch: `e` is the 3x3
 // conv_exp (+ bn1 + SiLU) exactly as launch_conv_gemm would take it (e.y unused), `q` the 1x1 conv_pwl (+ bn2) as
 // a KIND_GEMM conv (q.x unused).  The 128 x 128 conv_exp tile's SiLU'd, split mid channels stay in LDS and conv_pwl
 // runs on them as an epilogue GEMM: the same MFMAs in the same order as the two launches, without the mid map's
-// round trip through memory.  Supported where conv_exp would run unsplit (no split K: M2S_KSPLIT, small grids) on
-// 128 mid channels with at most 64 (padded) outputs; callers fall back to the two launches otherwise.
-bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q);
-void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, hipStream_t s, double flops, double bytes);
+// round trip through memory.  Supported where conv_exp would run unsplit (no split K: tune.ksplit, small grids) on
+// 128 mid channels with at most 64 (padded) outputs; callers fall back to the two launches otherwise.  The check
+// and the launch take the same `tune` (the engine's), so both plan the split from one value.
+bool conv_gemm_er_supported(const ConvArgs& e, const ConvArgs& q, const ConvTune& tune);
+void launch_conv_gemm_er(const ConvArgs& e, const ConvArgs& q, const ConvTune& tune, hipStream_t s, double flops,
+                         double bytes);
 // n (1..CONV_BATCH) split-fp32 KIND_CONV1D convs of one shape in one launch; put the longest K first
 // (blocks dispatch in z order, so the longest tiles start first and the short ones fill the tail).
-void launch_conv_gemm_batch(const ConvArgs* a, int n, hipStream_t s, double flops, double bytes);
+void launch_conv_gemm_batch(const ConvArgs* a, int n, const ConvTune& tune, hipStream_t s, double flops, double bytes);
 // bf16 3x3 stride-1 convs with cs_in in {32, 64}: persistent LDS-resident-weight kernel
 // (conv_halo.hip); launch_conv_gemm routes them there.
 bool conv_halo_supported(const ConvArgs& a);

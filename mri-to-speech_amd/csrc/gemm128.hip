@@ -487,7 +487,8 @@ bool se_gemm_sp_supported(int P, int cs_in, int cs_out) {
 }
 
 void launch_se_gemm_sp(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias,
-                       const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes) {
+                       const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes,
+                       int waves) {
   M2S_CHECK(se_gemm_sp_supported(P, cs_in, cs_out) && M % P == 0, "se_gemm_sp: unsupported shape");
   M2S_CHECK(x && w && bias && gate && y && y != res && y != x, "se_gemm_sp: operand pointers");
   M2S_CHECK((double)M * cs_in * 4 < 4294967295.0 * 4, "se_gemm_sp: input too large");
@@ -504,11 +505,6 @@ void launch_se_gemm_sp(const void* x, int M, int P, int cs_in, const void* w, in
   a.cs_in = cs_in;
   a.kp = cs_in;  // weight rows [hi kp | lo kp] with kp = cs_in (conv_gemm's split packing)
   a.cs_out = cs_out;
-  static const int waves = [] {
-    const char* e = std::getenv("M2S_SE_SP_WAVES");
-    return e && std::atoi(e) == 4 ? 4 : 8;
-  }();
-
   if (cs_out <= 128) {
     M2S_CHECK(n_pad >= 128, "se_gemm_sp: weight rows");
     if (waves == 8)  // 256 x 128, two waves per SIMD (each gates its rows' fragments for its 64 columns)

@@ -765,7 +765,7 @@ bool ir_ws_supported(int H, int W, int cs_in, int kp, int cs_mid) {
 void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_mid, const void* wpw, const float* bpw,
                   const float* wdw, const float* bdw, void* y, void* se_mean, double flops, double bytes,
                   hipStream_t s, AsyncReport rep, int stride, int OH, int OW, int pad_t, int pad_l, double spill,
-                  bool fm32) {
+                  bool fm32, int forced_parts) {
   M2S_CHECK(stride == 1 ? ir_ws_supported(H, W, cs_in, kp, cs_mid)
                         : stride == 2 && ir_ws_s2_supported(H, W, cs_in, kp, cs_mid, OH, OW, pad_t, pad_l),
             "ir_ws: unsupported shape");
@@ -781,8 +781,8 @@ void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_
   const int n_full = N / G * G, rem = N - n_full;
   int parts = rem > 0 ? std::max(1, (G + rem / 2) / rem) : 1;
   parts = std::max(1, std::min(parts, NSl / 3));
-  if (const char* e = getenv("M2S_IRWS_PARTS"))  // A/B: n = n ranges (1 = no tail split), 0 = the rule above
-    if (atoi(e) > 0) parts = std::min(atoi(e), std::max(1, NSl / 3));
+  // A/B (the caller's Switches::irws_parts): n = n ranges (1 = no tail split), 0 = the rule above
+  if (forced_parts > 0) parts = std::min(forced_parts, std::max(1, NSl / 3));
 #ifdef IRWS_TRACE
   static unsigned long long* tr = [] {
     unsigned long long* p = nullptr;

@@ -71,7 +71,8 @@ void launch_se_gemm_f8(const void* x8, int M, int P, int cs_in, const void* w8, 
 // gate split (M / P, [hi cs_in | lo cs_in]), res / y split (M, [hi cs_out | lo cs_out]).  P % 64 == 0.
 bool se_gemm_sp_supported(int P, int cs_in, int cs_out);
 void launch_se_gemm_sp(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias,
-                       const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes);
+                       const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes,
+                       int waves);  // waves: 8 (two a SIMD) or 4 a workgroup (Switches::se_sp_waves)
 
 // The same split SE-gated conv_pwl as a persistent warp-specialised GEMM: loader waves fill a 3-slot LDS
 // ring by LDS-DMA and consumer waves compute, synchronised by per-slot FULL / FREE counters in LDS (no
@@ -83,9 +84,11 @@ bool se_ws_supported(int P, int cs_in, int cs_out);
 // x_f32: x holds plain fp32 rows [M][cs_in] (ir_ws's fm32 output) instead of the interleaved split layout.
 // rev: the workgroups walk their tiles from the last row tile down (the rows a forward-walking producer wrote last
 // are read first); every tile's result is independent of the order.
+// half: a short last round runs as half tiles (Switches::sews_half); cfg: tile / ring variant, 0 = the default
+// (Switches::se_ws_cfg; A/B only).
 void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias, const void* gate,
-                  const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes, AsyncReport rep = {},
-                  bool x_f32 = false, bool rev = false);
+                  const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes, AsyncReport rep,
+                  bool x_f32, bool rev, bool half, int cfg);
 
 // fp8 engines: launch_se_gemm_f8's operation (e4m3 x8 / w8, bf16 gate / res / y) on the same warp-specialised
 // flag ring.  (se_ws.hip)
@@ -93,7 +96,7 @@ bool se_ws_f8_supported(int P, int cs_in, int cs_out);
 // y8 (optional): an e4m3 copy of y, rows of ld8 bytes (the next IR block's e4m3 expand operand, launch_ir_pwdw x8)
 void launch_se_ws_f8(const void* x8, int M, int P, int cs_in, const void* w8, int kp, int n_pad, const float* wscale,
                      const float* bias, const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops,
-                     double bytes, void* y8 = nullptr, int ld8 = 0, AsyncReport rep = {});
+                     double bytes, void* y8 = nullptr, int ld8 = 0, AsyncReport rep = {}, bool half = false);
 
 // The same for a stride-2 depthwise (TF-SAME, top / left pads pad_t / pad_l) on an IH x IW <= 256-pixel
 // conv_pw map: y (N, OH*OW, cs_mid), se_mean over the OH x OW output.  (ir_fused.hip)
@@ -108,9 +111,10 @@ bool ir_ws_s2_supported(int H, int W, int cs_in, int kp, int cs_mid, int OH, int
 void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_mid, const void* wpw, const float* bpw,
                   const float* wdw, const float* bdw, void* y, void* se_mean, double flops, double bytes,
                   hipStream_t s, AsyncReport rep = {}, int stride = 1, int OH = 0, int OW = 0, int pad_t = 0,
-                  int pad_l = 0, double spill = 0.0, bool fm32 = false);
+                  int pad_l = 0, double spill = 0.0, bool fm32 = false, int parts = 0);
 // fm32: y is stored as plain fp32 rows [N * OH * OW][cs_mid] (for launch_se_ws(x_f32 = true)) instead of the
 // interleaved split layout: one 16-byte store per 4 channels, no split in the consumers.
+// parts > 0: that many slice ranges for the tail images instead of the launcher's rule (Switches::irws_parts).
 // Stride-2 IR front half on bands of 4 output rows (blocks.3.0: 32x32 -> 16x16), split fp32 or bf16: y =
 // the SE GEMM's operand (N, OH*OW, cs_mid; split: interleaved hi/lo), psum = squeeze partial sums
 // (N, OH / 4, cs_mid) for launch_se_mean.  wdw: fp32 tap-major [9][cs_mid].  (ir_s2band.hip)
@@ -169,7 +173,9 @@ void launch_rb1_fused(const bf16_t* x, bf16_t* s, int B, int L, int C, int k, in
 // split fp32 (`split`: [hi | lo] weight rows, y in sp_t layout).  (stem_b0.hip)
 void launch_stem_b0(const float* frames, int N, int H, int W, int OH, int OW, int pad_t, int pad_l, const float* w9,
                     const float* b9, const void* w0, const float* b0, int kp0, const void* w1, const float* b1,
-                    int kp1, void* y, bool split, double flops, double bytes, hipStream_t s);
+                    int kp1, void* y, bool split, double flops, double bytes, hipStream_t s, int parts);
+// parts > 0: that many tile-row ranges a strip (clamped to the tile rows) instead of the launcher's fill rule
+// (Switches::stem_parts)
 
 // SqueezeExcite excitation (bf16, or split fp32 with split = true): gate (N, cs_mid) =
 // sigmoid(W2 · SiLU(W1 · mean + b1) + b2), mean (N, cs_mid) from the squeeze; w1 packed [>= rd][kp1],
@@ -264,19 +270,23 @@ size_t lstm_persistent_sync_bytes();
 // `err_host` (pinned, host-mapped) and writes NaN to the rest of the outputs.
 // Small batches (B <= 4): the same recurrence with h exchanged as data-tagged granules instead of a
 // counter barrier, VALU dot products (lstm_persistent.hip).  `sync` = lstm_small_sync_bytes().
-bool lstm_small_supported(int B, int H);
+// small_cap: the batch limit, 4 or 8 (Switches::lstm_small_b: 8 selects the 8-sequence instantiation for B <= 8); the
+// check and the launch take the engine's one value
+bool lstm_small_supported(int B, int H, int small_cap);
 size_t lstm_small_sync_bytes();
 // epoch: the engine's epoch count for a sync buffer of its own (tags continue across calls, no memset; null = zero
 // the buffer every call)
 void launch_lstm_small(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                       unsigned* err_host, hipStream_t s, unsigned* epoch = nullptr);
+                       unsigned* err_host, hipStream_t s, int small_cap, unsigned* epoch = nullptr);
 constexpr unsigned LSTM_SPIN_MAX = 1u << 24;
 // 4 < B <= 64: the same granule exchange with 512-thread workgroups, sequences in chunks of 16 whose
 // sweep overlaps the previous chunk's dot products (lstm_persistent.hip).  `sync` = lstm_mid_sync_bytes().
-bool lstm_mid_supported(int B, int H);
+// small_cap: as lstm_small_supported (lstm_mid starts above it); chunk: sequences per chunk, 4 / 8 / 16 forced
+// (Switches::lstm_mid_ch), else 4 up to B = 8 and 8 above
+bool lstm_mid_supported(int B, int H, int small_cap);
 size_t lstm_mid_sync_bytes();
 void launch_lstm_mid(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s);
+                     unsigned* err_host, hipStream_t s, int small_cap, int chunk);
 void launch_lstm_persistent(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync,
                             unsigned spin_max, unsigned* err_host, hipStream_t s);
 // B > 4 in split fp32 (the bf16x3 / bf16 / fp8 engines): three bf16 MFMA terms over W_hh and h_t split

@@ -584,7 +584,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
 // run on VALU: lane (wave, k half, row) holds the same 80 W_hh values as above and forms B fp32 dot
 // products of 80 terms; the 8 K-slice partials of each gate row are summed in LDS in a fixed order.
 constexpr int LS_BMAX = 4;   // default small-batch limit
-constexpr int LS_BCAP = 8;   // largest instantiation (M2S_LSTM_SMALL_B = 8 selects it for B <= 8)
+constexpr int LS_BCAP = 8;   // largest instantiation (a cap of 8, the engine's M2S_LSTM_SMALL_B, selects it for B <= 8)
 
 template <int LS_BMAX>
 __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restrict__ pre, const float* __restrict__ whh,
@@ -869,33 +869,22 @@ __global__ void __launch_bounds__(LM_THREADS, 1) lstm_mid_kernel(const float* __
 
 }  // namespace
 
-static int small_cap() {
-  static const int cap = [] {
-    const char* e = std::getenv("M2S_LSTM_SMALL_B");
-    return e && std::atoi(e) == 8 ? 8 : LS_BMAX;
-  }();
-  return cap;
-}
-
 // 4 < B <= 16: above 16 sequences every workgroup's sweep of B x 640 granules per step (sc1 loads, the
 // exchange volume grows with B) costs more than the counter barrier's plain loads of h (tools/lstm_bench.py,
 // profiles/r03f_lstm_ab.txt: B = 32 20.2 vs 18.3 us, B = 64 40.9 vs 24.7 us per step)
-bool lstm_mid_supported(int B, int H) { return H == LP_H && B > small_cap() && B <= 16; }
+// small_cap: lstm_small's batch limit (4 or 8: Switches::lstm_small_b, the caller's), which lstm_mid starts above
+bool lstm_mid_supported(int B, int H, int small_cap) { return H == LP_H && B > small_cap && B <= 16; }
 
 size_t lstm_mid_sync_bytes() { return 256 + (size_t)2 * 2 * LM_BMAX * LP_H * sizeof(unsigned long long); }
 
 void launch_lstm_mid(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s) {
-  M2S_CHECK(lstm_mid_supported(B, H) && T > 0, "lstm_mid: unsupported shape");
+                     unsigned* err_host, hipStream_t s, int small_cap, int chunk) {
+  M2S_CHECK(lstm_mid_supported(B, H, small_cap) && T > 0, "lstm_mid: unsupported shape");
   const int grid = 2 * (H / LP_U);
   // sequences per chunk: 4 up to B = 8 (two chunks at B = 8: the second one's sweep overlaps the first's
-  // dot products; 6.5 us per step vs 8.6 at one chunk of 8), 8 above; env M2S_LSTM_MID_CH for A/B runs
-  static const int ch_env = [] {
-    const char* e = std::getenv("M2S_LSTM_MID_CH");
-    const int v = e ? std::atoi(e) : 0;
-    return v == 4 || v == 8 || v == 16 ? v : 0;
-  }();
-  const int ch = ch_env ? ch_env : (B <= 8 ? 4 : 8);
+  // dot products; 6.5 us per step vs 8.6 at one chunk of 8), 8 above; chunk = 4 / 8 / 16 (the caller's
+  // Switches::lstm_mid_ch, M2S_LSTM_MID_CH) forces one for A/B runs
+  const int ch = chunk == 4 || chunk == 8 || chunk == 16 ? chunk : (B <= 8 ? 4 : 8);
   const void* fn = ch == 4 ? reinterpret_cast<const void*>(&lstm_mid_kernel<4>)
                    : ch == 16 ? reinterpret_cast<const void*>(&lstm_mid_kernel<16>)
                               : reinterpret_cast<const void*>(&lstm_mid_kernel<8>);
@@ -918,7 +907,7 @@ void launch_lstm_mid(const float* pre, const float* whh, float* hs, int B, int T
 
 bool lstm_persistent_supported(int H) { return H == LP_H; }
 
-bool lstm_small_supported(int B, int H) { return H == LP_H && B >= 1 && B <= small_cap(); }
+bool lstm_small_supported(int B, int H, int small_cap) { return H == LP_H && B >= 1 && B <= small_cap; }
 
 // Epoch tags for the granule hand-off (lstm_small, lstm_x3g): a launch publishes tags ep + step + 1 and waits for
 // ep + step, its timeout mark is ep + 1, and the engine's counter advances by T + 1 a launch, so every tag and mark of
@@ -941,10 +930,11 @@ unsigned lstm_epoch(void* sync, size_t bytes, int T, unsigned* epoch, hipStream_
 size_t lstm_small_sync_bytes() { return 256 + (size_t)2 * 2 * LS_BCAP * LP_H * sizeof(unsigned long long); }
 
 void launch_lstm_small(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                       unsigned* err_host, hipStream_t s, unsigned* epoch) {
-  M2S_CHECK(lstm_small_supported(B, H) && T > 0, "lstm_small: unsupported shape");
+                       unsigned* err_host, hipStream_t s, int small_cap, unsigned* epoch) {
+  M2S_CHECK((small_cap == LS_BMAX || small_cap == LS_BCAP) && lstm_small_supported(B, H, small_cap) && T > 0,
+            "lstm_small: unsupported shape");
   const int grid = 2 * (H / LP_U);
-  const bool b8 = B > LS_BMAX;  // the 8-sequence instantiation (M2S_LSTM_SMALL_B = 8)
+  const bool b8 = B > LS_BMAX;  // the 8-sequence instantiation (small_cap = 8)
   const void* fn = b8 ? reinterpret_cast<const void*>(&lstm_small_kernel<LS_BCAP>)
                       : reinterpret_cast<const void*>(&lstm_small_kernel<LS_BMAX>);
   const int resident = device_resident(fn, 256, 0);

@@ -278,46 +278,6 @@ class Acoustic {
   int device() const { return device_; }
   int n_mels() const { return n_mels_; }
   int chunk = 1920;  // = m2s.config.CNN_CHUNK (the benched pass size)
-  bool ir_fused_ = true;  // bf16: fused conv_pw + conv_dw + SE squeeze (env M2S_IR_FUSED=0 disables)
-  bool ir_ws_ = true;     // split fp32: the persistent warp-specialised form of it (env M2S_IR_WS=0 disables)
-  bool ir_ws_s2_ = true;  // ... also for the stride-2 block at 16x16 (env M2S_IR_WS_S2=0: ir_pwdw_s2)
-  // Small passes (the reference CLI's one clip, configs[1]'s 8 x 4): the persistent one-workgroup-per-image (ir_ws)
-  // and one-tile-per-CU (se_ws) kernels fill a few dozen CUs there, so below these sizes the pass runs the grid forms
-  // (ir_pwdw / ir_pwdw_s2, the split-K conv_gemm SE GEMM).  Env M2S_IRWS_MIN (images per pass) / M2S_SEWS_MIN (se_ws
-  // tiles, in CUs: 1 = one full round) override.
-  int irws_min_ = 512;
-  // ir_ws -> se_ws hand-off of the expanded map as plain fp32 rows instead of split pairs (env M2S_IRWS_F32=0: split)
-  bool irws_f32_ = true;
-  int sews_min_cus_ = 1;
-  bool stem_fused_ = true;  // bf16: stem + blocks.0 in one kernel (env M2S_STEM_FUSED=0 disables)
-  bool f8_er_ = true;            // fp8: EdgeResidual blocks.1.1/.2 on e4m3 (env M2S_F8_ER=0: bf16 er_fused)
-  bool se_y8_ = true;            // fp8: the SE GEMM also stores the next expand's e4m3 operand (env M2S_SE_Y8=0:
-                                 // launch_rows_e4m3 converts it; the same bytes, test_fp8_se_y8_e4m3_handoff_is_exact)
-  bool f8_er2_ = true;           // fp8: EdgeResidual blocks.2.1/.2 on e4m3 (er8w_fused; env M2S_F8_ER2=0: bf16 er2_fused)
-  bool er8_x8_ = true;           // ... their input as e4m3 bytes from the producer (env M2S_ER8_X8=0: converted
-                                 // in er8_fused; the same bytes, test_fp8_er8_e4m3_handoff_is_exact)
-  bool f8_expand_ = true;        // fp8: the stride-1 IR expand on e4m3 (env M2S_F8_EXPAND=0: bf16 expand)
-  bool f8_s2_ = true;            // fp8: the stride-2 IR blocks (blocks.3.0 ir_s2band, blocks.5.0 ir_pwdw_s2) with e4m3
-                                 // depthwise output + e4m3 SE GEMM (env M2S_F8_S2=0: bf16)
-  bool se_fused_ = true;    // bf16: SE excitation in one kernel (env M2S_SE_FUSED=0: two GEMMs)
-  bool er_fused_ = true;    // bf16: EdgeResidual 32->128->32 in one kernel (env M2S_ER_FUSED=0 disables)
-  bool se_sp_ = false;      // split: SE-gated conv_pwl on gemm128.hip (env M2S_SE_SP=1; default conv_gemm's in-LDS
-                            // scaling: the two measured equal, 7.85 vs 7.88 ms per step, profiles/r03o_se_sp_ab.txt)
-  bool se_ws_ = true;      // split: SE-gated conv_pwl on the warp-specialised flag ring (se_ws.hip; env M2S_SE_WS=0:
-                            // conv_gemm's barrier ring; 8.03 -> 7.17 ms per step, gpurun_out s4a)
-  bool er_mrg_ = true;      // split EdgeResidual blocks.1: merged W_hi / W_lo ring stages (env M2S_ER_MRG=0: one per
-                            // slot; 2088 vs 2164 us per launch, gpurun_out r03er)
-  bool ir_s2band_ = true;   // blocks.3.0: fused banded conv_pw + stride-2 depthwise (env M2S_IR_S2BAND=0: unfused)
-  bool er_s2_fused_ = true;  // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the 128-channel map stays in LDS
-                             // (conv_gemm.hip EP = 1; env M2S_ER_S2_FUSED=0: the two conv_gemm launches)
-  bool sews_rev_ = true;     // se_ws walks its tiles newest-first, behind ir_ws's forward walk: the end of the expanded
-                             // map is still in the Infinity Cache (env M2S_SEWS_REV=0: forward; bit-identical results;
-                             // 6.83 -> 6.58 ms of se_ws per 1920 frames)
-  bool lstm_persistent_ = true;  // one-launch BiLSTM recurrence (env M2S_LSTM_PERSISTENT=0: a launch per step)
-  bool lstm_mid_ = true;         // 4 < B <= 16: granule-exchange recurrence (env M2S_LSTM_MID=0: counter barrier)
-  bool lstm_x3_ = true;          // B > 4, non-fp32 engines: split-bf16 MFMA recurrence (env M2S_LSTM_X3=0: lstm_mid / f32)
-  bool lstm_x3g_ = true;   // ... and for 5..16 sequences its granule hand-off form (env M2S_LSTM_X3G=0: lstm_x3)
-  // (the M2S_* switches are read once, when the engine is created: A/B tests of fused vs unfused)
 
   size_t workspace_bytes(int B, int T, int H, int W) const;
   void forward(const float* frames, int B, int T, int H, int W, float* mel_norm, Workspace& ws, hipStream_t s);
@@ -428,6 +388,7 @@ class Acoustic {
   void effnet_dims(int H, int W, size_t* io_elems, size_t* mid_elems, size_t* se_elems) const;
 
   int dtype_, device_, n_mels_, hidden_;
+  const Switches sw_;  // the M2S_* switches as the environment held them when the engine was created (switches.hpp)
   Arena arena_;
   AcousticPlan p_;
   unsigned* err_host_ = nullptr;  // pinned, host-mapped: set by lstm_persistent_kernel on a barrier timeout
@@ -471,23 +432,6 @@ class Vocoder {
   // (m2s_vocoder_set_chunk_cone, for tests and timing); off: every stage runs on the full spans.  Same contract
   bool chunk_cone_ = true;
   size_t act_elems(int B, int T) const;
-  bool mrf_fused_ = true;  // bf16: fused ResBlock1 kernel for C in {32, 64} (env M2S_MRF_FUSED=0 disables)
-  bool mrf_halo_ = true;   // split: C = 64 MRF convs with once-staged input rows (env M2S_MRF_HALO=0: conv_gemm)
-  // split: each (c1, c2) pair of the C = 64 stage in one launch, the tensor between the convs kept in LDS
-  // (conv1d_halo_pair_kernel; env M2S_MRF_PAIR=0: one launch per conv; also off with M2S_MRF_HALO=0 / M2S_MRF_BATCH=0)
-  bool mrf_pair_ = true;
-  // ... and the last pair of every resblock chained in one launch with the MRF sum in registers, where the pass
-  // fills the chip (env M2S_MRF_CHAIN=0: one launch per resblock, the sum read and written in memory)
-  bool mrf_chain_ = true;
-  // ... and the C = 128 stage on the same kernel (8 waves, one workgroup per CU) instead of conv_gemm's batches
-  // (env M2S_MRF_PAIR128=1; packs that stage's weights a second time, in fragment order)
-  bool mrf_pair128_ = false;
-  // fp8: the C = 64 / 32 MRF convs on e4m3 (conv1d_f8, 128 / C taps a K step; env M2S_F8_MRF64=1 / M2S_F8_MRF32=1).
-  // Off: the fused bf16 ResBlock1 keeps a resblock's intermediates on chip and is faster at configs[4] (8 x 1000
-  // frames, same box, gpurun_out/f8s2: fp8 step 74.8 ms with both fused, 79.7 with C = 64 on e4m3, 85.1 with both)
-  bool f8_mrf64_ = false;
-  bool f8_mrf32_ = false;
-  bool mrf_batch_ = true;  // split: resblocks of a conv_gemm MRF stage batched per launch (env M2S_MRF_BATCH=0 disables)
 
  private:
   // tab (ragged calls, with a clip shorter than Tn): the device clip table; the input S of every upsampler and of
@@ -538,6 +482,7 @@ class Vocoder {
   void mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out, hipStream_t s);
   m2s_hifigan_h h_;
   int dtype_, device_;
+  const Switches sw_;  // as Acoustic::sw_
   Arena arena_;
   VocoderPlan p_;
   RaggedTable rtab_;

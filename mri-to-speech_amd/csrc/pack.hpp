@@ -256,10 +256,10 @@ inline void conv_cost(const ConvArgs& a, const PConv& p, double* flops_out, doub
 }
 
 template <typename T>
-inline void run_conv(const ConvArgs& a, const PConv& p, hipStream_t s) {
+inline void run_conv(const ConvArgs& a, const PConv& p, const ConvTune& tune, hipStream_t s) {
   double flops, bytes;
   conv_cost<T>(a, p, &flops, &bytes);
-  launch_conv<T>(a, s, flops, bytes);
+  launch_conv<T>(a, tune, s, flops, bytes);
 }
 
 // TF "SAME": out = ceil(in / s), total pad = max((out - 1) * s + k - in, 0), top/left = total / 2

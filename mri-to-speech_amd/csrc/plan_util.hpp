@@ -1,23 +1,13 @@
 // Small helpers shared by the execution-plan files (acoustic_cnn.cpp, acoustic_rnn.cpp, vocoder.cpp, model.cpp):
-// the M2S_* switch readers, the per-instantiation engine traits and the ConvArgs builders.  Internal: model.hpp
-// stays the header everything else includes.
+// the per-instantiation engine traits and the ConvArgs builders.  (The M2S_* switches: switches.hpp.)  Internal:
+// model.hpp stays the header everything else includes.
 #pragma once
 
-#include <cstdlib>
-#include <cstring>
 #include <type_traits>
 
 #include "pack.hpp"
 
 namespace m2s {
-
-// The M2S_* switches: read once, when an engine is created; "0" turns a flag off, anything else on.
-inline void env_flag(const char* name, bool& v) {
-  if (const char* e = std::getenv(name)) v = std::strcmp(e, "0") != 0;
-}
-inline void env_int(const char* name, int& v) {
-  if (const char* e = std::getenv(name)) v = std::atoi(e);
-}
 
 // Which engine a plan template runs for, from its activation type T alone.  dispatch_act (model.hpp) instantiates
 // bf16_t only for the bf16 and fp8 engines, sp_t only for bf16x3 and float only for fp32, so no plan needs a dtype_

@@ -1,5 +1,6 @@
 #include "prof.hpp"
 
+#include <cstdlib>
 #include <cstring>
 #include <map>
 #include <mutex>
@@ -46,6 +47,11 @@ Prof& P() {
 }  // namespace
 
 bool prof_on() { return P().on; }
+
+bool prof_detail() {
+  static const bool detail = std::getenv("M2S_PROF_DETAIL") != nullptr;
+  return detail;
+}
 
 StageTag::StageTag(const std::string& stage) : prev_(g_stage) { g_stage = stage; }
 StageTag::~StageTag() { g_stage = prev_; }

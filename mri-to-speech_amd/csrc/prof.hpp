@@ -8,6 +8,9 @@
 namespace m2s {
 
 bool prof_on();
+// M2S_PROF_DETAIL set: launchers record per-layer names (conv_gemm: K x N and rows per launch) instead of the kernel
+// symbol.  Process-wide like the profiler itself, read on first use: not an engine switch (switches.hpp).
+bool prof_detail();
 // Brackets one kernel launch with HIP events on `s` when profiling is enabled.
 // Stage label (e.g. "cnn", "bilstm", "mrf_c128") of the launches recorded while a StageTag lives on this
 // thread; nested tags restore the outer one.  bench.py's roofline.stages and tools/evidence.py's per-stage PMC

@@ -468,7 +468,7 @@ __global__ void __launch_bounds__(64 * (WM * WN + NL), 1) se_ws_kernel(const SeW
 }
 
 template <int WM, int WN, int NT, int NL, int NS, int IF, bool F8 = false, bool XF = false, bool REV = false>
-void launch_cfg(SeWsArgs& a, hipStream_t s, double flops, double bytes) {
+void launch_cfg(SeWsArgs& a, hipStream_t s, double flops, double bytes, bool half) {
   static_assert(IF <= 3, "tail waits");
   constexpr int BM = 64 * WM, BN = 16 * NT * WN;
   const void* fn = reinterpret_cast<const void*>(&se_ws_kernel<WM, WN, NT, NL, NS, IF, REV, F8, XF>);
@@ -480,15 +480,14 @@ void launch_cfg(SeWsArgs& a, hipStream_t s, double flops, double bytes) {
   M2S_CHECK(BM % a.P == 0 || a.P % BM == 0, "se_ws: tile rows vs image size");
   M2S_CHECK(a.cs_out <= BN, "se_ws: one n tile covers the outputs");
   M2S_CHECK((F8 ? a.kp / 128 : a.cs_in / 32) >= NS, "se_ws: K steps per tile >= ring slots (gate rows are double-buffered per tile)");
-  // tail balancing (M2S_SEWS_HALF=1, off by default): when the last round's tiles would fill at most half the
-  // workgroups, they run as twice as many half tiles (BM / 2 rows, still whole 64-row consumer blocks and whole images
+  // tail balancing (half: the caller's Switches::sews_half, M2S_SEWS_HALF=1 when its engine was created; off by
+  // default): when the last round's tiles would fill at most half the workgroups, they run as twice as many half tiles (BM / 2 rows, still whole 64-row consumer blocks and whole images
   // or halves of one) spread over them.  Parity-green, but a half tile costs about a full one here (the weight rows,
   // the ring and the flag protocol stay; half the consumers idle): same-box CNN 31.36 / 31.68 ms off, 31.54 / 31.51 on
   // (gpurun_out/r06i/ab.txt), unlike ir_ws's slice-range split
   const int tiles = ceil_div(a.M, BM), G = std::min(tiles, device_cus());
   const int full = tiles / G * G, rem = tiles - full;
-  const bool halve = rem > 0 && 2 * rem <= G && (BM / 2) % 64 == 0 && ((BM / 2) % a.P == 0 || a.P % (BM / 2) == 0) &&
-                     getenv("M2S_SEWS_HALF") && atoi(getenv("M2S_SEWS_HALF")) == 1;
+  const bool halve = rem > 0 && 2 * rem <= G && (BM / 2) % 64 == 0 && ((BM / 2) % a.P == 0 || a.P % (BM / 2) == 0) && half;
   a.full_tiles = halve ? full : tiles;
   a.n_tiles_m = halve ? full + 2 * rem : tiles;
   const dim3 grid(G);
@@ -513,7 +512,7 @@ bool se_ws_supported(int P, int cs_in, int cs_out) {
 
 void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_pad, const float* bias, const void* gate,
                   const void* res, void* y, int cs_out, hipStream_t s, double flops, double bytes, AsyncReport rep,
-                  bool x_f32, bool rev) {
+                  bool x_f32, bool rev, bool half, int cfg) {
   M2S_CHECK(se_ws_supported(P, cs_in, cs_out) && M % P == 0 && cs_out % 4 == 0, "se_ws: unsupported shape");
   M2S_CHECK(x && w && bias && gate && y && y != res && y != x, "se_ws: operand pointers");
   M2S_CHECK((double)M * cs_in * 4 < 2147483647.0 * 2, "se_ws: input too large");
@@ -532,43 +531,39 @@ void launch_se_ws(const void* x, int M, int P, int cs_in, const void* w, int n_p
   a.cs_out = cs_out;
   a.spin_max = rep.spin_max;
   a.err = rep.err;
-  // tile / ring variants (M2S_SE_WS_CFG, A/B only; 0 = the default)
-  static const int cfg = [] {
-    const char* e = std::getenv("M2S_SE_WS_CFG");
-    return e ? std::atoi(e) : 0;
-  }();
+  // cfg: tile / ring variants (the caller's Switches::se_ws_cfg, M2S_SE_WS_CFG; A/B only; 0 = the default)
   if (x_f32) {  // fp32 activations (ir_ws fm32): the default tiles only
     if (cs_out <= 128) {
       M2S_CHECK(n_pad >= 128, "se_ws: weight rows");
-      if (rev) return launch_cfg<4, 1, 8, 4, 3, 2, false, true, true>(a, s, flops, bytes);
-      return launch_cfg<4, 1, 8, 4, 3, 2, false, true>(a, s, flops, bytes);
+      if (rev) return launch_cfg<4, 1, 8, 4, 3, 2, false, true, true>(a, s, flops, bytes, half);
+      return launch_cfg<4, 1, 8, 4, 3, 2, false, true>(a, s, flops, bytes, half);
     }
     M2S_CHECK(n_pad >= 224, "se_ws: weight rows");
-    if (rev) return launch_cfg<2, 2, 7, 4, 3, 2, false, true, true>(a, s, flops, bytes);
-    return launch_cfg<2, 2, 7, 4, 3, 2, false, true>(a, s, flops, bytes);
+    if (rev) return launch_cfg<2, 2, 7, 4, 3, 2, false, true, true>(a, s, flops, bytes, half);
+    return launch_cfg<2, 2, 7, 4, 3, 2, false, true>(a, s, flops, bytes, half);
   }
   if (rev && cfg == 0) {  // the default tiles, walked newest-first
     M2S_CHECK(n_pad >= (cs_out <= 128 ? 128 : 224), "se_ws: weight rows");
-    if (cs_out <= 128) return launch_cfg<4, 1, 8, 4, 3, 2, false, false, true>(a, s, flops, bytes);
-    return launch_cfg<2, 2, 7, 4, 3, 2, false, false, true>(a, s, flops, bytes);
+    if (cs_out <= 128) return launch_cfg<4, 1, 8, 4, 3, 2, false, false, true>(a, s, flops, bytes, half);
+    return launch_cfg<2, 2, 7, 4, 3, 2, false, false, true>(a, s, flops, bytes, half);
   }
   if (cs_out <= 128) {
     M2S_CHECK(n_pad >= 128, "se_ws: weight rows");
     switch (cfg) {
-      case 1: return launch_cfg<4, 2, 4, 2, 3, 1>(a, s, flops, bytes);  // 256 x 128, 3 slots, 1 step in flight
-      case 2: return launch_cfg<2, 2, 4, 4, 4, 2>(a, s, flops, bytes);  // 128 x 128, 4 slots, 2 in flight
-      case 3: return launch_cfg<2, 2, 4, 4, 4, 1>(a, s, flops, bytes);  // 128 x 128, 4 slots, 1 in flight
-      case 4: return launch_cfg<4, 2, 4, 4, 3, 2>(a, s, flops, bytes);  // 256 x 128, 8 consumers 64 x 64 each
+      case 1: return launch_cfg<4, 2, 4, 2, 3, 1>(a, s, flops, bytes, half);  // 256 x 128, 3 slots, 1 step in flight
+      case 2: return launch_cfg<2, 2, 4, 4, 4, 2>(a, s, flops, bytes, half);  // 128 x 128, 4 slots, 2 in flight
+      case 3: return launch_cfg<2, 2, 4, 4, 4, 1>(a, s, flops, bytes, half);  // 128 x 128, 4 slots, 1 in flight
+      case 4: return launch_cfg<4, 2, 4, 4, 3, 2>(a, s, flops, bytes, half);  // 256 x 128, 8 consumers 64 x 64 each
       // 256 x 128 (one 16x16 image), 3 slots, 4 consumers of 64 rows x all 128 columns: each activation
       // fragment is gated and re-split by one wave instead of two (the 8-consumer 64 x 64 form above):
       // 408 -> 389 us per launch, same-box per-process A/B (profiles/r04_se_ws_wn1_kstats.txt)
-      default: return launch_cfg<4, 1, 8, 4, 3, 2>(a, s, flops, bytes);
+      default: return launch_cfg<4, 1, 8, 4, 3, 2>(a, s, flops, bytes, half);
     }
   } else {
     M2S_CHECK(n_pad >= 224, "se_ws: weight rows");
     switch (cfg) {
-      case 1: return launch_cfg<2, 2, 7, 2, 3, 1>(a, s, flops, bytes);  // 128 x 224 (two 8x8 images)
-      default: return launch_cfg<2, 2, 7, 4, 3, 2>(a, s, flops, bytes);
+      case 1: return launch_cfg<2, 2, 7, 2, 3, 1>(a, s, flops, bytes, half);  // 128 x 224 (two 8x8 images)
+      default: return launch_cfg<2, 2, 7, 4, 3, 2>(a, s, flops, bytes, half);
     }
   }
 }
@@ -579,7 +574,7 @@ bool se_ws_f8_supported(int P, int cs_in, int cs_out) {
 
 void launch_se_ws_f8(const void* x8, int M, int P, int cs_in, const void* w8, int kp, int n_pad, const float* wscale,
                      const float* bias, const void* gate, const void* res, void* y, int cs_out, hipStream_t s, double flops,
-                     double bytes, void* y8, int ld8, AsyncReport rep) {
+                     double bytes, void* y8, int ld8, AsyncReport rep, bool half) {
   M2S_CHECK(se_ws_f8_supported(P, cs_in, cs_out) && kp % 128 == 0 && kp >= cs_in && M % P == 0 && cs_out % 4 == 0,
             "se_ws_f8: unsupported shape");
   M2S_CHECK(!y8 || (ld8 >= cs_out && ld8 % 16 == 0 && y8 != x8), "se_ws_f8: e4m3 output rows");
@@ -608,10 +603,10 @@ void launch_se_ws_f8(const void* x8, int M, int P, int cs_in, const void* w8, in
     M2S_CHECK(n_pad >= 128, "se_ws_f8: weight rows");
     // 128 x 128 (half a 16x16 image), 4 consumers + 4 loaders, 4 slots: the 8-consumer 256-row tile of the
     // split form spills here (32 fp32 gates a lane next to e4m3 fragments)
-    launch_cfg<2, 2, 4, 4, 4, 2, true>(a, s, flops, bytes);
+    launch_cfg<2, 2, 4, 4, 4, 2, true>(a, s, flops, bytes, half);
   } else {
     M2S_CHECK(n_pad >= 224, "se_ws_f8: weight rows");
-    launch_cfg<2, 2, 7, 4, 3, 2, true>(a, s, flops, bytes);  // 128 x 224 (two 8x8 images)
+    launch_cfg<2, 2, 7, 4, 3, 2, true>(a, s, flops, bytes, half);  // 128 x 224 (two 8x8 images)
   }
 }
 

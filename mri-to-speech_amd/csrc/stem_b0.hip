@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(256, SP ? 2 : 3) stem_b0_kernel(const StemB0Ar
 
 void launch_stem_b0(const float* frames, int N, int H, int W, int OH, int OW, int pad_t, int pad_l, const float* w9,
                     const float* b9, const void* w0, const float* b0, int kp0, const void* w1, const float* b1,
-                    int kp1, void* y, bool split, double flops, double bytes, hipStream_t s) {
+                    int kp1, void* y, bool split, double flops, double bytes, hipStream_t s, int forced_parts) {
   M2S_CHECK(kp0 == 288 && kp1 == 160 && N > 0 && OH > 0 && OW > 0, "stem_b0: unsupported shape");
   constexpr int TH = 16;
   StemB0Args a;
@@ -494,9 +494,9 @@ void launch_stem_b0(const float* frames, int N, int H, int W, int OH, int OW, in
   const int nstrip = N * a.tiles_x;  // a workgroup walks whole strips (image, tile column) top to bottom
   const int per_cu = split ? 2 : 3;
   // small batches: strips cut into tile-row ranges so the units fill the workgroup slots (a cut costs one more
-  // first tile, ~1.2 tiles of work).  M2S_STEM_PARTS=n forces n (tests, A/B).
-  const char* fp = getenv("M2S_STEM_PARTS");
-  int parts = fp ? atoi(fp) : (cus * per_cu) / std::max(1, nstrip);
+  // first tile, ~1.2 tiles of work).  forced_parts = n > 0 forces n (tests, A/B: the caller's Switches::stem_parts,
+  // M2S_STEM_PARTS as the engine read it when it was created).
+  int parts = forced_parts > 0 ? forced_parts : (cus * per_cu) / std::max(1, nstrip);
   parts = std::max(1, std::min(parts, a.tiles_y));
   a.tpp = ceil_div(a.tiles_y, parts);
   a.parts = ceil_div(a.tiles_y, a.tpp);  // (no empty parts)

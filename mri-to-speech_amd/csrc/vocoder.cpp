@@ -2,8 +2,6 @@
 // layouts, and the ragged and chunk calls.  The weights are packed by pack_vocoder.cpp (host code); the constructor
 // here reads the switches, packs, uploads the arena and resolves device pointers.
 #include <algorithm>
-#include <initializer_list>
-#include <utility>
 
 #include "plan_util.hpp"
 #include "prof.hpp"
@@ -11,13 +9,8 @@
 namespace m2s {
 
 Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int device)
-    : h_(h), dtype_(dtype), device_(device) {
-  for (auto [name, v] : std::initializer_list<std::pair<const char*, bool*>>{
-           {"M2S_MRF_FUSED", &mrf_fused_}, {"M2S_MRF_BATCH", &mrf_batch_}, {"M2S_MRF_HALO", &mrf_halo_},
-           {"M2S_F8_MRF64", &f8_mrf64_},   {"M2S_F8_MRF32", &f8_mrf32_},   {"M2S_MRF_PAIR", &mrf_pair_},
-           {"M2S_MRF_CHAIN", &mrf_chain_}, {"M2S_MRF_PAIR128", &mrf_pair128_}})
-    env_flag(name, *v);
-  pack_vocoder(sd, h, dtype, f8_mrf64_, f8_mrf32_, arena_, p_, mrf_pair_ && mrf_pair128_);
+    : h_(h), dtype_(dtype), device_(device), sw_(Switches::from_env()) {
+  pack_vocoder(sd, h, dtype, sw_.f8_mrf64, sw_.f8_mrf32, arena_, p_, sw_.mrf_pair && sw_.mrf_pair128);
   arena_.upload(device);
   p_.pre.resolve(arena_);
   for (auto& u : p_.ups) u.resolve(arena_);
@@ -270,12 +263,12 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
   for (int j = 0; j < nk; ++j) ord[j] = j;
   std::sort(ord, ord + nk, [&](int x, int y) { return p_.rbs[i * nk + x].c1[0].kp > p_.rbs[i * nk + y].c1[0].kp; });
   auto a_in = [&](int j, int p) -> const T* { return p == 0 ? X : Bt[j][1 + ((p - 1) & 1)]; };  // lrelu(x) of pair p
-  bool halo = mrf_halo_;  // input rows staged once per tile (conv1d_halo.hip) where the stage has the weights for it
+  bool halo = sw_.mrf_halo;  // input rows staged once per tile (conv1d_halo.hip) where the stage has the weights for it
   for (int j = 0; j < nk; ++j) halo = halo && !p_.rbs[i * nk + j].h1.empty();
   // each (c1, c2) pair in one launch (conv1d_halo_pair_kernel) where every pair of the stage is within its reach;
   // a stage with one that is not runs as a whole on the launches below
   const int C = p_.ups[i].cout;
-  bool pair = halo && mrf_pair_ && kSplit<T> && (C == 64 || mrf_pair128_);
+  bool pair = halo && sw_.mrf_pair && kSplit<T> && (C == 64 || sw_.mrf_pair128);
   for (int j = 0; j < nk && pair; ++j)
     for (int d : p_.rbs[i * nk + j].dil) pair = pair && conv1d_halo_pair_supported(C, chan_stride(C), p_.rbs[i * nk + j].k, d);
   for (int j = 0; j < nk; ++j)  // C = 128 has the fragments for the pair kernel only
@@ -310,7 +303,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
     // the last pairs in resblock order: xs = sum_j resblock_j(x); S = xs / num_kernels, lrelu'd for an upsampler
     HaloPair hp[CONV_BATCH];
     double fl = 0.0, by = 0.0;
-    const bool chain = mrf_chain_ && conv1d_halo_pair_fills(C, B, L);
+    const bool chain = sw_.mrf_chain && conv1d_halo_pair_fills(C, B, L);
     for (int j = 0; j < nk; ++j) {
       double f = 0.0, b = 0.0;
       hp[j] = make(j, np - 1, &f, &b);
@@ -328,7 +321,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
     if (halo)
       launch_conv1d_halo_sp(cs, n, s, fl, by);
     else
-      launch_conv_gemm_batch(cs, n, s, fl, by);
+      launch_conv_gemm_batch(cs, n, sw_.conv, s, fl, by);
   };
   for (int p = 0; p < np; ++p) {
     ConvArgs cs[CONV_BATCH];
@@ -371,7 +364,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
           conv_cost<T>(c, rb.c2[p], &f, &b);
           launch_conv1d_halo_sp(&c, 1, s, f, b);
         } else {
-          run_conv<T>(c, rb.c2[p], s);
+          run_conv<T>(c, rb.c2[p], sw_.conv, s);
         }
       }
     }
@@ -417,8 +410,8 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
   };
   auto is_batched = [&](int i) {  // stage i's MRF runs as batched split launches (mrf_stage_batched)
     const PConv& up = p_.ups[i];
-    const bool fused = kNotF32<T> && mrf_fused_ && !p_.rbs[i * nk].f1.empty();
-    bool b = SPL && mrf_batch_ && !fused && h_.resblock == 1 && nk <= CONV_BATCH && up.cout >= 32 && up.cout % 32 == 0;
+    const bool fused = kNotF32<T> && sw_.mrf_fused && !p_.rbs[i * nk].f1.empty();
+    bool b = SPL && sw_.mrf_batch && !fused && h_.resblock == 1 && nk <= CONV_BATCH && up.cout >= 32 && up.cout % 32 == 0;
     for (int j = 0; j < nk; ++j) b = b && p_.rbs[i * nk + j].dil.size() == p_.rbs[i * nk].dil.size();
     return b;
   };
@@ -430,7 +423,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     StageTag tag("voc_pre");
     ConvArgs a = conv1d_args(p_.pre, mel_nlc, S, B, L);
     if (s_act) lrelu_out(a);
-    run_conv<T>(a, p_.pre, s);
+    run_conv<T>(a, p_.pre, sw_.conv, s);
   }
   for (int i = 0; i < h_.n_up; ++i) {
     const PConv& up = p_.ups[i];
@@ -446,7 +439,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       a.in_slope = 0.1f;
     }
     if (batched) lrelu_out(a);  // X = lrelu(upsampled x): the MRF convs read it as is (mrf_stage_batched)
-    run_conv<T>(a, up, s);
+    run_conv<T>(a, up, sw_.conv, s);
     L *= up.ct_u;
     StageTag mrf("mrf_c" + std::to_string(up.cout));  // the stage's MRF (ResBlocks + sum), models.py:119-125
     if (batched) {
@@ -506,7 +499,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       const T* hcur = X;
       const int np = (int)rb.dil.size();
       const int accum = mrf_accum(j, nk);
-      if (kNotF32<T> && mrf_fused_ && !rb.f1.empty()) {
+      if (kNotF32<T> && sw_.mrf_fused && !rb.f1.empty()) {
         // one launch for the whole resblock + MRF sum (mrf_fused.hip)
         const bf16_t* w1[8];
         const bf16_t* w2[8];
@@ -537,7 +530,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
         if (h_.resblock == 1) {  // xt = c2(lrelu(c1(lrelu(x)))) ; x = xt + x
           c.y = T1;
           lrelu_out(c);
-          run_conv<T>(c, rb.c1[p], s);
+          run_conv<T>(c, rb.c1[p], sw_.conv, s);
           c = conv1d_args(rb.c2[p], T1, out, B, L);
         }
         c.res = hcur;
@@ -545,7 +538,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
           c.accum = accum;
           c.accum_div = (float)nk;
         }
-        run_conv<T>(c, h_.resblock == 1 ? rb.c2[p] : rb.c1[p], s);
+        run_conv<T>(c, h_.resblock == 1 ? rb.c2[p] : rb.c1[p], sw_.conv, s);
         hcur = out;
       }
     }

@@ -185,3 +185,28 @@ def test_config1_split_k_matches_unsplit(rt, weights, monkeypatch):
     monkeypatch.setenv("M2S_KSPLIT", "1")
     b = rt.AcousticEngine(ac, dtype="bf16", device=DEV).forward(x).cpu().numpy()
     assert np.isfinite(a).all() and _cos(a, b) >= 0.9999 and np.abs(a - b).max() <= 2e-2
+
+
+def test_engine_keeps_the_switches_it_was_created_under(rt, weights, monkeypatch):
+    """An engine reads the M2S_* switches once, when it is created (csrc/switches.hpp): at configs[1]'s shape (8 x 4,
+    bf16) an engine created under M2S_KSPLIT=1 never splits K and one created without it does, whatever the
+    environment holds when they run, and each computes, bit for bit, what an engine created and run under its own
+    setting computes."""
+    ac = weights[0]
+    x = torch.from_numpy(synth.synth_frames(8, 4, seed=301)).to(DEV)
+
+    def ksum(names):
+        return [n for n in names if n.startswith("conv_gemm_ksum_kernel")]
+
+    monkeypatch.setenv("M2S_KSPLIT", "1")
+    u = rt.AcousticEngine(ac, dtype="bf16", device=DEV)
+    monkeypatch.delenv("M2S_KSPLIT")
+    s = rt.AcousticEngine(ac, dtype="bf16", device=DEV)
+    out_u, names_u = _launches(lambda: u.forward(x).cpu().numpy())
+    out_s, names_s = _launches(lambda: s.forward(x).cpu().numpy())
+    assert not ksum(names_u) and ksum(names_s)
+    monkeypatch.setenv("M2S_KSPLIT", "1")
+    out_s2, names_s2 = _launches(lambda: s.forward(x).cpu().numpy())
+    assert names_s2 == names_s and np.array_equal(out_s2, out_s)
+    ref_u = rt.AcousticEngine(ac, dtype="bf16", device=DEV).forward(x).cpu().numpy()  # created and run under 1
+    assert np.isfinite(out_u).all() and np.array_equal(out_u, ref_u)

@@ -1,4 +1,5 @@
-"""Same-process A/B of a kernel-selection switch read at engine construction (M2S_STEM_WS, M2S_SE_WS, ...):
+"""Same-process A/B of an M2S_* switch (csrc/switches.hpp: every one is read when an engine is created, so one engine
+is created per value, after the variable is set, and keeps it whatever the environment holds later):
 usage: python tools/ab_env.py VAR [probe_blocks] [dtype ...].  Times AcousticEngine.probe(x, probe_blocks)
 (default 2: stem + blocks.0) and the whole CNN over 1920 frames with VAR=1 and VAR=0, alternating.  GPU only."""
 import os
@@ -37,6 +38,5 @@ for dt in dtypes:
         engs[v] = rt.AcousticEngine(st, dtype=dt, device=dev)
     for rnd in range(2):
         for v, e in engs.items():
-            os.environ[var] = v  # (switches read per launch, e.g. M2S_IRWS_PARTS, take the engine's value here too)
             print(f"{var}={v} {dt:7s} probe({nb}) {timed(lambda: e.probe(x, nb)):7.3f} ms  cnn {timed(lambda: e.effnet(x)):7.3f} ms",
                   flush=True)

@@ -1,7 +1,7 @@
-"""Same-process A/B of launch-time switches on the reference CLI's small shapes: configs[2] (1 clip x 30 frames,
+"""Same-process A/B of M2S_* switches on the reference CLI's small shapes: configs[2] (1 clip x 30 frames,
 bf16x3 pipeline_forward) and configs[1] (8 x 4 frames, bf16 acoustic forward), GPU time per call by HIP events,
-settings alternated over rounds.  Switches read per launch (M2S_KSPLIT, M2S_KSPLIT_MAX, M2S_KSPLIT_MINST) take
-effect at once; engine-construction switches need fresh engines (built per setting here).
+settings alternated over rounds.  Every switch (M2S_KSPLIT, M2S_KSPLIT_MAX, M2S_KSPLIT_MINST among them) is read
+when an engine is created (csrc/switches.hpp) and kept by it, so the engines are built per setting here.
 usage: python tools/ab_small.py "M2S_KSPLIT_MAX=4" "M2S_KSPLIT_MAX=8" ...   ("" = defaults).  GPU only."""
 import os
 import sys

@@ -135,7 +135,8 @@ CASES = (
     # ---- acoustic
     [Case(f"ac_forward_1x3_{d}", {}, _ac("forward", d, frames=(1, 3))) for d in DTYPES]
     + [Case("ac_forward_1x3_bf16x3_persistent", PERSISTENT, _ac("forward", "bf16x3", frames=(1, 3))),
-       # ... and no split K (read at every launch, so set through the call): blocks.2.0 on launch_conv_gemm_er
+       # ... and no split K (read, like every switch, when the case's engine is created): blocks.2.0 on
+       # launch_conv_gemm_er
        Case("ac_forward_1x3_bf16x3_persistent_ksplit1", dict(PERSISTENT, M2S_KSPLIT="1"),
             _ac("forward", "bf16x3", frames=(1, 3)))]
     + [Case(f"ac_forward_1x9_chunk4_{d}", {}, _ac("forward", d, frames=(1, 9), chunk=4)) for d in ("bf16x3", "fp32")]
