@@ -24,7 +24,7 @@ Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int d
   M2S_HIP(hipHostMalloc(reinterpret_cast<void**>(&err_host_), sizeof(unsigned), hipHostMallocMapped | hipHostMallocCoherent));
   *err_host_ = 0;
   M2S_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&err_dev_), err_host_, 0));
-  M2S_HIP(hipMalloc(&gsync_, std::max(lstm_small_sync_bytes(), lstm_x3g_sync_bytes())));
+  M2S_HIP(hipMalloc(&gsync_, lstm_sync_bytes(true)));
 }
 
 Acoustic::~Acoustic() {

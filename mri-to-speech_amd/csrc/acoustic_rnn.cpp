@@ -30,44 +30,23 @@ void Acoustic::head(const float* h, long rows, bool merged, float* mel_norm, hip
                   merged);
 }
 
-size_t Acoustic::lstm_sync_bytes() {
-  return std::max({lstm_persistent_sync_bytes(), lstm_small_sync_bytes(), lstm_mid_sync_bytes(), lstm_x3_sync_bytes(),
-                   lstm_x3g_sync_bytes()});
-}
-
 void Acoustic::lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps,
                                double rows, hipStream_t s) {
   const int H = hidden_;
   const float* whh = arena_.at<float>(p_.whh);
-  // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
-  const double bytes = 4.0 * 2 * 4 * H * H + 4.0 * rows * (8.0 * H + 2.0 * H);
-  const double f2 = 2.0 * 2 * 4.0 * H * H * seq_steps, f3 = 3.0 * 2 * 4.0 * H * H * seq_steps;
-  if (sw_.lstm_persistent && lstm_small_supported(B, H, sw_.lstm_small_b)) {
-    ProfScope ps("lstm_small_kernel", f2, bytes, s);
-    launch_lstm_small(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, sw_.lstm_small_b,
-                      &gsync_epoch_);
-  } else if (sw_.lstm_persistent && sw_.lstm_x3 && sw_.lstm_x3g && dtype_ != M2S_DT_F32 &&
-             lstm_x3g_supported(B, H)) {
-    // 5..16 sequences (configs[4]'s 8 clips a GPU): the granule hand-off (lstm_persistent.hip lstm_x3g_kernel)
-    ProfScope ps("lstm_x3g_kernel", f3, bytes, s);
-    launch_lstm_x3g(pre, whh, hs, B, T, H, gsync_, lstm_spin_max_, err_dev_, s, &gsync_epoch_);
-  } else if (sw_.lstm_persistent && sw_.lstm_x3 && dtype_ != M2S_DT_F32 && lstm_persistent_supported(H)) {
-    // split engines above the small-batch kernel: 4.1 / 5.2 / 9.9 us per step at B = 8 / 16 / 64 against
-    // lstm_mid's 7.2 / 11.9 and the f32 counter-barrier kernel's 24 (gpurun_out lstm2, lstm3_x3small)
-    ProfScope ps("lstm_x3_kernel", f3, bytes, s);
-    launch_lstm_x3(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else if (sw_.lstm_persistent && sw_.lstm_mid && lstm_mid_supported(B, H, sw_.lstm_small_b)) {
-    ProfScope ps("lstm_mid_kernel", f2, bytes, s);
-    launch_lstm_mid(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s, sw_.lstm_small_b, sw_.lstm_mid_ch);
-  } else if (sw_.lstm_persistent && lstm_persistent_supported(H)) {
-    ProfScope ps("lstm_persistent_kernel", f2, bytes, s);
-    launch_lstm_persistent(pre, whh, hs, B, T, H, sync, lstm_spin_max_, err_dev_, s);
-  } else {
+  const LstmPlan p = lstm_plan(
+      {sw_.lstm_persistent, sw_.lstm_mid, sw_.lstm_x3, sw_.lstm_x3g, sw_.lstm_small_b, sw_.lstm_mid_ch}, dtype_, B, H);
+  if (p.route == LstmRoute::Step) {
     for (int st = 0; st < T; ++st) {
-      ProfScope ps("lstm_step_kernel", 2.0 * 2 * (rows / T) * 4.0 * H * H, 4.0 * 2 * 4 * H * H, s);
+      ProfScope ps(p.name, 2.0 * 2 * (rows / T) * 4.0 * H * H, 4.0 * 2 * 4 * H * H, s);
       launch_lstm_step(pre, whh, hs, cst, B, T, H, st, s);
     }
+    return;
   }
+  // algorithmic bytes: W_hh of both directions once, gate pre-activations in, h out
+  ProfScope ps(p.name, p.terms * 2 * 4.0 * H * H * seq_steps, 4.0 * 2 * 4 * H * H + 4.0 * rows * (8.0 * H + 2.0 * H), s);
+  launch_lstm(p, pre, whh, hs, B, T, H, p.engine_sync ? gsync_ : sync, p.engine_sync ? &gsync_epoch_ : nullptr,
+              lstm_spin_max_, err_dev_, s);
 }
 
 Acoustic::LstmBufs Acoustic::lstm_bufs(Workspace& ws, int B, int T) const {
@@ -76,7 +55,7 @@ Acoustic::LstmBufs Acoustic::lstm_bufs(Workspace& ws, int B, int T) const {
   b.pre = ws.take<float>(BT * 8 * H);
   b.hs = ws.take<float>(2 * BT * H);
   b.cst = ws.take<float>((size_t)2 * B * H);
-  b.sync = ws.take<char>(lstm_sync_bytes());
+  b.sync = ws.take<char>(lstm_sync_bytes(false));
   return b;
 }
 

@@ -1,6 +1,7 @@
 // Launchers for the non-GEMM kernels of the hot path.
 #pragma once
 
+#include "lstm_route.hpp"
 #include "m2s_common.hpp"
 
 namespace m2s {
@@ -261,46 +262,20 @@ void launch_gap(const T* x, int N, int P, int C, int cs, float* feats, hipStream
 void launch_lstm_step(const float* pre, const float* whh, float* hs, float* cst, int B, int T, int H,
                       int step, hipStream_t s);
 
-// The same recurrence for all T steps in ONE persistent launch (lstm_persistent.hip): W_hh resident
-// in VGPRs across 160 workgroups, a release/acquire counter barrier per step.  H = 640 only.
-// `sync` = lstm_persistent_sync_bytes() of device memory (reset by the launcher).
-bool lstm_persistent_supported(int H);
-size_t lstm_persistent_sync_bytes();
-// `spin_max` bounds each barrier wait (polls with s_sleep 1); on a timeout the kernel stores 1 to
-// `err_host` (pinned, host-mapped) and writes NaN to the rest of the outputs.
-// Small batches (B <= 4): the same recurrence with h exchanged as data-tagged granules instead of a
-// counter barrier, VALU dot products (lstm_persistent.hip).  `sync` = lstm_small_sync_bytes().
-// small_cap: the batch limit, 4 or 8 (Switches::lstm_small_b: 8 selects the 8-sequence instantiation for B <= 8); the
-// check and the launch take the engine's one value
-bool lstm_small_supported(int B, int H, int small_cap);
-size_t lstm_small_sync_bytes();
-// epoch: the engine's epoch count for a sync buffer of its own (tags continue across calls, no memset; null = zero
-// the buffer every call)
-void launch_lstm_small(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                       unsigned* err_host, hipStream_t s, int small_cap, unsigned* epoch = nullptr);
+// The same recurrence for all T steps in ONE launch (lstm_persistent.hip; H = 640 only): W_hh resident in VGPRs
+// across co-resident workgroups that hand h_t to each other every step.  Five kernels, chosen by lstm_plan
+// (lstm_route.hpp): lstm_small (B <= 4 or 8: data-tagged fp32 granules, VALU dot products), lstm_x3g (split engines,
+// B <= 16: three bf16 MFMA terms over hi / lo operands, split granules), lstm_x3 (split engines above that: h
+// published split by write-through stores behind per-workgroup flags), lstm_mid (fp32, B <= 16: granules in chunks
+// whose sweep overlaps the previous chunk's dot products) and lstm_persistent (exact-f32 MFMA, counter barrier).
+// `sync`: lstm_sync_bytes(p.engine_sync) of device memory: the engine's own buffer where the plan says so (its
+// granule tags continue across calls from *epoch, no memset; a null epoch zeroes it every call), else the call's
+// workspace (reset by the launcher).  `spin_max` bounds each hand-off wait (polls with s_sleep 1); on a timeout the
+// kernel stores 1 to `err_host` (pinned, host-mapped) and writes NaN to the rest of the outputs.
 constexpr unsigned LSTM_SPIN_MAX = 1u << 24;
-// 4 < B <= 64: the same granule exchange with 512-thread workgroups, sequences in chunks of 16 whose
-// sweep overlaps the previous chunk's dot products (lstm_persistent.hip).  `sync` = lstm_mid_sync_bytes().
-// small_cap: as lstm_small_supported (lstm_mid starts above it); chunk: sequences per chunk, 4 / 8 / 16 forced
-// (Switches::lstm_mid_ch), else 4 up to B = 8 and 8 above
-bool lstm_mid_supported(int B, int H, int small_cap);
-size_t lstm_mid_sync_bytes();
-void launch_lstm_mid(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s, int small_cap, int chunk);
-void launch_lstm_persistent(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync,
-                            unsigned spin_max, unsigned* err_host, hipStream_t s);
-// B > 4 in split fp32 (the bf16x3 / bf16 / fp8 engines): three bf16 MFMA terms over W_hh and h_t split
-// hi / lo, h_t published split by write-through stores behind per-workgroup flags (no fences).
-// Split engines, 5..16 sequences: lstm_x3's arithmetic with the h_t hand-off as data-tagged granules (no flag round
-// trip, no store drain); `sync` = lstm_x3g_sync_bytes() (epoch-tagged, see launch_lstm_small).  (lstm_persistent.hip)
-bool lstm_x3g_supported(int B, int H);
-size_t lstm_x3g_sync_bytes();
-void launch_lstm_x3g(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s, unsigned* epoch = nullptr);
-// `sync` = lstm_x3_sync_bytes() (flags reset by the launcher).
-size_t lstm_x3_sync_bytes();
-void launch_lstm_x3(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                    unsigned* err_host, hipStream_t s);
+size_t lstm_sync_bytes(bool engine);
+void launch_lstm(const LstmPlan& p, const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync,
+                 unsigned* epoch, unsigned spin_max, unsigned* err_host, hipStream_t s);
 
 // Sliding-window BiLSTM (lstm_window.hip): S independent windows of at most W <= 16 steps, one launch per step,
 // no cross-workgroup communication.  H = 640 only.

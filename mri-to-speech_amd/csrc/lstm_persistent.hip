@@ -19,30 +19,27 @@
 // Spins are bounded: on timeout the workgroup sets the error word, poisons its remaining outputs
 // with NaN and leaves, so the grid always drains; the engine's pinned host flag (`err_host`) is set
 // too, and the C ABI reports it (m2s_acoustic_status; the next forward fails with M2S_E_INTERNAL).
-// Products are exact fp32 (MFMA f32); only the summation order differs from torch.  The gate
-// activations are the rcp-based sigmoid (v_exp + v_rcp, 1 ulp each) and tanh(x) = 2 sigmoid(2x) - 1
-// (absolute error ~1e-7): the cell update is on every step's critical path, and libm's expf + IEEE
-// divide and tanhf cost 7.51 against 7.18 us per recurrent step at 8 x 1000 (gpurun_out lstmfa0/1).
+// Products are exact fp32 (MFMA f32); only the summation order differs from torch.
+// The pieces the kernels of this file share (gate activations, W_hh fragment loads, the split MFMA chain, partial
+// sums, the cell update, the timeout exit) are in lstm_cell.hpp; the batch limits and the ladder that picks a kernel
+// for a call are in lstm_route.hpp, and launch_lstm at the end of this file launches what that ladder returned.
 #include <algorithm>
-#include <cstdlib>
+#include <string>
 
 #include "kernels.hpp"
+#include "lstm_cell.hpp"
 
 namespace m2s {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 
-__device__ __forceinline__ float lstm_sig(float x) { return sigmoidf_(x); }
-__device__ __forceinline__ float lstm_tanh(float x) { return 2.f * sigmoidf_(2.f * x) - 1.f; }
-
-constexpr int LP_H = 640;          // hidden size this kernel is built for
+constexpr int LP_H = LSTM_H;       // hidden size these kernels are built for
 constexpr int LP_U = 8;            // units per workgroup (32 gate rows = one MFMA M tile)
 constexpr int LP_KW = LP_H / 4;    // K slice per wave
 constexpr int LP_KH = LP_KW / 2;   // floats per lane per B tile (k half = lane / 32)
 constexpr int LP_BT = 2;           // 32-sequence B tiles per pass
-constexpr int LP_BMAX = 64;        // sequences per launch (c in LDS); larger batches: several launches
+constexpr int LP_BMAX = LSTM_LAUNCH_B;  // sequences per launch (c in LDS); larger batches: several launches
 
 struct LstmSync {
   unsigned arrive[2];  // per-direction monotonic arrival counters
@@ -70,15 +67,7 @@ __global__ void __launch_bounds__(256, 1) lstm_persistent_kernel(const float* __
   float wa[LP_KH];
   {
     const int r = l32, g = r / LP_U, u = ug * LP_U + (r % LP_U);
-    const float* wr = whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase;
-#pragma unroll
-    for (int s = 0; s < LP_KH; s += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(wr + s);
-      wa[s] = v.x;
-      wa[s + 1] = v.y;
-      wa[s + 2] = v.z;
-      wa[s + 3] = v.w;
-    }
+    lstm_wfrag_f32(whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase, wa);
   }
   for (int i = tid; i < LP_U * LP_BMAX; i += 256) (&cst[0][0])[i] = 0.f;
   if (tid == 0) abort_flag = 0;
@@ -87,7 +76,7 @@ __global__ void __launch_bounds__(256, 1) lstm_persistent_kernel(const float* __
   unsigned* arrive = &sync->arrive[dir];
   const int nbt = (B + 31) / 32;
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
+    const int t = lstm_time(dir, step, T);
     const int tprev = dir == 0 ? t - 1 : t + 1;
     // this thread's gate pre-activations for the cell update (pairs p = tid + 256 k; B <= LP_BMAX = 64, so
     // one B-tile pass), fetched before the barrier wait so their latency hides under it
@@ -117,10 +106,10 @@ __global__ void __launch_bounds__(256, 1) lstm_persistent_kernel(const float* __
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
       __syncthreads();
-      if (abort_flag) {  // barrier timed out: flag the host, poison the remaining outputs, leave
+      if (abort_flag) {  // barrier timed out (lstm_poison's text: as a call this kernel ran slower)
         if (tid == 0 && err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         for (int st = step; st < T; ++st) {
-          const int tt = dir == 0 ? st : T - 1 - st;
+          const int tt = lstm_time(dir, st, T);
           for (int p = tid; p < LP_U * B; p += 256)
             hsd[((size_t)(p / LP_U) * T + tt) * H + ug * LP_U + p % LP_U] = __builtin_nanf("");
         }
@@ -173,13 +162,7 @@ __global__ void __launch_bounds__(256, 1) lstm_persistent_kernel(const float* __
           gs[g] = (red[0][j][r][bl % 32] + red[1][j][r][bl % 32]) + (red[2][j][r][bl % 32] + red[3][j][r][bl % 32]);
         }
         const int unit = ug * LP_U + u;
-        const float gi = lstm_sig(prf[k][0] + gs[0]);
-        const float gf = lstm_sig(prf[k][1] + gs[1]);
-        const float gg = lstm_tanh(prf[k][2] + gs[2]);
-        const float go = lstm_sig(prf[k][3] + gs[3]);
-        const float c = step > 0 ? gf * cst[u][b] + gi * gg : gi * gg;
-        cst[u][b] = c;
-        hsd[((size_t)b * T + t) * H + unit] = go * lstm_tanh(c);
+        hsd[((size_t)b * T + t) * H + unit] = lstm_cell(prf[k], gs, step > 0, cst[u][b]);
       }
       __syncthreads();  // red reused by the next B tiles
     }
@@ -254,18 +237,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     const int r = 32 * m + l32, g = r / LX_U, u = ug * LX_U + (r % LX_U);
-    const float* wr = whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kw + 8 * hh;
-#pragma unroll
-    for (int s = 0; s < LX_KS; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(wr + 16 * s);
-      const float4 b = *reinterpret_cast<const float4*>(wr + 16 * s + 4);
-      const float v0[4] = {a.x, a.y, a.z, a.w}, v1[4] = {b.x, b.y, b.z, b.w};
-      uint2 h0, l0, h1, l1;
-      split4(v0, h0, l0);
-      split4(v1, h1, l1);
-      whi[m][s] = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-      wlo[m][s] = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-    }
+    lstm_wfrag_split(whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kw + 8 * hh, whi[m], wlo[m]);
   }
   for (int i = tid; i < LX_U * LX_S; i += 64 * LX_W) (&cst[0][0])[i] = 0.f;
   if (tid == 0) abort_flag = 0;
@@ -276,7 +248,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
   bf16_t* hxd = hx + (size_t)dir * 2 * hx_par;
   const int cu = tid % LX_U, cb = tid / LX_U;  // cell-update pair (unit, sequence) of this thread
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
+    const int t = lstm_time(dir, step, T);
     // the cell update's gate pre-activations, fetched before the wait (their latency hides under it)
     float prf[4];
     {
@@ -308,13 +280,8 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
         }
       }
       __syncthreads();
-      if (abort_flag) {  // a peer stopped publishing: flag the host, poison the remaining outputs, leave
-        if (tid == 0 && err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        for (int st = step; st < T; ++st) {
-          const int tt = dir == 0 ? st : T - 1 - st;
-          for (int p = tid; p < LX_U * nb; p += 64 * LX_W)
-            hsd[((size_t)(p / LX_U) * T + tt) * H + ug * LX_U + p % LX_U] = __builtin_nanf("");
-        }
+      if (abort_flag) {  // a peer stopped publishing
+        lstm_poison<LX_U, 64 * LX_W>(hsd, err_host, dir, ug, step, T, nb);
         return;
       }
       // ---- B fragments of h_{t-1}: sequence s0 + l32, k = kw + 16 s + 8 hh (hi and lo), sc1 loads -------
@@ -328,21 +295,11 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
         bh[s] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, o + 32 * s, 0, 16));
         bl[s] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, o + 32 * s + 2 * LP_H, 0, 16));
       }
-      // three terms per k-step, small ones first; the two row tiles' chains interleave
-#pragma unroll
-      for (int s = 0; s < LX_KS; ++s)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bl[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-        }
+      lstm_mfma_x3(whi, wlo, bh, bl, acc);
     }
     // ---- K-slice partials -> LDS: acc[m][i] holds row 32 m + 8(i/4) + 4 hh + i%4, sequence l32 ----------
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) red[wave][32 * m + 8 * (i / 4) + 4 * hh + (i % 4)][l32] = acc[m][i];
+    for (int m = 0; m < 2; ++m) lstm_store_partial(red[wave] + 32 * m, acc[m], hh, l32);
     __syncthreads();
     // ---- cell update: thread -> (unit cu, sequence cb), partials summed in a fixed order ----------------
     if (cb < nb) {
@@ -350,16 +307,9 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int r = g * LX_U + cu;
-        gs[g] = ((red[0][r][cb] + red[1][r][cb]) + (red[2][r][cb] + red[3][r][cb])) +
-                ((red[4][r][cb] + red[5][r][cb]) + (red[6][r][cb] + red[7][r][cb]));
+        gs[g] = lstm_sum8(red, r, cb);
       }
-      const float gi = lstm_sig(prf[0] + gs[0]);
-      const float gf = lstm_sig(prf[1] + gs[1]);
-      const float gg = lstm_tanh(prf[2] + gs[2]);
-      const float go = lstm_sig(prf[3] + gs[3]);
-      const float c = step > 0 ? gf * cst[cu][cb] + gi * gg : gi * gg;
-      cst[cu][cb] = c;
-      const float h = go * lstm_tanh(c);
+      const float h = lstm_cell(prf, gs, step > 0, cst[cu][cb]);
       hsd[((size_t)cb * T + t) * H + ug * LX_U + cu] = h;
       hst[cb][cu] = h;
     }
@@ -403,7 +353,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3_kernel(const float* __re
 // hi / lo A fragments, three v_mfma_f32_32x32x16_bf16 terms, K-slice partials summed in LDS in a fixed order, fp32
 // cell state and gate math.  Granules are double-buffered by step parity (no workgroup of a direction can be more
 // than one step ahead of another: publishing h_{t+1} needs every h_t).
-constexpr int LG_BMAX = 16;                            // sequences (one half of lstm_x3's 32-sequence tile)
+constexpr int LG_BMAX = LSTM_GRANULE_B;                // sequences (one half of lstm_x3's 32-sequence tile)
 constexpr int LG_ROWB = 2 * 2 * LP_H + 16;             // LDS image row bytes: hi 640 | lo 640 bf16 + pad
 constexpr int LG_PAIRS = LP_H / 2;                     // 16-byte granule pairs per sequence
 
@@ -418,7 +368,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
   extern __shared__ char lx_pad[];  // occupancy only
   const int H = LP_H;
   const int dir = blockIdx.x / LX_G, ug = blockIdx.x % LX_G;
-  const int nb = B;  // launch_lstm_x3g: B <= LG_BMAX, one workgroup row of sequences
+  const int nb = B;  // launch_lstm: B <= LG_BMAX, one workgroup row of sequences
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int hh = lane >> 5, l32 = lane & 31;
   const int kw = wave * LX_KW;
@@ -430,18 +380,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
 #pragma unroll
   for (int m = 0; m < 2; ++m) {
     const int r = 32 * m + l32, g = r / LX_U, u = ug * LX_U + (r % LX_U);
-    const float* wr = whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kw + 8 * hh;
-#pragma unroll
-    for (int s = 0; s < LX_KS; ++s) {
-      const float4 a = *reinterpret_cast<const float4*>(wr + 16 * s);
-      const float4 b = *reinterpret_cast<const float4*>(wr + 16 * s + 4);
-      const float v0[4] = {a.x, a.y, a.z, a.w}, v1[4] = {b.x, b.y, b.z, b.w};
-      uint2 h0, l0, h1, l1;
-      split4(v0, h0, l0);
-      split4(v1, h1, l1);
-      whi[m][s] = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-      wlo[m][s] = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-    }
+    lstm_wfrag_split(whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kw + 8 * hh, whi[m], wlo[m]);
   }
   for (int i = tid; i < LX_U * LG_BMAX; i += 64 * LX_W) (&cst[0][0])[i] = 0.f;
   for (int i = tid; i < LG_BMAX * LG_ROWB / 16; i += 64 * LX_W)  // rows >= nb stay zero (their B columns unused)
@@ -452,7 +391,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
   const int cu = tid % LX_U, cb = tid / LX_U;  // cell-update pair (unit, sequence) of this thread
   const uint32_t hx0 = (uint32_t)(uintptr_t)hxl;
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
+    const int t = lstm_time(dir, step, T);
     float prf[4];
     {
       const float* pr = pre + ((size_t)cb * T + t) * 8 * H + (size_t)dir * 4 * H + ug * LX_U + cu;
@@ -509,10 +448,10 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
         *reinterpret_cast<uint32_t*>(hxl + sq * LG_ROWB + 2 * H + 2 * u2) = lo;
       }
       __syncthreads();
-      if (abort_flag) {  // a peer stopped publishing: flag the host, poison the remaining outputs, leave
+      if (abort_flag) {  // a peer stopped publishing (lstm_poison's text: as a call this kernel ran slower)
         if (tid == 0 && err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         for (int st = step; st < T; ++st) {
-          const int tt = dir == 0 ? st : T - 1 - st;
+          const int tt = lstm_time(dir, st, T);
           for (int p = tid; p < LX_U * nb; p += 64 * LX_W)
             hsd[((size_t)(p / LX_U) * T + tt) * H + ug * LX_U + p % LX_U] = __builtin_nanf("");
         }
@@ -530,14 +469,7 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
           bh[s] = bl[s] = make_uint4(0u, 0u, 0u, 0u);
         }
       }
-#pragma unroll
-      for (int s = 0; s < LX_KS; ++s)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bl[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-        }
+      lstm_mfma_x3(whi, wlo, bh, bl, acc);
     }
 #pragma unroll
     for (int m = 0; m < 2; ++m)
@@ -550,23 +482,16 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int r = g * LX_U + cu;
-        gs[g] = ((red[0][r][cb] + red[1][r][cb]) + (red[2][r][cb] + red[3][r][cb])) +
-                ((red[4][r][cb] + red[5][r][cb]) + (red[6][r][cb] + red[7][r][cb]));
+        gs[g] = lstm_sum8(red, r, cb);
       }
-      const float gi = lstm_sig(prf[0] + gs[0]);
-      const float gf = lstm_sig(prf[1] + gs[1]);
-      const float gg = lstm_tanh(prf[2] + gs[2]);
-      const float go = lstm_sig(prf[3] + gs[3]);
-      const float c = step > 0 ? gf * cst[cu][cb] + gi * gg : gi * gg;
-      cst[cu][cb] = c;
-      const float h = go * lstm_tanh(c);
+      const float h = lstm_cell(prf, gs, step > 0, cst[cu][cb]);
       hsd[((size_t)cb * T + t) * H + ug * LX_U + cu] = h;
       if (step + 1 < T) {
-        const bf16_t hb = f2bf(h), lb = f2bf(h - bf2f(hb));  // the split of sp_t (17 bits)
+        bf16_t hb, lb;
+        lstm_split_h(h, hb, lb);
         __hip_atomic_store(gd + (size_t)(step & 1) * LG_BMAX * H + (size_t)cb * H + ug * LX_U + cu,
                            ((unsigned long long)(ep + (unsigned)step + 1u) << 32) | ((unsigned)lb << 16) | (unsigned)hb,
-                           __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
     }
     __syncthreads();  // red and the image are rewritten next step
@@ -583,8 +508,8 @@ __global__ void __launch_bounds__(64 * LX_W, 1) lstm_x3g_kernel(const float* __r
 // most one step ahead of any other: publishing h_{t+1} needs every h_t).  The recurrence products
 // run on VALU: lane (wave, k half, row) holds the same 80 W_hh values as above and forms B fp32 dot
 // products of 80 terms; the 8 K-slice partials of each gate row are summed in LDS in a fixed order.
-constexpr int LS_BMAX = 4;   // default small-batch limit
-constexpr int LS_BCAP = 8;   // largest instantiation (a cap of 8, the engine's M2S_LSTM_SMALL_B, selects it for B <= 8)
+constexpr int LS_BMAX = LSTM_SMALL_B;    // default small-batch limit
+constexpr int LS_BCAP = LSTM_SMALL_CAP;  // largest instantiation (a cap of 8, the engine's M2S_LSTM_SMALL_B, selects it for B <= 8)
 
 template <int LS_BMAX>
 __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restrict__ pre, const float* __restrict__ whh,
@@ -606,22 +531,14 @@ __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restr
   float wa[LP_KH];
   {
     const int r = l32, g = r / LP_U, u = ug * LP_U + (r % LP_U);
-    const float* wr = whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase;
-#pragma unroll
-    for (int s = 0; s < LP_KH; s += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(wr + s);
-      wa[s] = v.x;
-      wa[s + 1] = v.y;
-      wa[s + 2] = v.z;
-      wa[s + 3] = v.w;
-    }
+    lstm_wfrag_f32(whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase, wa);
   }
   if (tid < LP_U * LS_BMAX) (&cst[0][0])[tid] = 0.f;
   if (tid == 0) abort_flag = 0;
   __syncthreads();
 
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
+    const int t = lstm_time(dir, step, T);
     float p[LS_BMAX];
 #pragma unroll
     for (int b = 0; b < LS_BMAX; ++b) p[b] = 0.f;
@@ -645,10 +562,10 @@ __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restr
         hsh[i / H][i % H] = __uint_as_float((unsigned)x);
       }
       __syncthreads();
-      if (abort_flag) {  // a peer stopped publishing: flag the host, poison the remaining outputs, leave
+      if (abort_flag) {  // a peer stopped publishing (lstm_poison's text: as a call this kernel ran slower)
         if (tid == 0 && err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         for (int st = step; st < T; ++st) {
-          const int tt = dir == 0 ? st : T - 1 - st;
+          const int tt = lstm_time(dir, st, T);
           for (int q = tid; q < LP_U * B; q += 256)
             hsd[((size_t)(q / LP_U) * T + tt) * H + ug * LP_U + q % LP_U] = __builtin_nanf("");
         }
@@ -681,21 +598,15 @@ __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restr
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         const int r = g * LP_U + u;
-        gs[g] = ((red[0][r][b] + red[1][r][b]) + (red[2][r][b] + red[3][r][b])) +
-                ((red[4][r][b] + red[5][r][b]) + (red[6][r][b] + red[7][r][b]));
+        gs[g] = lstm_sum8(red, r, b);
       }
       const float* pr = pre + ((size_t)b * T + t) * 8 * H + (size_t)dir * 4 * H;
-      const float gi = lstm_sig(pr[unit] + gs[0]);
-      const float gf = lstm_sig(pr[H + unit] + gs[1]);
-      const float gg = lstm_tanh(pr[2 * H + unit] + gs[2]);
-      const float go = lstm_sig(pr[3 * H + unit] + gs[3]);
-      const float c = step > 0 ? gf * cst[u][b] + gi * gg : gi * gg;
-      cst[u][b] = c;
-      const float h = go * lstm_tanh(c);
+      const float pr4[4] = {pr[unit], pr[H + unit], pr[2 * H + unit], pr[3 * H + unit]};
+      const float h = lstm_cell(pr4, gs, step > 0, cst[u][b]);
       hsd[((size_t)b * T + t) * H + unit] = h;
       if (step + 1 < T)
         __hip_atomic_store(gd + (size_t)(step & 1) * LS_BMAX * H + (size_t)b * H + unit,
-                           ((unsigned long long)(ep + (unsigned)step + 1u) << 32) | __float_as_uint(h), __ATOMIC_RELAXED,
+                           lstm_granule(ep + (unsigned)step + 1u, h), __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
     __syncthreads();  // red and hsh are rewritten next step
@@ -715,7 +626,8 @@ __global__ void __launch_bounds__(256, 1) lstm_small_kernel(const float* __restr
 // Double buffering by step parity stays safe per chunk: a workgroup can publish chunk c of h_{t+1} only
 // after every workgroup published chunk c of h_t, i.e. after each of them finished reading chunk c of
 // h_{t-1}.  Exact fp32 products; the partial-sum order is fixed.
-constexpr int LM_BMAX = 64, LM_THREADS = 512;
+constexpr int LM_BMAX = LSTM_LAUNCH_B, LM_THREADS = 512;  // (c and the granules hold 64; lstm_plan routes B <= 16)
+static_assert(LSTM_GRANULE_B <= LM_BMAX && LSTM_GRANULE_B <= LX_S && LSTM_LAUNCH_B == 2 * LX_S, "lstm_route.hpp limits");
 constexpr int LM_KL = LP_H / 16;                    // k per lane (16 slices of 40)
 
 template <int LM_CH>
@@ -740,15 +652,7 @@ __global__ void __launch_bounds__(LM_THREADS, 1) lstm_mid_kernel(const float* __
   float wa[LM_KL];
   {
     const int r = l32, g = r / LP_U, u = ug * LP_U + (r % LP_U);
-    const float* wr = whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase;
-#pragma unroll
-    for (int s = 0; s < LM_KL; s += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(wr + s);
-      wa[s] = v.x;
-      wa[s + 1] = v.y;
-      wa[s + 2] = v.z;
-      wa[s + 3] = v.w;
-    }
+    lstm_wfrag_f32(whh + ((size_t)dir * 4 * H + (size_t)g * H + u) * H + kbase, wa);
   }
   for (int i = tid; i < LP_U * LM_BMAX; i += LM_THREADS) (&cst[0][0])[i] = 0.f;
   if (tid == 0) abort_flag = 0;
@@ -791,7 +695,7 @@ __global__ void __launch_bounds__(LM_THREADS, 1) lstm_mid_kernel(const float* __
   };
 
   for (int step = 0; step < T; ++step) {
-    const int t = dir == 0 ? step : T - 1 - step;
+    const int t = lstm_time(dir, step, T);
     if (step > 0) {
       issue(step, 0);
       land(step, 0, 0);
@@ -807,13 +711,8 @@ __global__ void __launch_bounds__(LM_THREADS, 1) lstm_mid_kernel(const float* __
         for (int q = 0; q < 4; ++q) pr4[q] = pr[q * H];
       }
       __syncthreads();  // chunk c's image complete (and red free)
-      if (abort_flag) {  // a peer stopped publishing: flag the host, poison the remaining outputs, leave
-        if (tid == 0 && err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        for (int st = step; st < T; ++st) {
-          const int tt = dir == 0 ? st : T - 1 - st;
-          for (int q = tid; q < LP_U * B; q += LM_THREADS)
-            hsd[((size_t)(q / LP_U) * T + tt) * H + ug * LP_U + q % LP_U] = __builtin_nanf("");
-        }
+      if (abort_flag) {  // a peer stopped publishing
+        lstm_poison<LP_U, LM_THREADS>(hsd, err_host, dir, ug, step, T, B);
         return;
       }
       if (step > 0 && c + 1 < nch) issue(step, c + 1);  // next chunk's exchange under this chunk's math
@@ -850,64 +749,63 @@ __global__ void __launch_bounds__(LM_THREADS, 1) lstm_mid_kernel(const float* __
             s += (red[sl][r][cb] + red[sl + 1][r][cb]) + (red[sl + 2][r][cb] + red[sl + 3][r][cb]);
           gs[q] = s;
         }
-        const float gi = lstm_sig(pr4[0] + gs[0]);
-        const float gf = lstm_sig(pr4[1] + gs[1]);
-        const float gg = lstm_tanh(pr4[2] + gs[2]);
-        const float go = lstm_sig(pr4[3] + gs[3]);
-        const float cc = step > 0 ? gf * cst[cu][b] + gi * gg : gi * gg;
-        cst[cu][b] = cc;
-        const float h = go * lstm_tanh(cc);
+        const float h = lstm_cell(pr4, gs, step > 0, cst[cu][b]);
         hsd[((size_t)b * T + t) * H + unit] = h;
         if (step + 1 < T)
           __hip_atomic_store(gd + (size_t)(step & 1) * LM_BMAX * H + (size_t)b * H + unit,
-                             ((unsigned long long)(step + 1) << 32) | __float_as_uint(h), __ATOMIC_RELAXED,
+                             lstm_granule((unsigned)(step + 1), h), __ATOMIC_RELAXED,
                              __HIP_MEMORY_SCOPE_AGENT);
       }
     }
   }
 }
 
-}  // namespace
+// ---- host: one launcher for the five kernels --------------------------------------------------------------------
+// A hand-off buffer is [256 B of sync words: the error word (lstm_persistent: LstmSync) | payload: granules, or
+// lstm_x3's flags and split h].
+constexpr size_t LSTM_SYNC_WORDS = 256;
 
-// 4 < B <= 16: above 16 sequences every workgroup's sweep of B x 640 granules per step (sc1 loads, the
-// exchange volume grows with B) costs more than the counter barrier's plain loads of h (tools/lstm_bench.py,
-// profiles/r03f_lstm_ab.txt: B = 32 20.2 vs 18.3 us, B = 64 40.9 vs 24.7 us per step)
-// small_cap: lstm_small's batch limit (4 or 8: Switches::lstm_small_b, the caller's), which lstm_mid starts above
-bool lstm_mid_supported(int B, int H, int small_cap) { return H == LP_H && B > small_cap && B <= 16; }
+struct LstmKernel {
+  const void* fn;
+  const char* tag;   // names the kernel in an error text
+  int grid, threads;
+  size_t lds;
+  int max_b;         // sequences a launch takes
+  bool loops;        // more sequences: one launch per max_b of them (else an unsupported shape)
+  size_t bytes;      // sync words + payload
+  size_t zero;       // the leading bytes a launch needs zeroed
+};
 
-size_t lstm_mid_sync_bytes() { return 256 + (size_t)2 * 2 * LM_BMAX * LP_H * sizeof(unsigned long long); }
-
-void launch_lstm_mid(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s, int small_cap, int chunk) {
-  M2S_CHECK(lstm_mid_supported(B, H, small_cap) && T > 0, "lstm_mid: unsupported shape");
-  const int grid = 2 * (H / LP_U);
-  // sequences per chunk: 4 up to B = 8 (two chunks at B = 8: the second one's sweep overlaps the first's
-  // dot products; 6.5 us per step vs 8.6 at one chunk of 8), 8 above; chunk = 4 / 8 / 16 (the caller's
-  // Switches::lstm_mid_ch, M2S_LSTM_MID_CH) forces one for A/B runs
-  const int ch = chunk == 4 || chunk == 8 || chunk == 16 ? chunk : (B <= 8 ? 4 : 8);
-  const void* fn = ch == 4 ? reinterpret_cast<const void*>(&lstm_mid_kernel<4>)
-                   : ch == 16 ? reinterpret_cast<const void*>(&lstm_mid_kernel<16>)
-                              : reinterpret_cast<const void*>(&lstm_mid_kernel<8>);
-  const int resident = device_resident(fn, LM_THREADS, 0);
-  M2S_CHECK(grid <= resident, "lstm_mid: grid not co-resident on this device");
-  M2S_HIP(hipMemsetAsync(sync, 0, lstm_mid_sync_bytes(), s));
-  unsigned* err = static_cast<unsigned*>(sync);
-  unsigned long long* gran = reinterpret_cast<unsigned long long*>(static_cast<char*>(sync) + 256);
-  if (ch == 4)
-    hipLaunchKernelGGL((lstm_mid_kernel<4>), dim3(grid), dim3(LM_THREADS), 0, s, pre, whh, hs, B, T, gran, err,
-                       spin_max, err_host);
-  else if (ch == 16)
-    hipLaunchKernelGGL((lstm_mid_kernel<16>), dim3(grid), dim3(LM_THREADS), 0, s, pre, whh, hs, B, T, gran, err,
-                       spin_max, err_host);
-  else
-    hipLaunchKernelGGL((lstm_mid_kernel<8>), dim3(grid), dim3(LM_THREADS), 0, s, pre, whh, hs, B, T, gran, err,
-                       spin_max, err_host);
-  M2S_HIP(hipGetLastError());
+LstmKernel lstm_kernel(LstmRoute route, int inst) {
+  const int units8 = 2 * (LP_H / LP_U);  // (direction, 8-unit group) workgroups
+  const size_t gran = (size_t)2 * 2 * LP_H * sizeof(unsigned long long);  // granules a sequence: 2 dir x 2 parity x H
+  switch (route) {
+    case LstmRoute::Small: {
+      const void* fn = inst == LS_BCAP ? reinterpret_cast<const void*>(&lstm_small_kernel<LS_BCAP>)
+                                       : reinterpret_cast<const void*>(&lstm_small_kernel<LS_BMAX>);
+      return {fn, "lstm_small", units8, 256, 0, inst, false, LSTM_SYNC_WORDS + LS_BCAP * gran, LSTM_SYNC_WORDS + LS_BCAP * gran};
+    }
+    case LstmRoute::X3g:  // (direction, unit group): one row of <= 16 sequences
+      return {reinterpret_cast<const void*>(&lstm_x3g_kernel), "lstm_x3g", 2 * LX_G, 64 * LX_W, LX_PAD_LDS, LG_BMAX, false,
+              LSTM_SYNC_WORDS + LG_BMAX * gran, LSTM_SYNC_WORDS + LG_BMAX * gran};
+    case LstmRoute::X3:  // (direction, sequence half, unit group); error word + flags: epochs restart at 0 each launch
+      return {reinterpret_cast<const void*>(&lstm_x3_kernel), "lstm_x3", 2 * 2 * LX_G, 64 * LX_W, LX_PAD_LDS, LP_BMAX, true,
+              LX_FLAGS + (size_t)2 * 2 * LP_BMAX * 2 * LP_H * sizeof(bf16_t), LX_FLAGS};
+    case LstmRoute::Mid: {
+      const void* fn = inst == 4    ? reinterpret_cast<const void*>(&lstm_mid_kernel<4>)
+                       : inst == 16 ? reinterpret_cast<const void*>(&lstm_mid_kernel<16>)
+                                    : reinterpret_cast<const void*>(&lstm_mid_kernel<8>);
+      return {fn, "lstm_mid", units8, LM_THREADS, 0, LG_BMAX, false, LSTM_SYNC_WORDS + LM_BMAX * gran,
+              LSTM_SYNC_WORDS + LM_BMAX * gran};
+    }
+    case LstmRoute::Persistent:
+      return {reinterpret_cast<const void*>(&lstm_persistent_kernel), "lstm_persistent", units8, 256, 0, LP_BMAX, true,
+              LSTM_SYNC_WORDS, LSTM_SYNC_WORDS};
+    case LstmRoute::Step: break;
+  }
+  M2S_CHECK(false, "launch_lstm: the step route has no one-launch kernel");
+  return {};
 }
-
-bool lstm_persistent_supported(int H) { return H == LP_H; }
-
-bool lstm_small_supported(int B, int H, int small_cap) { return H == LP_H && B >= 1 && B <= small_cap; }
 
 // Epoch tags for the granule hand-off (lstm_small, lstm_x3g): a launch publishes tags ep + step + 1 and waits for
 // ep + step, its timeout mark is ep + 1, and the engine's counter advances by T + 1 a launch, so every tag and mark of
@@ -927,89 +825,46 @@ unsigned lstm_epoch(void* sync, size_t bytes, int T, unsigned* epoch, hipStream_
   return e;
 }
 
-size_t lstm_small_sync_bytes() { return 256 + (size_t)2 * 2 * LS_BCAP * LP_H * sizeof(unsigned long long); }
+}  // namespace
 
-void launch_lstm_small(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                       unsigned* err_host, hipStream_t s, int small_cap, unsigned* epoch) {
-  M2S_CHECK((small_cap == LS_BMAX || small_cap == LS_BCAP) && lstm_small_supported(B, H, small_cap) && T > 0,
-            "lstm_small: unsupported shape");
-  const int grid = 2 * (H / LP_U);
-  const bool b8 = B > LS_BMAX;  // the 8-sequence instantiation (small_cap = 8)
-  const void* fn = b8 ? reinterpret_cast<const void*>(&lstm_small_kernel<LS_BCAP>)
-                      : reinterpret_cast<const void*>(&lstm_small_kernel<LS_BMAX>);
-  const int resident = device_resident(fn, 256, 0);
-  M2S_CHECK(grid <= resident, "lstm_small: grid not co-resident on this device");
-  // [256 B: error word][granules 2 dir x 2 parity x LS_BMAX x H], epoch-tagged (lstm_epoch)
-  const unsigned ep = lstm_epoch(sync, lstm_small_sync_bytes(), T, epoch, s);
-  unsigned* err = static_cast<unsigned*>(sync);
-  unsigned long long* gran = reinterpret_cast<unsigned long long*>(static_cast<char*>(sync) + 256);
-  if (b8)
-    hipLaunchKernelGGL(lstm_small_kernel<LS_BCAP>, dim3(grid), dim3(256), 0, s, pre, whh, hs, B, T, gran, err, spin_max,
-                       err_host, ep);
-  else
-    hipLaunchKernelGGL(lstm_small_kernel<LS_BMAX>, dim3(grid), dim3(256), 0, s, pre, whh, hs, B, T, gran, err, spin_max,
-                       err_host, ep);
-  M2S_HIP(hipGetLastError());
+size_t lstm_sync_bytes(bool engine) {
+  size_t n = 0;
+  for (LstmRoute r : {LstmRoute::Small, LstmRoute::X3g, LstmRoute::X3, LstmRoute::Mid, LstmRoute::Persistent})
+    if (lstm_engine_sync(r) == engine) n = std::max(n, lstm_kernel(r, 0).bytes);
+  return n;
 }
 
-size_t lstm_persistent_sync_bytes() { return 256; }
-
-void launch_lstm_persistent(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync,
-                            unsigned spin_max, unsigned* err_host, hipStream_t s) {
-  M2S_CHECK(lstm_persistent_supported(H) && B > 0 && T > 0, "lstm_persistent: unsupported shape");
-  const int grid = 2 * (H / LP_U);
-  // Every workgroup must be resident (the step barrier waits on all of them).  The grid is 160
-  // workgroups at one per CU; check it against the occupancy query once.  (A plain launch has the
-  // same residency as a cooperative one, which only adds this check - and crashes rocprofv3 7.x's
-  // kernel tracer at process exit.)
-  const int resident = device_resident(reinterpret_cast<const void*>(&lstm_persistent_kernel), 256, 0);
-  M2S_CHECK(grid <= resident, "lstm_persistent: grid not co-resident on this device");
-  LstmSync* sp = static_cast<LstmSync*>(sync);
-  for (int b0 = 0; b0 < B; b0 += LP_BMAX) {  // c lives in LDS: at most LP_BMAX sequences per launch
-    const int nb = std::min(LP_BMAX, B - b0);
-    M2S_HIP(hipMemsetAsync(sync, 0, lstm_persistent_sync_bytes(), s));
-    hipLaunchKernelGGL(lstm_persistent_kernel, dim3(grid), dim3(256), 0, s, pre, whh, hs, B, b0, nb, T, sp, spin_max,
-                       err_host);
-    M2S_HIP(hipGetLastError());
+void launch_lstm(const LstmPlan& p, const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync,
+                 unsigned* epoch, unsigned spin_max, unsigned* err_host, hipStream_t s) {
+  const LstmKernel k = lstm_kernel(p.route, p.inst);
+  const std::string tag = k.tag;
+  M2S_CHECK(H == LP_H && B >= 1 && (B <= k.max_b || k.loops) && T > 0, tag + ": unsupported shape");
+  // Every workgroup must be resident (a step's hand-off waits on all of them).  The grid is 80 or 160 workgroups at
+  // one per CU; check it against the occupancy query.  (A plain launch has the same residency as a cooperative one,
+  // which only adds this check - and crashes rocprofv3 7.x's kernel tracer at process exit.)
+  M2S_CHECK(k.grid <= device_resident(k.fn, k.threads, k.lds), tag + ": grid not co-resident on this device");
+  void* payload = static_cast<char*>(sync) + LSTM_SYNC_WORDS;
+  void* hx = static_cast<char*>(sync) + LX_FLAGS;  // lstm_x3: split h behind its flags
+  for (int b0 = 0; b0 < B; b0 += k.max_b) {  // c lives in LDS: at most max_b sequences per launch
+    int nb = std::min(k.max_b, B - b0);
+    unsigned ep = 0;
+    if (p.engine_sync)
+      ep = lstm_epoch(sync, k.zero, T, epoch, s);
+    else
+      M2S_HIP(hipMemsetAsync(sync, 0, k.zero, s));
+    // each kernel's own parameter list
+    void* a_bar[] = {&pre, &whh, &hs, &B, &b0, &nb, &T, &sync, &spin_max, &err_host};
+    void* a_x3[] = {&pre, &whh, &hs, &B, &b0, &nb, &T, &sync, &hx, &spin_max, &err_host};
+    void* a_x3g[] = {&pre, &whh, &hs, &B, &T, &sync, &payload, &spin_max, &err_host, &ep};
+    void* a_small[] = {&pre, &whh, &hs, &B, &T, &payload, &sync, &spin_max, &err_host, &ep};
+    void* a_mid[] = {&pre, &whh, &hs, &B, &T, &payload, &sync, &spin_max, &err_host};
+    void** args = p.route == LstmRoute::Persistent ? a_bar
+                  : p.route == LstmRoute::X3       ? a_x3
+                  : p.route == LstmRoute::X3g      ? a_x3g
+                  : p.route == LstmRoute::Small    ? a_small
+                                                   : a_mid;
+    M2S_HIP(hipLaunchKernel(k.fn, dim3(k.grid), dim3(k.threads), args, k.lds, s));
   }
-}
-
-size_t lstm_x3_sync_bytes() { return LX_FLAGS + (size_t)2 * 2 * LP_BMAX * 2 * LP_H * sizeof(bf16_t); }
-
-void launch_lstm_x3(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                    unsigned* err_host, hipStream_t s) {
-  M2S_CHECK(lstm_persistent_supported(H) && B > 0 && T > 0, "lstm_x3: unsupported shape");
-  const int grid = 2 * 2 * LX_G;  // (direction, sequence half, unit group)
-  const int resident = device_resident(reinterpret_cast<const void*>(&lstm_x3_kernel), 64 * LX_W, LX_PAD_LDS);
-  M2S_CHECK(grid <= resident, "lstm_x3: grid not co-resident on this device");
-  unsigned* sp = static_cast<unsigned*>(sync);
-  bf16_t* hx = reinterpret_cast<bf16_t*>(static_cast<char*>(sync) + LX_FLAGS);
-  for (int b0 = 0; b0 < B; b0 += LP_BMAX) {  // c lives in LDS: at most LP_BMAX sequences per launch
-    const int nb = std::min(LP_BMAX, B - b0);
-    M2S_HIP(hipMemsetAsync(sync, 0, LX_FLAGS, s));  // error word + flags: epochs restart at 0 each launch
-    hipLaunchKernelGGL(lstm_x3_kernel, dim3(grid), dim3(64 * LX_W), LX_PAD_LDS, s, pre, whh, hs, B, b0, nb, T, sp, hx,
-                       spin_max, err_host);
-    M2S_HIP(hipGetLastError());
-  }
-}
-
-size_t lstm_x3g_sync_bytes() { return 256 + (size_t)2 * 2 * LG_BMAX * LP_H * sizeof(unsigned long long); }
-
-bool lstm_x3g_supported(int B, int H) { return H == LP_H && B >= 1 && B <= LG_BMAX; }
-
-void launch_lstm_x3g(const float* pre, const float* whh, float* hs, int B, int T, int H, void* sync, unsigned spin_max,
-                     unsigned* err_host, hipStream_t s, unsigned* epoch) {
-  M2S_CHECK(lstm_x3g_supported(B, H) && T > 0, "lstm_x3g: unsupported shape");
-  const int grid = 2 * LX_G;  // (direction, unit group): one row of <= 16 sequences
-  const int resident = device_resident(reinterpret_cast<const void*>(&lstm_x3g_kernel), 64 * LX_W, LX_PAD_LDS);
-  M2S_CHECK(grid <= resident, "lstm_x3g: grid not co-resident on this device");
-  // [256 B: error word][granules 2 dir x 2 parity x LG_BMAX x H], epoch-tagged (lstm_epoch)
-  const unsigned ep = lstm_epoch(sync, lstm_x3g_sync_bytes(), T, epoch, s);
-  unsigned* err = static_cast<unsigned*>(sync);
-  unsigned long long* gran = reinterpret_cast<unsigned long long*>(static_cast<char*>(sync) + 256);
-  hipLaunchKernelGGL(lstm_x3g_kernel, dim3(grid), dim3(64 * LX_W), LX_PAD_LDS, s, pre, whh, hs, B, T, err, gran, spin_max,
-                     err_host, ep);
-  M2S_HIP(hipGetLastError());
 }
 
 }  // namespace m2s

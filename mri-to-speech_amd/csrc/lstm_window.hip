@@ -23,16 +23,12 @@
 #include <algorithm>
 
 #include "kernels.hpp"
+#include "lstm_cell.hpp"
 
 namespace m2s {
 namespace {
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-__device__ __forceinline__ float lw_sig(float x) { return sigmoidf_(x); }
-__device__ __forceinline__ float lw_tanh(float x) { return 2.f * sigmoidf_(2.f * x) - 1.f; }
-
-constexpr int LW_H = 640;            // hidden size these kernels are built for
+constexpr int LW_H = LSTM_H;         // hidden size these kernels are built for
 constexpr int LW_U = 16;             // units per workgroup (64 gate rows = two MFMA M tiles)
 constexpr int LW_S = 32;             // windows per tile (one MFMA N tile)
 constexpr int LW_W = 8;              // waves
@@ -73,9 +69,9 @@ __global__ void __launch_bounds__(256) lstm_window_step0_kernel(const float* __r
   float h = 0.f, cc = 0.f;
   if (active) {
     const float* pr = pre + (long)(dir == 0 ? e.x : e.x + k - 1) * 8 * LW_H + (long)dir * 4 * LW_H + u;
-    const float gi = lw_sig(pr[0]), gg = lw_tanh(pr[2 * LW_H]), go = lw_sig(pr[3 * LW_H]);
+    const float gi = lstm_sig(pr[0]), gg = lstm_tanh(pr[2 * LW_H]), go = lstm_sig(pr[3 * LW_H]);
     cc = gi * gg;
-    h = go * lw_tanh(cc);
+    h = go * lstm_tanh(cc);
   }
   float* hf = dir == 0 ? hf0 : hf1;
   if (hf) hf[i] = h;
@@ -84,9 +80,10 @@ __global__ void __launch_bounds__(256) lstm_window_step0_kernel(const float* __r
   c[(long)dir * S * LW_H + i] = cc;
   if constexpr (SPLIT) {
     bf16_t* o = static_cast<bf16_t*>(hop) + ((long)dir * S + w) * 2 * LW_H + u;
-    const bf16_t hi = f2bf(h);
+    bf16_t hi, lo;
+    lstm_split_h(h, hi, lo);
     o[0] = hi;
-    o[LW_H] = f2bf(h - bf2f(hi));
+    o[LW_H] = lo;
   } else {
     static_cast<float*>(hop)[(long)dir * S * LW_H + i] = h;
   }
@@ -111,33 +108,12 @@ __global__ void __launch_bounds__(64 * LW_W, 1) lstm_window_step_kernel(const fl
   float wa[SPLIT ? 1 : 2][SPLIT ? 1 : LW_KH];
   if constexpr (SPLIT) {
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const float* wr = wg + (size_t)(32 * m + l32) * LW_H + kw + 8 * hh;  // k = kw + 16 s + 8 hh + 0..7
-#pragma unroll
-      for (int s = 0; s < LW_KS; ++s) {
-        const float4 a = *reinterpret_cast<const float4*>(wr + 16 * s);
-        const float4 b = *reinterpret_cast<const float4*>(wr + 16 * s + 4);
-        const float v0[4] = {a.x, a.y, a.z, a.w}, v1[4] = {b.x, b.y, b.z, b.w};
-        uint2 h0, l0, h1, l1;
-        split4(v0, h0, l0);
-        split4(v1, h1, l1);
-        whi[m][s] = __builtin_bit_cast(bf16x8, make_uint4(h0.x, h0.y, h1.x, h1.y));
-        wlo[m][s] = __builtin_bit_cast(bf16x8, make_uint4(l0.x, l0.y, l1.x, l1.y));
-      }
-    }
+    for (int m = 0; m < 2; ++m)
+      lstm_wfrag_split(wg + (size_t)(32 * m + l32) * LW_H + kw + 8 * hh, whi[m], wlo[m]);  // k = kw + 16 s + 8 hh + 0..7
   } else {
 #pragma unroll
-    for (int m = 0; m < 2; ++m) {
-      const float* wr = wg + (size_t)(32 * m + l32) * LW_H + kw + LW_KH * hh;  // k = kw + 40 hh + s
-#pragma unroll
-      for (int s = 0; s < LW_KH; s += 4) {
-        const float4 v = *reinterpret_cast<const float4*>(wr + s);
-        wa[m][s] = v.x;
-        wa[m][s + 1] = v.y;
-        wa[m][s + 2] = v.z;
-        wa[m][s + 3] = v.w;
-      }
-    }
+    for (int m = 0; m < 2; ++m)
+      lstm_wfrag_f32(wg + (size_t)(32 * m + l32) * LW_H + kw + LW_KH * hh, wa[m]);  // k = kw + 40 hh + s
   }
 
   const int cu = tid % LW_U, cb = tid / LW_U;  // cell-update pair (unit, window of the tile) of this thread
@@ -174,15 +150,7 @@ __global__ void __launch_bounds__(64 * LW_W, 1) lstm_window_step_kernel(const fl
         bh[s] = wl < S ? *reinterpret_cast<const uint4*>(hr + 16 * s) : make_uint4(0u, 0u, 0u, 0u);
         bl[s] = wl < S ? *reinterpret_cast<const uint4*>(hr + 16 * s + LW_H) : make_uint4(0u, 0u, 0u, 0u);
       }
-      // three terms per k-step, small ones first (lstm_x3_kernel's order)
-#pragma unroll
-      for (int s = 0; s < LW_KS; ++s)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wlo[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bl[s]), acc[m], 0, 0, 0);
-          acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(whi[m][s], __builtin_bit_cast(bf16x8, bh[s]), acc[m], 0, 0, 0);
-        }
+      lstm_mfma_x3(whi, wlo, bh, bl, acc);
     } else {
       float hb[LW_KH];
       const float* hr = static_cast<const float*>(hin) + ((long)dir * S + wl) * LW_H + kw + LW_KH * hh;
@@ -202,9 +170,7 @@ __global__ void __launch_bounds__(64 * LW_W, 1) lstm_window_step_kernel(const fl
     }
     // ---- K-slice partials -> LDS: acc[m][i] holds row 32 m + 8 (i / 4) + 4 hh + i % 4, window l32 ---------------
 #pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-      for (int i = 0; i < 16; ++i) red[wave][32 * m + 8 * (i / 4) + 4 * hh + (i % 4)][l32] = acc[m][i];
+    for (int m = 0; m < 2; ++m) lstm_store_partial(red[wave] + 32 * m, acc[m], hh, l32);
     __syncthreads();
     // ---- cell update: thread -> (unit cu, window cb), partials summed in a fixed order --------------------------
     if (live) {
@@ -214,15 +180,10 @@ __global__ void __launch_bounds__(64 * LW_W, 1) lstm_window_step_kernel(const fl
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
           const int r = g * LW_U + cu;
-          gs[g] = ((red[0][r][cb] + red[1][r][cb]) + (red[2][r][cb] + red[3][r][cb])) +
-                  ((red[4][r][cb] + red[5][r][cb]) + (red[6][r][cb] + red[7][r][cb]));
+          gs[g] = lstm_sum8(red, r, cb);
         }
-        const float gi = lw_sig(prf[0] + gs[0]);
-        const float gf = lw_sig(prf[1] + gs[1]);
-        const float gg = lw_tanh(prf[2] + gs[2]);
-        const float go = lw_sig(prf[3] + gs[3]);
-        cc = gf * cprev + gi * gg;
-        h = go * lw_tanh(cc);
+        cc = cprev;
+        h = lstm_cell(prf, gs, true, cc);
       }
       const long o = ((long)dir * S + wc) * LW_H + unit;
       c[o] = cc;
@@ -230,9 +191,10 @@ __global__ void __launch_bounds__(64 * LW_W, 1) lstm_window_step_kernel(const fl
       if (hout) {
         if constexpr (SPLIT) {
           bf16_t* ho = static_cast<bf16_t*>(hout) + ((long)dir * S + wc) * 2 * LW_H + unit;
-          const bf16_t hi = f2bf(h);
+          bf16_t hi, lo;
+          lstm_split_h(h, hi, lo);
           ho[0] = hi;
-          ho[LW_H] = f2bf(h - bf2f(hi));
+          ho[LW_H] = lo;
         } else {
           static_cast<float*>(hout)[o] = h;
         }

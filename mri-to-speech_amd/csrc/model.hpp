@@ -362,11 +362,11 @@ class Acoustic {
     // conv_pwl runs on se_ws; ... and ir_ws handed it plain fp32 rows
     bool f8, sews, mid_f32;
   };
-  // the recurrence kernel for (B, T): the selection ladder shared by bilstm and bilstm_ragged.  seq_steps / rows:
-  // the recurrent steps and (b, t) rows that count as algorithmic work (a ragged call: the valid ones)
+  // the recurrence for (B, T), shared by bilstm and bilstm_ragged: the kernel lstm_plan (lstm_route.hpp) chooses,
+  // one record, one launch (or a launch per step).  seq_steps / rows: the recurrent steps and (b, t) rows that count
+  // as algorithmic work (a ragged call: the valid ones)
   void lstm_recurrence(const float* pre, float* hs, float* cst, void* sync, int B, int T, double seq_steps, double rows,
                        hipStream_t s);
-  static size_t lstm_sync_bytes();
   RaggedTable rtab_;
   template <typename T>
   void effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
@@ -391,10 +391,11 @@ class Acoustic {
   const Switches sw_;  // the M2S_* switches as the environment held them when the engine was created (switches.hpp)
   Arena arena_;
   AcousticPlan p_;
-  unsigned* err_host_ = nullptr;  // pinned, host-mapped: set by lstm_persistent_kernel on a barrier timeout
+  unsigned* err_host_ = nullptr;  // pinned, host-mapped: set by a one-launch BiLSTM kernel whose hand-off wait timed out
   unsigned* err_dev_ = nullptr;
-  // the granule BiLSTM kernels' sync buffer (lstm_small / lstm_x3g), zeroed once, and its epoch count
-  // (lstm_persistent.hip lstm_epoch)
+  // the hand-off buffer of the plans with engine_sync (lstm_route.hpp: lstm_small, lstm_x3g), lstm_sync_bytes(true),
+  // and its epoch count: zeroed on first use, near the tag wrap and under stream capture, else tags continue from
+  // the last call (lstm_persistent.hip lstm_epoch)
   void* gsync_ = nullptr;
   unsigned gsync_epoch_ = 0;
 };

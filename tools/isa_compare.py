@@ -14,7 +14,7 @@ import collections, difflib, os, re, subprocess, sys, tempfile
 
 CSRC = "mri-to-speech_amd/csrc"
 DEFAULT = ("conv_gemm conv_halo gemm128 mrf_fused er_fused er2_fused ers2_fused er_sp_fused er8_fused er8w_fused "
-           "ir_ws se_ws conv1d_halo dwse kernels").split()
+           "ir_ws se_ws conv1d_halo dwse kernels lstm_persistent lstm_window").split()
 RES = (".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_size", ".private_segment_fixed_size",
        ".vgpr_spill_count", ".sgpr_spill_count")
 
