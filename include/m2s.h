@@ -202,6 +202,39 @@ enum m2s_frame_norm { M2S_FRAME_ZSCORE_MINMAX = 0, M2S_FRAME_UNIT = 1 };
 int m2s_preprocess_frames_resize(const uint8_t* frames, int n, int h, int w, int channels, int out_h, int out_w,
                                  int interp, int norm, float* out, void* stream);
 
+/* ------------------------------------------------------------------- occlusion ----
+ * The masking experiment (scripts/mask_rtmri_video.py, docs/rtmri_pipeline_notes.md step 5) on the device.
+ *
+ * m2s_preprocess_frames_masked: the frame front end above for n_masks masked variants of every frame in one
+ * launch.  masks is device fp32 (n_masks,h,w); out is (n_masks,n,out_h,out_w).  Variant m of frame i is the
+ * reference's application, every byte of every channel -> (uint8)clip((float)byte * masks[m][y][x], 0, 255)
+ * (one IEEE multiply, truncation toward zero: numpy's bits), followed by m2s_preprocess_frames_resize: BGR ->
+ * grey, resize, normalisation.  Mask values outside [0, 1] are legal (the clip handles them); masks must be
+ * finite.  M2S_E_ARG before anything is launched: every refusal of m2s_preprocess_frames_resize, n_masks outside
+ * 1..65535, a null masks with n > 0.  n = 0 is a no-op.  Stateless, no workspace, writes out completely and
+ * nothing else; can be captured into a graph.  Device pointers, stream-ordered. */
+int m2s_preprocess_frames_masked(const uint8_t* frames, int n, int h, int w, int channels, const float* masks, int n_masks,
+                                 int out_h, int out_w, int interp, int norm, float* out, void* stream);
+
+/* m2s_occlusion_reduce: the variants' mels of ONE clip -> scores and an occlusion-sensitivity map, without a host
+ * read.  mel is device fp32 (V,T,n_mels), variant 0 the unmasked baseline, variant m + 1 the clip under mask m,
+ * M = V - 1.  band_mask is device fp32 (n_bands,n_mels) of 0 / 1 (the Grad-CAM bands); an "all bins" column is
+ * always appended: nb = n_bands + 1.  Outputs, device fp32:
+ *   score     (M,nb)    mean over t and over the band's bins of |mel[m + 1] - mel[0]| (dB where mel is mel_db);
+ *                       a band without bins scores 0
+ *   per_frame (M,T,nb)  the same per frame; may be NULL
+ *   map       (nb,h,w)  sum_m c_m score[m][b] / sum_m c_m with c_m = max(1 - masks[m], 0), masks device fp32
+ *                       (M,h,w), finite; 0 where sum_m c_m > 1e-6 does not hold.  With normalize != 0 every band
+ *                       becomes (v - min) / ((max - min) + 1e-6) over its pixels, the Grad-CAM heat maps' rule: a
+ *                       flat band gives zeros.  May be NULL, and masks with it.
+ * At most two launches, no atomics, a fixed summation order: repeated calls are bit-identical.  M2S_E_ARG before
+ * anything is launched: V < 2, T < 1, n_mels outside 1..256, n_bands outside 0..8, a null band_mask with
+ * n_bands > 0, a null mel or score, a map without masks or with h or w < 1.  No workspace; can be captured into
+ * a graph.  Stream-ordered. */
+int m2s_occlusion_reduce(const float* mel, int V, int T, int n_mels, const float* band_mask, int n_bands,
+                         const float* masks, int h, int w, int normalize, float* score, float* per_frame, float* map,
+                         void* stream);
+
 /* Packs a Generator state dict (weight_g/weight_v or plain weight after remove_weight_norm).
  * Strict like load_state_dict(ckpt['generator']): a missing key is M2S_E_ARG.  Synchronous. */
 int m2s_vocoder_create(const m2s_tensor* sd, int n, const m2s_hifigan_h* h, int dtype, int device, m2s_vocoder** out);

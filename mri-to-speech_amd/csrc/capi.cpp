@@ -223,6 +223,23 @@ int m2s_preprocess_frames_resize(const uint8_t* frames, int n, int h, int w, int
   });
 }
 
+int m2s_preprocess_frames_masked(const uint8_t* frames, int n, int h, int w, int channels, const float* masks, int n_masks,
+                                 int out_h, int out_w, int interp, int norm, float* out, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(n >= 0 && n_masks >= 1 && (n == 0 || (frames && masks && out)), "bad argument");
+    m2s::launch_frames_masked(frames, n, h, w, channels, masks, n_masks, out_h, out_w, interp, norm, out, S(stream));
+  });
+}
+
+int m2s_occlusion_reduce(const float* mel, int V, int T, int n_mels, const float* band_mask, int n_bands,
+                         const float* masks, int h, int w, int normalize, float* score, float* per_frame, float* map,
+                         void* stream) {
+  return guarded([&] {
+    m2s::launch_occlusion_reduce(mel, V, T, n_mels, band_mask, n_bands, masks, h, w, normalize, score, per_frame, map,
+                                 S(stream));  // checks the limits
+  });
+}
+
 int m2s_vocoder_create(const m2s_tensor* sd, int n, const m2s_hifigan_h* h, int dtype, int device, m2s_vocoder** out) {
   return guarded([&] {
     M2S_CHECK(out && h && (sd || n == 0), "null argument");

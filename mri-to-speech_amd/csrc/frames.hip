@@ -24,6 +24,12 @@
 // reduction scratch and the level table reuse the source bytes, which are dead after pass 1.  ZSCORE_MINMAX is
 // preprocess_kernel's arithmetic on the resized integers; UNIT is (float)g / 255.0f.  Store-bound: h*w*ch bytes in,
 // 4*out_h*out_w bytes out per frame.
+//
+// Masked variant (frames_masked_kernel): grid (frame, mask variant), the same body with the staging
+// helpers' MASKED branch compiled in.  Every byte of every channel becomes (uint8)clip((float)byte * mask[y][x], 0,
+// 255) on its way into LDS (scripts/mask_rtmri_video.py:96-98: one IEEE multiply, truncation), before bgr_grey.  The
+// mask row is read from global memory (float4 where its base m*h*w*4 allows, dwords otherwise) and never staged, so
+// the LDS layout and limits are the unmasked kernel's; frames and masks are re-read per variant out of L2.
 #include "kernels.hpp"
 #include "prof.hpp"
 
@@ -92,9 +98,31 @@ __device__ __forceinline__ Coef coef_unpack(uint2 e) {
 
 __device__ __forceinline__ int bgr_grey(int b, int g, int r) { return (1868 * b + 9617 * g + 4899 * r + (1 << 13)) >> 14; }
 
-// NW dwords of grey pixels per step: NW source dwords (grey) or 3 NW (BGR) -> NW dwords of LDS; bytes for the rest
-template <int NW>
-__device__ __forceinline__ void stage_frame(const uint8_t* __restrict__ f, int hw, int ch, uint8_t* src, int tid) {
+// the reference's mask application to one byte: float multiply, clip to [0, 255], truncate
+__device__ __forceinline__ int mask_byte(int b, float m) { return (int)fminf(fmaxf((float)b * m, 0.f), 255.f); }
+
+// the masks of pixels p .. p + 3 (p % 4 == 0): one 16-byte load where the mask's base allows it
+__device__ __forceinline__ float4 mask4(const float* __restrict__ mk, int p, bool mvec) {
+  if (mvec) return *reinterpret_cast<const float4*>(mk + p);
+  return make_float4(mk[p], mk[p + 1], mk[p + 2], mk[p + 3]);
+}
+
+template <bool MASKED>
+__device__ __forceinline__ uint8_t stage_pixel(const uint8_t* __restrict__ f, int ch, int p, const float* __restrict__ mk) {
+  if constexpr (MASKED) {
+    const float m = mk[p];
+    return ch == 1 ? (uint8_t)mask_byte(f[p], m)
+                   : (uint8_t)bgr_grey(mask_byte(f[3 * p], m), mask_byte(f[3 * p + 1], m), mask_byte(f[3 * p + 2], m));
+  } else {
+    return ch == 1 ? f[p] : (uint8_t)bgr_grey(f[3 * p], f[3 * p + 1], f[3 * p + 2]);
+  }
+}
+
+// NW dwords of grey pixels per step: NW source dwords (grey) or 3 NW (BGR) -> NW dwords of LDS; bytes for the rest.
+// MASKED: every source byte goes through mask_byte with its pixel's mask first (mk = this variant's mask).
+template <int NW, bool MASKED>
+__device__ __forceinline__ void stage_frame(const uint8_t* __restrict__ f, int hw, int ch, uint8_t* src, int tid,
+                                            const float* __restrict__ mk, bool mvec) {
   const int nv = hw / (4 * NW);
   const uint32_t* f32 = reinterpret_cast<const uint32_t*>(f);
   uint32_t* s32 = reinterpret_cast<uint32_t*>(src);
@@ -103,6 +131,14 @@ __device__ __forceinline__ void stage_frame(const uint8_t* __restrict__ f, int h
       uint32_t v[NW];
 #pragma unroll
       for (int j = 0; j < NW; ++j) v[j] = f32[k * NW + j];
+      if constexpr (MASKED) {
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+          const float4 m = mask4(mk, 4 * (k * NW + j), mvec);
+          v[j] = (uint32_t)mask_byte(v[j] & 255, m.x) | ((uint32_t)mask_byte((v[j] >> 8) & 255, m.y) << 8) |
+                 ((uint32_t)mask_byte((v[j] >> 16) & 255, m.z) << 16) | ((uint32_t)mask_byte(v[j] >> 24, m.w) << 24);
+        }
+      }
 #pragma unroll
       for (int j = 0; j < NW; ++j) s32[k * NW + j] = v[j];
     }
@@ -114,25 +150,31 @@ __device__ __forceinline__ void stage_frame(const uint8_t* __restrict__ f, int h
 #pragma unroll
       for (int j = 0; j < NW; ++j) {
         uint32_t o = 0;
+        float mq[4] = {1.f, 1.f, 1.f, 1.f};
+        if constexpr (MASKED) {
+          const float4 m = mask4(mk, 4 * (k * NW + j), mvec);
+          mq[0] = m.x, mq[1] = m.y, mq[2] = m.z, mq[3] = m.w;
+        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int b = 3 * (4 * j + q);  // byte offset of the pixel's B within v
-          const int B = (v[b >> 2] >> (8 * (b & 3))) & 255;
-          const int G = (v[(b + 1) >> 2] >> (8 * ((b + 1) & 3))) & 255;
-          const int R = (v[(b + 2) >> 2] >> (8 * ((b + 2) & 3))) & 255;
+          int B = (v[b >> 2] >> (8 * (b & 3))) & 255;
+          int G = (v[(b + 1) >> 2] >> (8 * ((b + 1) & 3))) & 255;
+          int R = (v[(b + 2) >> 2] >> (8 * ((b + 2) & 3))) & 255;
+          if constexpr (MASKED) B = mask_byte(B, mq[q]), G = mask_byte(G, mq[q]), R = mask_byte(R, mq[q]);
           o |= (uint32_t)bgr_grey(B, G, R) << (8 * q);
         }
         s32[k * NW + j] = o;
       }
     }
   }
-  for (int p = nv * 4 * NW + tid; p < hw; p += FR_THREADS)
-    src[p] = ch == 1 ? f[p] : (uint8_t)bgr_grey(f[3 * p], f[3 * p + 1], f[3 * p + 2]);
+  for (int p = nv * 4 * NW + tid; p < hw; p += FR_THREADS) src[p] = stage_pixel<MASKED>(f, ch, p, mk);
 }
 
-// 8 waves a SIMD (64 VGPRs): two workgroups share a CU where their LDS fits (84 x 84 -> 256 x 256 takes 77 KB)
-__global__ void __launch_bounds__(FR_THREADS, 8) frames_kernel(const uint8_t* __restrict__ frames, int h, int w, int ch, int Ho,
-                                                            int Wo, int interp, int norm_mode, float* __restrict__ out) {
+// One frame through staging, resize and normalisation: f the frame's bytes, o its output, mk its mask (MASKED only).
+template <bool MASKED>
+__device__ __forceinline__ void frames_body(const uint8_t* __restrict__ f, const float* __restrict__ mk, int h, int w, int ch,
+                                            int Ho, int Wo, int interp, int norm_mode, float* __restrict__ o) {
   extern __shared__ __attribute__((aligned(16))) uint8_t fr_lds[];
   const int hw = h * w, how = Ho * Wo;
   const FrLayout L(hw, how, Ho, Wo);
@@ -140,8 +182,6 @@ __global__ void __launch_bounds__(FR_THREADS, 8) frames_kernel(const uint8_t* __
   uint8_t* src = fr_lds + L.dst;
   uint2* ty = reinterpret_cast<uint2*>(fr_lds + L.dst + L.src);
   uint2* tx = ty + Ho;
-  const uint8_t* f = frames + (size_t)blockIdx.x * hw * ch;
-  float* o = out + (size_t)blockIdx.x * how;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   double inv_y, scale_y, inv_x, scale_x;
@@ -153,13 +193,13 @@ __global__ void __launch_bounds__(FR_THREADS, 8) frames_kernel(const uint8_t* __
     scale_x = 1.0 / inv_x;
   }
 
+  const bool mvec = MASKED && ((uintptr_t)mk & 15) == 0;  // a mask base is dword-aligned, 16-byte aligned only sometimes
   if (((uintptr_t)f & 15) == 0)
-    stage_frame<4>(f, hw, ch, src, tid);
+    stage_frame<4, MASKED>(f, hw, ch, src, tid, mk, mvec);
   else if (((uintptr_t)f & 3) == 0)
-    stage_frame<1>(f, hw, ch, src, tid);
+    stage_frame<1, MASKED>(f, hw, ch, src, tid, mk, mvec);
   else
-    for (int p = tid; p < hw; p += FR_THREADS)
-      src[p] = ch == 1 ? f[p] : (uint8_t)bgr_grey(f[3 * p], f[3 * p + 1], f[3 * p + 2]);
+    for (int p = tid; p < hw; p += FR_THREADS) src[p] = stage_pixel<MASKED>(f, ch, p, mk);
   if (L.tab)
     for (int i = tid; i < Ho + Wo; i += FR_THREADS)
       ty[i] = coef_pack(i < Ho ? coef_at(i, h, inv_y, scale_y, interp) : coef_at(i - Ho, w, inv_x, scale_x, interp));
@@ -287,16 +327,39 @@ __global__ void __launch_bounds__(FR_THREADS, 8) frames_kernel(const uint8_t* __
   }
 }
 
+// 8 waves a SIMD (64 VGPRs): two workgroups share a CU where their LDS fits (84 x 84 -> 256 x 256 takes 77 KB)
+__global__ void __launch_bounds__(FR_THREADS, 8) frames_kernel(const uint8_t* __restrict__ frames, int h, int w, int ch, int Ho,
+                                                            int Wo, int interp, int norm_mode, float* __restrict__ out) {
+  const int hw = h * w, how = Ho * Wo;
+  frames_body<false>(frames + (size_t)blockIdx.x * hw * ch, nullptr, h, w, ch, Ho, Wo, interp, norm_mode,
+                     out + (size_t)blockIdx.x * how);
+}
+
+// grid (frame, mask variant): out (n_masks, N, Ho, Wo)
+__global__ void __launch_bounds__(FR_THREADS, 8) frames_masked_kernel(const uint8_t* __restrict__ frames, int h, int w, int ch,
+                                                                   const float* __restrict__ masks, int Ho, int Wo,
+                                                                   int interp, int norm_mode, float* __restrict__ out) {
+  const int hw = h * w, how = Ho * Wo;
+  frames_body<true>(frames + (size_t)blockIdx.x * hw * ch, masks + (size_t)blockIdx.y * hw, h, w, ch, Ho, Wo, interp,
+                    norm_mode, out + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * how);
+}
+
 }  // namespace
 
-void launch_frames(const uint8_t* frames, int N, int h, int w, int channels, int out_h, int out_w, int interp, int norm,
-                   float* out, hipStream_t s) {
+namespace {
+void check_frames(int N, int h, int w, int channels, int out_h, int out_w, int interp, int norm) {
   M2S_CHECK(N >= 0 && h > 0 && w > 0 && out_h > 0 && out_w > 0, "frames: bad shape");
   M2S_CHECK(channels == 1 || channels == 3, "frames: channels must be 1 (grey) or 3 (BGR)");
   M2S_CHECK(h <= out_h && w <= out_w, "frames: a shrinking resize is not supported (OpenCV takes other paths there)");
   M2S_CHECK((long)h * w <= FR_MAX_PIX && (long)out_h * out_w <= FR_MAX_PIX, "frames: more than 65536 pixels a frame");
   M2S_CHECK(interp == 0 || interp == 1, "frames: unknown m2s_frame_interp");
   M2S_CHECK(norm == 0 || norm == 1, "frames: unknown m2s_frame_norm");
+}
+}  // namespace
+
+void launch_frames(const uint8_t* frames, int N, int h, int w, int channels, int out_h, int out_w, int interp, int norm,
+                   float* out, hipStream_t s) {
+  check_frames(N, h, w, channels, out_h, out_w, interp, norm);
   if (N == 0) return;
   M2S_CHECK(frames && out, "frames: null argument");
   const FrLayout L(h * w, out_h * out_w, out_h, out_w);
@@ -306,6 +369,22 @@ void launch_frames(const uint8_t* frames, int N, int h, int w, int channels, int
   ProfScope ps("frames_kernel", 0.0, bytes, s);
   hipLaunchKernelGGL(frames_kernel, dim3(N), dim3(FR_THREADS), L.total, s, frames, h, w, channels, out_h, out_w, interp, norm,
                      out);
+  M2S_HIP(hipGetLastError());
+}
+
+void launch_frames_masked(const uint8_t* frames, int N, int h, int w, int channels, const float* masks, int n_masks,
+                          int out_h, int out_w, int interp, int norm, float* out, hipStream_t s) {
+  check_frames(N, h, w, channels, out_h, out_w, interp, norm);
+  M2S_CHECK(n_masks >= 1 && n_masks <= 65535, "frames: n_masks outside 1..65535");
+  if (N == 0) return;
+  M2S_CHECK(frames && masks && out, "frames: null argument");
+  const FrLayout L(h * w, out_h * out_w, out_h, out_w);
+  allow_lds(reinterpret_cast<const void*>(&frames_masked_kernel));
+  StageTag tag("frames");
+  const double bytes = (double)N * n_masks * ((double)h * w * (channels + 4.0) + 4.0 * out_h * out_w);
+  ProfScope ps("frames_masked_kernel", 0.0, bytes, s);
+  hipLaunchKernelGGL(frames_masked_kernel, dim3(N, n_masks), dim3(FR_THREADS), L.total, s, frames, h, w, channels, masks, out_h,
+                     out_w, interp, norm, out);
   M2S_HIP(hipGetLastError());
 }
 

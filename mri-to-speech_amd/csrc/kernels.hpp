@@ -252,6 +252,18 @@ void launch_preprocess(const uint8_t* frames, int N, int H, int W, int channels,
 // At most 65536 pixels a frame on either side.  One workgroup per frame, no workspace.  (frames.hip)
 void launch_frames(const uint8_t* frames, int N, int h, int w, int channels, int out_h, int out_w, int interp, int norm,
                    float* out, hipStream_t s);
+// n_masks masked variants of every frame: masks (n_masks,h,w) fp32, every byte of every channel becomes
+// (uint8)clip((float)byte * mask[y][x], 0, 255) before BGR -> grey; out (n_masks,N,out_h,out_w).  Grid (N, n_masks),
+// the masks read from global memory while the frame is staged.  (frames.hip)
+void launch_frames_masked(const uint8_t* frames, int N, int h, int w, int channels, const float* masks, int n_masks,
+                          int out_h, int out_w, int interp, int norm, float* out, hipStream_t s);
+
+// Occlusion scores and map of one clip: mel (V,T,n_mels), variant 0 the baseline; band_mask (n_bands,n_mels) 0 / 1;
+// score (V-1,nb), per_frame (V-1,T,nb) or null, map (nb,h,w) or null from masks (V-1,h,w); nb = n_bands + 1 (the
+// last column is all bins).  Two launches, fixed summation order.  (occlusion.hip)
+void launch_occlusion_reduce(const float* mel, int V, int T, int n_mels, const float* band_mask, int n_bands,
+                             const float* masks, int h, int w, int normalize, float* score, float* per_frame, float* map,
+                             hipStream_t s);
 
 // Global average pool: x (N,P,cs) T -> feats (N,C) fp32 (dense, row stride C).
 template <typename T>

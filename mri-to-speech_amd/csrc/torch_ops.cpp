@@ -17,6 +17,8 @@
 //   preprocess_frames  _preprocess_frame after the host decode         run_mri_video_inference.py:34-54
 //   preprocess_frames_resize  the same with cv2.resize on the device, and the training convention
 //                      (INTER_AREA, / 255)                            mri2speech_code/preprocess_rtmri_data.py:99-113
+//   preprocess_frames_masked  build_mask's application ahead of the front end, every variant   scripts/mask_rtmri_video.py:96-98
+//   occlusion_reduce   the masking experiment's comparison, as scores and a map   docs/rtmri_pipeline_notes.md step 5
 //   *_pairs            the model on every training pair of a clip   mri2speech_code/preprocess_rtmri_data.py:198-259,
 //                      train_mri_acoustic_model.py:349-384
 //   mel_metrics        MaskedMSEMAE, band MAEs, eval_mel's losses and MCD-like   train_mri_acoustic_model.py:57-167,
@@ -438,6 +440,55 @@ at::Tensor preprocess_frames_resize(const at::Tensor& frames, int64_t out_h, int
   return out;
 }
 
+// the same for M masked variants of every frame: masks (M,h,w) fp32 -> (M,T,out_h,out_w); every byte is multiplied
+// by its pixel's mask, clipped and truncated before BGR -> grey (scripts/mask_rtmri_video.py:96-98)
+at::Tensor preprocess_frames_masked(const at::Tensor& frames, const at::Tensor& masks, int64_t out_h, int64_t out_w,
+                                    int64_t interp, int64_t norm) {
+  TORCH_CHECK(frames.is_cuda() && frames.scalar_type() == at::kByte, "preprocess_frames_masked: uint8 HIP tensor expected");
+  TORCH_CHECK(frames.dim() == 3 || (frames.dim() == 4 && frames.size(3) == 3), "preprocess_frames_masked: (T,h,w[,3])");
+  TORCH_CHECK(out_h > 0 && out_w > 0 && out_h <= 65536 && out_w <= 65536, "preprocess_frames_masked: bad output size");
+  TORCH_CHECK(masks.is_cuda() && masks.scalar_type() == at::kFloat && masks.dim() == 3 && masks.size(0) >= 1 &&
+                  masks.size(1) == frames.size(1) && masks.size(2) == frames.size(2),
+              "preprocess_frames_masked: masks must be a fp32 HIP tensor (M,h,w) of the frames' size, M >= 1");
+  const Guard g(frames.device());
+  const at::Tensor x = frames.contiguous(), mk = masks.contiguous();
+  const int n = x.size(0), hh = x.size(1), ww = x.size(2), ch = x.dim() == 4 ? 3 : 1;
+  at::Tensor out = at::empty({mk.size(0), n, out_h, out_w}, x.options().dtype(at::kFloat));
+  ok(m2s_preprocess_frames_masked(x.data_ptr<uint8_t>(), n, hh, ww, ch, mk.data_ptr<float>(), (int)mk.size(0), (int)out_h,
+                                  (int)out_w, (int)interp, (int)norm, out.data_ptr<float>(), S()),
+     "preprocess_frames_masked");
+  return out;
+}
+
+// mel (V,T,n_mels) of one clip's variants (0 = baseline), band_mask (n_bands,n_mels), masks (V-1,h,w) or None ->
+// score (V-1,nb), per_frame (V-1,T,nb) [(0,T,nb) unless wanted], map (nb,h,w) [(nb,0,0) without masks]
+std::tuple<at::Tensor, at::Tensor, at::Tensor> occlusion_reduce(const at::Tensor& mel_, const at::Tensor& band_mask_,
+                                                                const c10::optional<at::Tensor>& masks_, bool normalize,
+                                                                bool want_per_frame) {
+  TORCH_CHECK(mel_.dim() == 3, "occlusion_reduce: mel must be (V,T,n_mels)");
+  TORCH_CHECK(band_mask_.dim() == 2 && band_mask_.size(1) == mel_.size(2), "occlusion_reduce: band_mask must be (n_bands,n_mels)");
+  const Guard g(mel_.device());
+  const at::Tensor mel = f32_on_device(mel_, "mel"), bm = f32_on_device(band_mask_, "band_mask");
+  const int V = mel.size(0), T = mel.size(1), nm = mel.size(2), n_bands = bm.size(0), nb = n_bands + 1;
+  const int M = V > 0 ? V - 1 : 0;
+  at::Tensor masks;
+  int h = 0, w = 0;
+  if (masks_.has_value()) {
+    masks = f32_on_device(*masks_, "masks");
+    TORCH_CHECK(masks.dim() == 3 && masks.size(0) == M, "occlusion_reduce: masks must be (V-1,h,w)");
+    h = masks.size(1), w = masks.size(2);
+  }
+  at::Tensor score = at::empty({M, nb}, mel.options());
+  at::Tensor pf = at::empty({want_per_frame ? M : 0, T, nb}, mel.options());
+  at::Tensor map = at::empty({nb, h, w}, mel.options());
+  ok(m2s_occlusion_reduce(mel.data_ptr<float>(), V, T, nm, n_bands ? bm.data_ptr<float>() : nullptr, n_bands,
+                          masks.defined() ? masks.data_ptr<float>() : nullptr, h, w, normalize ? 1 : 0,
+                          score.data_ptr<float>(), want_per_frame ? pf.data_ptr<float>() : nullptr,
+                          masks.defined() ? map.data_ptr<float>() : nullptr, S()),
+     "occlusion_reduce");
+  return {score, pf, map};
+}
+
 m2s_cam* Cm(int64_t h) {
   TORCH_CHECK(h != 0, "null cam handle");
   return reinterpret_cast<m2s_cam*>(h);
@@ -744,6 +795,9 @@ TORCH_LIBRARY(m2s, m) {
   m.def("hifigan_forward_chunk(int handle, Tensor mel, int[] lengths, int[] context, int[] hold, int hop) -> Tensor");
   m.def("preprocess_frames(Tensor frames) -> Tensor");
   m.def("preprocess_frames_resize(Tensor frames, int out_h, int out_w, int interp, int norm) -> Tensor");
+  m.def("preprocess_frames_masked(Tensor frames, Tensor masks, int out_h, int out_w, int interp, int norm) -> Tensor");
+  m.def("occlusion_reduce(Tensor mel, Tensor band_mask, Tensor? masks, bool normalize, bool want_per_frame)"
+        " -> (Tensor, Tensor, Tensor)");
   m.def("cam_backbone(int handle, Tensor frames) -> (Tensor, Tensor, Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_forward(Tensor x, Tensor[] weights) -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_train_backward(Tensor dy, Tensor x, Tensor[] weights, Tensor gates, Tensor cells, Tensor hid)"
@@ -780,6 +834,8 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("hifigan_forward_chunk", &hifigan_forward_chunk);
   m.impl("preprocess_frames", &preprocess_frames);
   m.impl("preprocess_frames_resize", &preprocess_frames_resize);
+  m.impl("preprocess_frames_masked", &preprocess_frames_masked);
+  m.impl("occlusion_reduce", &occlusion_reduce);
   m.impl("cam_backbone", &cam_backbone);
   m.impl("bilstm_train_forward", &bilstm_train_forward);
   m.impl("bilstm_train_backward", &bilstm_train_backward);

@@ -88,6 +88,9 @@ def lib():
         "m2s_mel_glue": (i, [fp, i, i, fp, fp, fp, fp, vp]),
         "m2s_preprocess_frames": (i, [fp, i, i, i, i, fp, vp]),
         "m2s_preprocess_frames_resize": (i, [fp, i, i, i, i, i, i, i, i, fp, vp]),
+        # occlusion: masks / mel / band_mask and every output are device pointers
+        "m2s_preprocess_frames_masked": (i, [fp, i, i, i, i, fp, i, i, i, i, i, fp, vp]),
+        "m2s_occlusion_reduce": (i, [fp, i, i, i, fp, i, fp, i, i, i, fp, fp, fp, vp]),
         "m2s_vocoder_create": (i, [C.POINTER(Tensor), i, C.POINTER(HifiganH), i, i, C.POINTER(vp)]),
         "m2s_vocoder_destroy": (None, [vp]),
         "m2s_vocoder_workspace_bytes": (sz, [vp, i, i]),
@@ -176,7 +179,8 @@ def exported_symbols() -> List[str]:
                         "m2s_acoustic_destroy", "m2s_acoustic_set_chunk", "m2s_acoustic_status",
                         "m2s_acoustic_set_lstm_spin_limit", "m2s_acoustic_set_ws_spin_limit", "m2s_acoustic_workspace_bytes",
                         "m2s_acoustic_forward", "m2s_effnet_forward", "m2s_effnet_probe", "m2s_bilstm_summerge",
-                        "m2s_mel_glue", "m2s_preprocess_frames", "m2s_preprocess_frames_resize", "m2s_vocoder_create",
+                        "m2s_mel_glue", "m2s_preprocess_frames", "m2s_preprocess_frames_resize", "m2s_preprocess_frames_masked",
+                        "m2s_occlusion_reduce", "m2s_vocoder_create",
                         "m2s_vocoder_destroy",
                         "m2s_vocoder_workspace_bytes", "m2s_vocoder_forward", "m2s_pipeline_workspace_bytes",
                         "m2s_pipeline_forward", "m2s_acoustic_ragged_workspace_bytes", "m2s_bilstm_summerge_ragged",

@@ -42,6 +42,9 @@ ANALYSIS_OPS = ("mel_spectrogram",)
 FRAME_OPS = ("preprocess_frames_resize",)
 FRAME_INTERPS = {"linear": 0, "area": 1}
 FRAME_NORMS = {"zscore": 0, "unit": 1}
+# occlusion (m2s/occlusion.py; include/m2s.h "occlusion"): the frame front end for M masked variants of every frame, and
+# the variants' mels -> per-band scores and a coverage-weighted map
+OCCLUSION_OPS = ("preprocess_frames_masked", "occlusion_reduce")
 # Grad-CAM engine (m2s/gradcam.py; handle = GradCam.handle): every band and target frame of a clip in one call, and
 # its stages (include/m2s.h "Grad-CAM engine")
 GRADCAM_OPS = ("gradcam", "gradcam_cotangents", "bilstm_train_backward_multi", "cam_heatmap")
@@ -215,6 +218,17 @@ def _register_fakes():
     @f("m2s::preprocess_frames_resize")
     def _pre_resize(frames, out_h, out_w, interp, norm):
         return frames.new_empty((frames.shape[0], out_h, out_w), dtype=torch.float32)
+
+    @f("m2s::preprocess_frames_masked")
+    def _pre_masked(frames, masks, out_h, out_w, interp, norm):
+        return frames.new_empty((masks.shape[0], frames.shape[0], out_h, out_w), dtype=torch.float32)
+
+    @f("m2s::occlusion_reduce")
+    def _occlusion(mel, band_mask, masks, normalize, want_per_frame):
+        m, t, nb = mel.shape[0] - 1, mel.shape[1], band_mask.shape[0] + 1
+        e = lambda *shape: mel.new_empty(shape, dtype=torch.float32)
+        h, w = (masks.shape[1], masks.shape[2]) if masks is not None else (0, 0)
+        return e(m, nb), e(m if want_per_frame else 0, t, nb), e(nb, h, w)
 
     @f("m2s::cam_backbone")
     def _cam(handle, frames):

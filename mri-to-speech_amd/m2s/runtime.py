@@ -320,6 +320,33 @@ def preprocess_frames(frames: torch.Tensor, size=None, interp: str = "linear", n
                                                 _ops.FRAME_NORMS[norm])
 
 
+def preprocess_frames_masked(frames: torch.Tensor, masks, size=None, interp: str = "linear",
+                             norm: str = "zscore") -> torch.Tensor:
+    """``preprocess_frames`` for M masked variants of every frame in one launch: uint8 frames (T,h,w[,3]) on the
+    device, ``masks`` (M,h,w) or one (h,w) mask (tensor or array, fp32) -> (M,T,H,W) fp32.  Variant m is the
+    reference's application, ``(frame.astype(float32) * mask).clip(0, 255).astype(uint8)`` on every channel
+    (scripts/mask_rtmri_video.py:96-98), followed by the front end of ``preprocess_frames(frames, size, interp,
+    norm)`` (``size`` None = the frames' own size); an all-ones mask gives that call's output bit for bit."""
+    if frames.dtype != torch.uint8:
+        raise N.M2SError(f"expected uint8 frames, got {frames.dtype}")
+    if frames.device.type != "cuda":
+        raise N.M2SError("preprocess_frames_masked runs on the HIP device; move the decoded frames there first")
+    if not (frames.dim() == 3 or (frames.dim() == 4 and frames.shape[-1] == 3)):
+        raise N.M2SError(f"expected (T,H,W) or (T,H,W,3) frames, got {tuple(frames.shape)}")
+    if interp not in _ops.FRAME_INTERPS:
+        raise N.M2SError(f"interp {interp!r} is none of {sorted(_ops.FRAME_INTERPS)}")
+    if norm not in _ops.FRAME_NORMS:
+        raise N.M2SError(f"norm {norm!r} is none of {sorted(_ops.FRAME_NORMS)}")
+    mk = torch.as_tensor(masks, dtype=torch.float32).to(frames.device)
+    if mk.dim() == 2:
+        mk = mk[None]
+    if mk.dim() != 3 or mk.shape[0] < 1 or tuple(mk.shape[1:]) != tuple(frames.shape[1:3]):
+        raise N.M2SError(f"expected masks (M,{frames.shape[1]},{frames.shape[2]}), got {tuple(mk.shape)}")
+    out_h, out_w = (int(frames.shape[1]), int(frames.shape[2])) if size is None else (int(size[0]), int(size[1]))
+    return _ops.load().preprocess_frames_masked(frames.contiguous(), mk.contiguous(), out_h, out_w,
+                                                _ops.FRAME_INTERPS[interp], _ops.FRAME_NORMS[norm])
+
+
 class Pipeline:
     """frames -> (mel_norm, mel_db, mel_log, wav) on one stream (run_mri_video_inference.py:218-242)."""
 
@@ -377,6 +404,66 @@ class Pipeline:
         db, ln = mel_glue(mn, self.mean, self.std)
         wav = self.voc.forward_ragged(ln, lengths)
         return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": wav}
+
+    def occlusion(self, frames_u8: torch.Tensor, masks, bands=None, size=None, interp: str = "linear",
+                  norm: str = "zscore", windowed=None, wav_variants=(), chunk: int = 64, normalize: bool = False):
+        """The masking experiment of one clip on the device (docs/rtmri_pipeline_notes.md step 5).
+
+        ``frames_u8`` uint8 (T,h,w[,3]) on the device, ``masks`` (M,h,w) fp32 (``m2s.occlusion``), ``bands`` {name:
+        mel-bin indices} (``m2s.gradcam.parse_band_arguments``) or None.  An all-ones mask is prepended as variant
+        0, the masked front end makes the (1 + M, T) batch at ``size`` (None = the frames' size), ONE engine call
+        runs it (whole-clip ``forward``; ``windowed`` = a window length for ``forward_windowed``, merge "latest"),
+        the mel glue gives mel_db and ``occlusion_reduce`` the scores in dB.  Returns dict: ``score`` (M,nb),
+        ``per_frame`` (M,T,nb), ``map`` (nb,h,w) (min-max scaled with ``normalize``), ``names`` (nb columns, the
+        last "all"), ``mel_db`` / ``mel_norm`` (T,n_mels) of the baseline, ``wavs`` {v: (T*hop,)} for the variants
+        ``wav_variants`` names (0 = baseline, m + 1 = masks[m]).  An engine call holds at most ``chunk`` variants,
+        variant 0 included in every one, so each difference is taken inside one batch.  Nothing is read back to
+        the host between the uint8 upload and the returned tensors."""
+        from .occlusion import band_matrix
+        if frames_u8.dim() not in (3, 4) or frames_u8.shape[0] < 1:
+            raise N.M2SError(f"expected one clip of uint8 frames (T,h,w[,3]), got {tuple(frames_u8.shape)}")
+        if frames_u8.device != self.device:
+            raise N.M2SError(f"frames on {frames_u8.device}, pipeline on {self.device}")
+        mk = torch.as_tensor(masks, dtype=torch.float32).to(self.device)
+        if mk.dim() == 2:
+            mk = mk[None]
+        M, T = int(mk.shape[0]), int(frames_u8.shape[0])
+        chunk = int(chunk)
+        if M < 1 or chunk < 2:
+            raise N.M2SError("occlusion needs at least one mask and a chunk of at least 2 variants")
+        wav_variants = [int(v) for v in wav_variants]
+        if any(not 0 <= v <= M for v in wav_variants):
+            raise N.M2SError(f"wav_variants outside 0..{M}")
+        bm, names = band_matrix(bands, self.ac.n_mels)
+        bm = bm.to(self.device)
+        ones = torch.ones_like(mk[:1])
+        red = _ops.load().occlusion_reduce
+        base, parts, wavs = None, [], {}
+        for lo in range(0, M, chunk - 1):
+            hi = min(M, lo + chunk - 1)
+            x = preprocess_frames_masked(frames_u8, torch.cat([ones, mk[lo:hi]]), size, interp, norm)  # (1+Mc,T,H,W)
+            B = int(x.shape[0])
+            if windowed is None:
+                mn = self.ac.forward(x)
+            else:
+                mn = self.ac.forward_windowed(x.reshape(B * T, *x.shape[2:]), [T] * B, int(windowed), "latest")
+                mn = mn.view(B, T, -1)
+            db, ln = mel_glue(mn, self.mean, self.std)
+            if base is None:
+                base = {"mel_db": db[0], "mel_norm": mn[0]}
+            for v in wav_variants:
+                row = 0 if v == 0 else v - lo
+                if (v == 0 and lo == 0) or (v > 0 and lo < v <= hi):
+                    wavs[v] = self.voc.forward(ln[row:row + 1], layout=1)[0, 0]
+            parts.append((db, lo, hi))
+        if len(parts) == 1:
+            score, pf, mp = red(parts[0][0], bm, mk, bool(normalize), True)
+        else:
+            # |(a - b) - 0| = |a - b| exactly: the chunks' own differences against a zero baseline give the bits of
+            # a per-chunk reduction, and the map sees every variant
+            diff = torch.cat([torch.zeros_like(parts[0][0][:1])] + [db[1:] - db[:1] for db, _, _ in parts])
+            score, pf, mp = red(diff, bm, mk, bool(normalize), True)
+        return {"score": score, "per_frame": pf, "map": mp, "names": names, "wavs": wavs, **base}
 
     def forward_pairs(self, frames, lengths=None, window: int = 4):
         """The acoustic model on every training pair of the clips (AcousticEngine.forward_pairs): normalised mel

@@ -46,12 +46,23 @@ class AcousticStream:
         """Feature rows held between calls (0 .. window - 1)."""
         return 0 if self._tail is None else int(self._tail.shape[0])
 
-    def push(self, frames: torch.Tensor) -> torch.Tensor:
+    def push(self, frames: torch.Tensor, masks=None) -> torch.Tensor:
         """frames (n,[1,]H,W) fp32 in [0, 1] on the engine's device, n >= 1 -> mel_norm (n, n_mels) for exactly
         these frames.  uint8 frames, (n,h,w) grey or (n,h,w,3) BGR at the scanner's size, go through the device
         front end first (``runtime.preprocess_frames`` to the ``size`` (H, W) / ``interp`` / ``norm`` given at
-        construction)."""
-        if frames.dtype == torch.uint8:
+        construction).  ``masks``: one (h,w) articulator mask (``m2s.occlusion``) applied to the uint8 frames on
+        the way (``runtime.preprocess_frames_masked``): the stream of the host-masked frames, bit for bit."""
+        if masks is not None:
+            from .runtime import preprocess_frames_masked
+            if frames.dtype != torch.uint8:
+                raise ValueError("masks apply to uint8 frames at the scanner's size")
+            mk = torch.as_tensor(masks, dtype=torch.float32)
+            if mk.dim() == 3 and mk.shape[0] == 1:
+                mk = mk[0]
+            if mk.dim() != 2:
+                raise ValueError(f"a stream takes one (h,w) mask, got {tuple(mk.shape)}")
+            frames = preprocess_frames_masked(frames, mk, self.size, self.interp, self.norm)[0]
+        elif frames.dtype == torch.uint8:
             from .runtime import preprocess_frames
             frames = preprocess_frames(frames, self.size, self.interp, self.norm)
         if frames.dim() == 4:
@@ -168,12 +179,12 @@ class SpeechStream:
         self.acoustic.reset()
         self.vocoder.reset()
 
-    def push(self, frames: torch.Tensor):
-        """frames (n,[1,]H,W) fp32, or uint8 (n,h,w[,3]) at the scanner's size (``AcousticStream.push``) -> dict:
-        mel_norm / mel_db / mel_log (n, n_mels) of the pushed frames, wav = the samples of the rows that became
-        final (``VocoderStream.push``)."""
+    def push(self, frames: torch.Tensor, masks=None):
+        """frames (n,[1,]H,W) fp32, or uint8 (n,h,w[,3]) at the scanner's size (``AcousticStream.push``; ``masks``:
+        one (h,w) articulator mask for uint8 frames) -> dict: mel_norm / mel_db / mel_log (n, n_mels) of the
+        pushed frames, wav = the samples of the rows that became final (``VocoderStream.push``)."""
         from .runtime import mel_glue
-        mn = self.acoustic.push(frames)
+        mn = self.acoustic.push(frames, masks)
         db, ln = mel_glue(mn, self.pipeline.mean, self.pipeline.std)
         return {"mel_norm": mn, "mel_db": db, "mel_log": ln, "wav": self.vocoder.push(ln)}
 
