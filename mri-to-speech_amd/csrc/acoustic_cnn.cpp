@@ -1,5 +1,7 @@
-// Execution plan of the acoustic model's CNN (tf_efficientnetv2_b2 backbone + GAP): which kernel runs for which
-// block, shape and switch, and the scratch of a pass.  The weights are packed by pack_acoustic.cpp (host code); the
+// The acoustic model's CNN (tf_efficientnetv2_b2 backbone + GAP): the scratch of a pass, and the launches of the
+// route table cnn_route() (cnn_route.hpp) plans for it.  Which kernel takes which block, shape and switch is decided
+// there, once per pass size; the effnet_* functions here execute one record each: a switch on the route, each case
+// the launcher call with its flops / bytes record.  The weights are packed by pack_acoustic.cpp (host code); the
 // constructor here reads the switches, packs, uploads the arena and resolves device pointers.
 #include <algorithm>
 
@@ -117,13 +119,14 @@ static ConvArgs conv2d_args(const Pass& p, const PConv& pc, const void* x, void*
   ConvArgs a = conv_args(pc);
   a.x = x;
   a.y = y;
-  a.IH = p.oh;
-  a.IW = p.ow;
-  a.OH = p.nh;
-  a.OW = p.nw;
-  a.pad_t = p.qt;
-  a.pad_l = p.ql;
-  a.M = p.nc * p.nh * p.nw;
+  const BlockRoute& r = *p.r;
+  a.IH = r.oh;
+  a.IW = r.ow;
+  a.OH = r.nh;
+  a.OW = r.nw;
+  a.pad_t = r.qt;
+  a.pad_l = r.ql;
+  a.M = p.nc * r.nh * r.nw;
   return a;
 }
 
@@ -139,172 +142,150 @@ void Acoustic::effnet_cn(EffPass<T>& p, size_t k) {
 template <typename T>
 void Acoustic::effnet_er(EffPass<T>& p, size_t k) {
   const Block& b = p_.blocks[k];
-  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  const BlockRoute& r = *p.r;
+  const int nc = p.nc, oh = r.oh, ow = r.ow, nh = r.nh, nw = r.nw, qt = r.qt, ql = r.ql;
   T *const cur = p.cur, *const nxt = p.nxt;
   hipStream_t s = p.s;
   const int co = chan_stride(b.cout);
   const double px = (double)nc * nh * nw, flops = 2.0 * px * b.mid * (9.0 * b.cin + b.cout);
-  // no fused kernel takes the block: conv_exp and conv_pwl as two convs, the expanded map in M
-  auto unfused = [&] {
-    ConvArgs a = conv2d_args(p, b.c1, cur, p.b.M);
-    a.act = ACT_SILU;
-    ConvArgs q = pw_args(b.c2, p.b.M, nxt, nc * nh * nw, nh * nw);
-    q.res = b.skip ? cur : nullptr;
-    if (kSplit<T> && sw_.er_s2_fused && b.stride == 2 && conv_gemm_er_supported(a, q, sw_.conv)) {
-      // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the expanded map stays in LDS (M is not touched);
-      // compulsory bytes = the block's input and output maps and both convs' weights
-      launch_conv_gemm_er(a, q, sw_.conv, s, flops,
-                          4.0 * ((double)nc * oh * ow * b.cin + px * b.cout + (9.0 * b.cin + b.cout) * b.mid));
-    } else {
-      run_conv<T>(a, b.c1, sw_.conv, s);
-      run_conv<T>(q, b.c2, sw_.conv, s);
-    }
-  };
   if constexpr (kSplit<T>) {
-    if (sw_.er_fused && b.er_sp && er_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
-      launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt, flops,
-                   4.0 * px * (b.c1.cs_in + co), s, sw_.er_mrg);
-    } else if (sw_.er_fused && b.ers_sp && b.stride == 2 && ers2_sp_supported(nh, nw, b.c1.cs_in, b.mid, co)) {
-      launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_wexp), b.c1.b,
-                     arena_.ptr(b.er_wpwl), b.c2.b, nxt, flops, 4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co), s);
-    } else {
-      unfused();
+    switch (r.er) {
+      case ErRoute::ErSp:
+        launch_er_sp(cur, nc, nh, nw, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_sp_w), b.c1.b, b.c2.b, nxt, flops,
+                     4.0 * px * (b.c1.cs_in + co), s, sw_.er_mrg);
+        return;
+      case ErRoute::Ers2Sp:
+        launch_ers2_sp(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.ptr(b.er_wexp), b.c1.b,
+                       arena_.ptr(b.er_wpwl), b.c2.b, nxt, flops, 4.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co), s);
+        return;
+      default:
+        break;
     }
   } else if constexpr (std::is_same<T, bf16_t>::value) {
-    uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
-    const Block* const nb = k + 1 < p_.blocks.size() ? &p_.blocks[k + 1] : nullptr;
-    // the next block is an e4m3 EdgeResidual (er8_fused): this block also stores its output as e4m3 bytes
-    // (er8w_fused, blocks.2.1/.2, always takes its e4m3 operand from the producer; M2S_ER8_X8=0 switches only
-    // er8_fused to its in-kernel conversion)
-    uint8_t* const er8_next = X8[0] && sw_.f8_er && nb && ((sw_.er8_x8 && nb->er8) || (sw_.f8_er2 && nb->er8w))
-                                  ? (cur8 == X8[0] ? X8[1] : X8[0])
-                                  : nullptr;
-    if (sw_.er_fused && sw_.f8_er && b.er8 && er8_fused_supported(nh, nw, b.cin, b.mid, b.cout)) {
-      uint8_t* y8 = cur8 && er8_next && er8_fused_supported(nh, nw, b.cout, b.mid, b.cout) ? er8_next : nullptr;
-      launch_er8_fused(cur, nc, nh, nw, arena_.at<uint8_t>(b.er8_wexp), arena_.at<float>(b.er8_sexp), b.c1.b,
-                       arena_.at<uint8_t>(b.er8_wpwl), arena_.at<float>(b.er8_spwl), b.c2.b, nxt, flops,
-                       2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, cur8, y8);
-      next8 = y8;
-    } else if (sw_.er_fused && b.er_frag && er_fused_supported(nh, nw, b.cin, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-      launch_er_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt,
-                      flops, 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
-    } else if (sw_.er_fused && sw_.f8_er && sw_.f8_er2 && b.er8w && cur8 &&
-               er8w_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout)) {
-      uint8_t* y8 = er8_next && nb->er8w ? er8_next : nullptr;
-      launch_er8w_fused(cur, cur8, nc, nh, nw, arena_.at<uint8_t>(b.er8w_w), arena_.at<float>(b.er8w_sexp), b.c1.b,
-                        arena_.at<float>(b.er8w_spwl), b.c2.b, nxt, y8, flops,
-                        // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
-                        px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
-      next8 = y8;
-    } else if (sw_.er_fused && b.er_frag && er2_fused_supported(nh, nw, b.c1.cs_in, b.mid, b.cout, b.c1.kp, b.c2.kp)) {
-      launch_er2_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, b.c2.b, nxt, flops,
-                       2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
-    } else if (sw_.er_fused && b.er_frag && b.stride == 2 &&
-               ers2_fused_supported(nh, nw, b.c1.cs_in, b.mid, co, b.c1.kp, b.c2.kp)) {
-      // fp8: an e4m3 copy of the output for an er8_fused next block (the copy is (N, OH, OW, cs_out) bytes)
-      uint8_t* y8 = er8_next && ((co == 32 && nb->er8 && er8_fused_supported(nh, nw, 32, 128, 32)) ||
-                                 (co == 64 && nb->er8w && er8w_fused_supported(nh, nw, 64, 224, b.cout)))
-                        ? er8_next
-                        : nullptr;
-      launch_ers2_fused(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.at<bf16_t>(b.er_wexp), b.c1.b,
-                        arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt, flops,
-                        2.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co) + (y8 ? px * 32 : 0.0), s, y8);
-      next8 = y8;
-    } else {
-      unfused();
+    // fp8: the e4m3 copy of the input a producer wrote, and the one of the output the next block reads
+    const uint8_t* const x8 = r.x8_in ? p.cur8 : nullptr;
+    uint8_t* const y8 = p.next8 = r.y8_out ? p.other8() : nullptr;
+    switch (r.er) {
+      case ErRoute::Er8:  // without x8 the kernel converts its input itself (M2S_ER8_X8=0)
+        launch_er8_fused(cur, nc, nh, nw, arena_.at<uint8_t>(b.er8_wexp), arena_.at<float>(b.er8_sexp), b.c1.b,
+                         arena_.at<uint8_t>(b.er8_wpwl), arena_.at<float>(b.er8_spwl), b.c2.b, nxt, flops,
+                         2.0 * px * (2.0 * b.cin) + (3.0 * 8 * 2048 + 2 * 2048), s, x8, y8);
+        return;
+      case ErRoute::Er:
+        launch_er_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt,
+                        flops, 2.0 * px * (2.0 * b.cin) + 2.0 * (9.0 * 32 * 128 + 128 * 32), s);
+        return;
+      case ErRoute::Er8w:
+        launch_er8w_fused(cur, x8, nc, nh, nw, arena_.at<uint8_t>(b.er8w_w), arena_.at<float>(b.er8w_sexp), b.c1.b,
+                          arena_.at<float>(b.er8w_spwl), b.c2.b, nxt, y8, flops,
+                          // e4m3 input + bf16 shortcut + bf16 output (+ its e4m3 copy) + the weights once
+                          px * (b.cin + 2.0 * b.cin + 2.0 * b.cout + (y8 ? b.cout : 0.0)) + (9.0 * b.cin + b.cout) * b.mid, s);
+        return;
+      case ErRoute::Er2:
+        launch_er2_fused(cur, nc, nh, nw, arena_.at<bf16_t>(b.er_wexp), b.c1.b, b.c2.b, nxt, flops,
+                         2.0 * px * (2.0 * b.c1.cs_in) + 2.0 * er2_stage_elems(), s);
+        return;
+      case ErRoute::Ers2:  // the copy is (N, OH, OW, cs_out) bytes
+        launch_ers2_fused(cur, nc, oh, ow, nh, nw, qt, ql, b.c1.cs_in, b.mid, co, arena_.at<bf16_t>(b.er_wexp), b.c1.b,
+                          arena_.at<bf16_t>(b.er_wpwl), b.c2.b, nxt, flops,
+                          2.0 * ((double)nc * oh * ow * b.c1.cs_in + px * co) + (y8 ? px * 32 : 0.0), s, y8);
+        return;
+      default:
+        break;
     }
+  }
+  // ErRoute::Unfused: conv_exp and conv_pwl as two convs, the expanded map in M
+  ConvArgs a = conv2d_args(p, b.c1, cur, p.b.M);
+  a.act = ACT_SILU;
+  ConvArgs q = pw_args(b.c2, p.b.M, nxt, nc * nh * nw, nh * nw);
+  q.res = b.skip ? cur : nullptr;
+  // conv_gemm_er_supported asks plan_ksplit and that the device, so this choice is not in the route table
+  if (kSplit<T> && sw_.er_s2_fused && b.stride == 2 && conv_gemm_er_supported(a, q, sw_.conv)) {
+    // split blocks.2.0: conv_pwl as conv_exp's epilogue GEMM, the expanded map stays in LDS (M is not touched);
+    // compulsory bytes = the block's input and output maps and both convs' weights
+    launch_conv_gemm_er(a, q, sw_.conv, s, flops,
+                        4.0 * ((double)nc * oh * ow * b.cin + px * b.cout + (9.0 * b.cin + b.cout) * b.mid));
   } else {
-    unfused();
+    run_conv<T>(a, b.c1, sw_.conv, s);
+    run_conv<T>(q, b.c2, sw_.conv, s);
   }
 }
 
 template <typename T>
 void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
   const Block& b = p_.blocks[k];
-  const int nc = p.nc, oh = p.oh, ow = p.ow, nh = p.nh, nw = p.nw, qt = p.qt, ql = p.ql;
+  const BlockRoute& r = *p.r;
+  const int nc = p.nc, oh = r.oh, ow = r.ow, nh = r.nh, nw = r.nw, qt = r.qt, ql = r.ql;
   T *const cur = p.cur, *const M = p.b.M, *const M2 = p.b.M2, *const se_mean = p.b.se_mean;
   float* const sums = p.b.sums;
-  uint8_t *&cur8 = p.cur8, *const *const X8 = p.b.X8;
   hipStream_t s = p.s;
   const int cs = chan_stride(b.mid);
-  constexpr bool SPL = kSplit<T>, FUSABLE = kNotF32<T>;
-  p.f8 = p.mid_f32 = false;
-  bool &f8 = p.f8, &mid_f32 = p.mid_f32;  // fp8 engine: e4m3 depthwise output -> the e4m3 SE GEMM
+  constexpr bool SPL = kSplit<T>;
+  const bool f8 = r.f8;  // fp8 engine: e4m3 depthwise output -> the e4m3 SE GEMM
   const float *const dw_w = arena_.at<float>(b.dw_w), *const dw_b = arena_.at<float>(b.dw_b);
   // bf16 feeds the fused kernel bf16 depthwise taps (dword halves), split fp32 the fp32 taps
   const void* wdw = SPL ? dw_w : arena_.ptr(b.dw_w2);
-  const bool big = nc >= sw_.irws_min;  // persistent ir_ws only where its one-image workgroups fill the chip
-  // the SE-gated conv_pwl runs on se_ws (effnet_ir_pwl): then ir_ws hands it the expanded map as plain fp32 rows
-  // (one 16-byte store per 4 channels, no split; se_ws gates the fp32 value before its one split)
-  const bool sews = p.sews = SPL && sw_.se_ws && se_ws_supported(nh * nw, cs, chan_stride(b.cout)) &&
-                             // se_ws runs one persistent workgroup per tile (256 rows; 128 at 8 x 8) up to one per CU:
-                             // below a full round of tiles the split-K conv_gemm SE GEMM fills the chip instead
-                             ceil_div(nc * nh * nw, nh * nw == 64 ? 128 : 256) >= sw_.sews_min_cus * device_cus();
-  // the persistent front half on an ih x iw input map (stride 2: down to nh x nw, passed with its pads)
+  const double Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
+  // the persistent front half on an ih x iw input map (stride 2: down to nh x nw, passed with its pads); where the
+  // SE-gated conv_pwl runs on se_ws it hands it the expanded map as plain fp32 rows (mid_f32: one 16-byte store per
+  // 4 channels, no split; se_ws gates the fp32 value before its one split)
   auto ir_ws = [&](int ih, int iw, int stride, int OH, int OW, int pad_t, int pad_l) {
-    const double Pi = (double)ih * iw, Po = (double)nh * nw;
+    const double Pi = (double)ih * iw;  // (stride 1: the block's nh x nw map)
     launch_ir_ws(cur, nc, ih, iw, b.c1.cs_in, b.c1.kp, cs, b.c1.w, b.c1.b, dw_w, dw_b, M2, se_mean,
                  2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
                  // algorithmic bytes on the real channel counts (split fp32: 4 B an element): compulsory = the
                  // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
                  // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
                  4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), stride,
-                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, mid_f32 = sews && sw_.irws_f32, sw_.irws_parts);
+                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, r.mid_f32, sw_.irws_parts);
   };
-  // fp8, the expand on e4m3: x8 of the block input (rows of P pixels an image), or null where the expand stays bf16
-  auto input8 = [&](bool f8x, int P) -> const uint8_t* {
-    if (!f8x) return nullptr;
-    if (!cur8) {  // no e4m3 producer wrote this input: convert it
-      cur8 = X8[0];
-      launch_rows_e4m3(cur, (long)nc * P, b.c1.cs_in, cur8, b.f8x_kp, s);
+  // fp8, the expand on e4m3: x8 of the block input, or null where the expand stays bf16
+  if (r.convert8) {  // no e4m3 producer wrote this input: convert it
+    p.cur8 = p.b.X8[0];
+    launch_rows_e4m3(cur, (long)nc * oh * ow, b.c1.cs_in, p.cur8, b.f8x_kp, s);
+  }
+  const uint8_t* const x8 = r.x8_in ? p.cur8 : nullptr;
+  const double Pi = (double)oh * ow;
+  switch (r.front) {
+    case IrFront::IrWs:
+      ir_ws(nh, nw, 1, 0, 0, 0, 0);
+      break;
+    case IrFront::Pwdw:
+      launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, nh, nw, cs, M2, se_mean, SPL,
+                     2.0 * nc * Po * b.mid * (b.c1.cin + 9), nc * Po * ((x8 ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid),
+                     s, f8, x8, x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
+      break;
+    case IrFront::IrWsS2:
+      ir_ws(oh, ow, 2, nh, nw, qt, ql);
+      break;
+    case IrFront::PwdwS2:
+      launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, oh, ow, nh, nw, qt, ql, cs, M2, se_mean,
+                        SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
+                        nc * ((x8 ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8, x8,
+                        x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
+      break;
+    case IrFront::S2Band: {
+      launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, dw_w, dw_b, nh, nw, qt, ql, cs, M2, sums, SPL,
+                       2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
+                       nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
+      ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * ir_s2band_bands(nh) + es * nc * cs, s);
+      launch_se_mean<T>(sums, nc, ir_s2band_bands(nh), cs, 1.0f / (float)(nh * nw), se_mean, s);
+      break;
     }
-    return cur8;
-  };
-  if (SPL && b.stride == 1 && sw_.ir_fused && sw_.ir_ws && big && ir_ws_supported(nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
-    ir_ws(nh, nw, 1, 0, 0, 0, 0);
-  } else if (FUSABLE && b.stride == 1 && sw_.ir_fused && ir_fused_supported(nh, nw, b.c1.cs_in, cs, SPL)) {
-    const double P = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-    f8 = b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-    // the expand on e4m3 (x8 of the block input)
-    const uint8_t* const x8 = input8(f8 && sw_.f8_expand && b.f8_pw && X8[0], nh * nw);
-    launch_ir_pwdw(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, nh, nw, cs, M2, se_mean, SPL,
-                   2.0 * nc * P * b.mid * (b.c1.cin + 9), nc * P * ((x8 ? 1.0 : es) * b.c1.cin + (f8 ? 1.0 : es) * b.mid),
-                   s, f8, x8, x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
-  } else if (SPL && b.stride == 2 && sw_.ir_fused && sw_.ir_ws && sw_.ir_ws_s2 && big &&
-             ir_ws_s2_supported(oh, ow, b.c1.cs_in, b.c1.kp, cs, nh, nw, qt, ql)) {
-    ir_ws(oh, ow, 2, nh, nw, qt, ql);
-  } else if (FUSABLE && b.stride == 2 && sw_.ir_fused && ir_fused_s2_supported(oh, ow, b.c1.cs_in, cs, SPL) &&
-             nh * nw <= 64) {
-    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-    // fp8 engines (blocks.5.0): e4m3 depthwise output for the e4m3 SE GEMM, the expand on e4m3 as for stride 1
-    f8 = sw_.f8_s2 && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-    const uint8_t* const x8 = input8(f8 && sw_.f8_expand && b.f8_pw && X8[0], oh * ow);
-    launch_ir_pwdw_s2(cur, nc, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, wdw, dw_b, oh, ow, nh, nw, qt, ql, cs, M2, se_mean,
-                      SPL, 2.0 * nc * b.mid * (Pi * b.c1.cin + Po * 9),
-                      nc * ((x8 ? 1.0 : es) * Pi * b.c1.cin + (f8 ? 1.0 : es) * Po * b.mid), s, f8, x8,
-                      x8 ? arena_.ptr(b.f8x_w) : nullptr, x8 ? arena_.at<float>(b.f8x_s) : nullptr, b.f8x_kp);
-  } else if (FUSABLE && b.stride == 2 && sw_.ir_fused && sw_.ir_s2band &&
-             ir_s2band_supported(oh, ow, nh, nw, b.c1.cs_in, b.c1.kp, cs)) {
-    const double Pi = (double)oh * ow, Po = (double)nh * nw, es = SPL ? 4.0 : 2.0;
-    // fp8 engines (blocks.3.0): e4m3 depthwise output for the e4m3 SE GEMM (the expand stays bf16)
-    f8 = sw_.f8_s2 && b.f8_pwl && se_gemm_f8_supported(nh * nw, cs, chan_stride(b.cout));
-    launch_ir_s2band(cur, nc, oh, ow, b.c1.cs_in, b.c1.kp, b.c1.w, b.c1.b, dw_w, dw_b, nh, nw, qt, ql, cs, M2, sums, SPL,
-                     2.0 * nc * b.mid * (Pi * 1.125 * b.c1.cin + Po * 9),
-                     nc * (es * Pi * b.c1.cs_in + (f8 ? 1.0 : es) * Po * cs), s, f8);
-    ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * ir_s2band_bands(nh) + es * nc * cs, s);
-    launch_se_mean<T>(sums, nc, ir_s2band_bands(nh), cs, 1.0f / (float)(nh * nw), se_mean, s);
-  } else {
-    ConvArgs e = pw_args(b.c1, cur, M, nc * oh * ow, oh * ow);
-    e.act = ACT_SILU;
-    run_conv<T>(e, b.c1, sw_.conv, s);
-    {
-      ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
-                   kStoreBytes<T> * (double)nc * (oh * ow + nh * nw) * b.mid, s);
-      launch_dwconv<T>(M, nc, oh, ow, nh, nw, b.stride, qt, ql, b.mid, cs, dw_w, dw_b, M2, sums, s);
-    }
-    {
-      ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * dw_pixel_blocks(nh, nw) + kStoreBytes<T> * (double)nc * cs, s);
-      launch_se_mean<T>(sums, nc, dw_pixel_blocks(nh, nw), cs, 1.0f / (float)(nh * nw), se_mean, s);
+    case IrFront::Unfused: {
+      ConvArgs e = pw_args(b.c1, cur, M, nc * oh * ow, oh * ow);
+      e.act = ACT_SILU;
+      run_conv<T>(e, b.c1, sw_.conv, s);
+      {
+        ProfScope ps(b.stride == 2 ? tname<T>("dwconv_kernel", ", 2") : tname<T>("dwconv_kernel", ", 1"), 2.0 * nc * nh * nw * b.mid * 9,
+                     kStoreBytes<T> * (double)nc * (oh * ow + nh * nw) * b.mid, s);
+        launch_dwconv<T>(M, nc, oh, ow, nh, nw, b.stride, qt, ql, b.mid, cs, dw_w, dw_b, M2, sums, s);
+      }
+      {
+        ProfScope ps(tname<T>("se_mean_kernel"), 0.0, 4.0 * nc * cs * dw_pixel_blocks(nh, nw) + kStoreBytes<T> * (double)nc * cs, s);
+        launch_se_mean<T>(sums, nc, dw_pixel_blocks(nh, nw), cs, 1.0f / (float)(nh * nw), se_mean, s);
+      }
+      break;
     }
   }
 }
@@ -315,67 +296,71 @@ void Acoustic::effnet_ir_se(EffPass<T>& p, size_t k) {
   const int nc = p.nc, cs = chan_stride(b.mid);
   T *const se_mean = p.b.se_mean, *const se_hid = p.b.se_hid, *const scale = p.b.scale;
   hipStream_t s = p.s;
-  if (kNotF32<T> && sw_.se_fused && se_excite_supported(b.rd, b.se2.kp, cs)) {
-    launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
-                     kSplit<T>, s);
-  } else {
-    ConvArgs r1 = pw_args(b.se1, se_mean, se_hid, nc, 1);  // conv_reduce + SiLU, all images of the chunk at once
-    r1.act = ACT_SILU;
-    run_conv<T>(r1, b.se1, sw_.conv, s);
-    ConvArgs r2 = pw_args(b.se2, se_hid, scale, nc, 1);  // conv_expand + sigmoid -> per-(image, channel) gates
-    r2.act = ACT_SIGMOID;
-    run_conv<T>(r2, b.se2, sw_.conv, s);
+  switch (p.r->se) {
+    case IrSe::Excite:
+      launch_se_excite(se_mean, nc, b.mid, cs, b.se1.w, b.se1.kp, b.se1.b, b.rd, b.se2.w, b.se2.kp, b.se2.b, scale,
+                       kSplit<T>, s);
+      break;
+    case IrSe::Convs: {
+      ConvArgs r1 = pw_args(b.se1, se_mean, se_hid, nc, 1);  // conv_reduce + SiLU, all images of the chunk at once
+      r1.act = ACT_SILU;
+      run_conv<T>(r1, b.se1, sw_.conv, s);
+      ConvArgs r2 = pw_args(b.se2, se_hid, scale, nc, 1);  // conv_expand + sigmoid -> per-(image, channel) gates
+      r2.act = ACT_SIGMOID;
+      run_conv<T>(r2, b.se2, sw_.conv, s);
+      break;
+    }
   }
 }
 
 template <typename T>
 void Acoustic::effnet_ir_pwl(EffPass<T>& p, size_t k) {
   const Block& b = p_.blocks[k];
-  const int nc = p.nc, nh = p.nh, nw = p.nw, cs = chan_stride(b.mid), co = chan_stride(b.cout);
+  const BlockRoute& r = *p.r;
+  const int nc = p.nc, nh = r.nh, nw = r.nw, cs = chan_stride(b.mid), co = chan_stride(b.cout);
   T *const cur = p.cur, *const nxt = p.nxt, *const M2 = p.b.M2, *const scale = p.b.scale;
-  uint8_t *const cur8 = p.cur8, *const *const X8 = p.b.X8, *&next8 = p.next8;
   hipStream_t s = p.s;
-  const bool f8 = p.f8, sews = p.sews, mid_f32 = p.mid_f32;
-  const Block* const nb = k + 1 < p_.blocks.size() ? &p_.blocks[k + 1] : nullptr;
-  // the next block takes an e4m3 expand operand (fp8 engines: stride-1 IR blocks, and the stride-2 one on
-  // ir_pwdw_s2, whose input map is this block's nh x nw output)
-  const bool want8 = X8[0] && sw_.f8_expand && nb && nb->f8_pw &&
-                     (nb->stride == 1 ||
-                      (sw_.f8_s2 && ir_fused_s2_supported(nh, nw, nb->c1.cs_in, chan_stride(nb->mid), false)));
   // fp8: an e4m3 copy of the output for the next block's expand, into the buffer cur8 does not hold
-  const int ld8 = want8 ? nb->f8x_kp : 0;
-  if (f8 && want8 && sw_.se_y8) next8 = cur8 == X8[0] ? X8[1] : X8[0];
+  uint8_t* const next8 = p.next8 = r.y8_out ? p.other8() : nullptr;
+  const int ld8 = r.ld8;
   const double rows = (double)nc * nh * nw;
   const void* const res = b.skip ? cur : nullptr;
-  if (f8 && sw_.se_ws && se_ws_f8_supported(nh * nw, cs, co)) {
-    launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
-                    arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
-                    rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
-                        (next8 ? rows * b.cout : 0.0),
-                    next8, ld8, ws_report(), sw_.sews_half);
-  } else if (f8) {
-    launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
+  switch (r.pwl) {
+    case IrPwl::SeWsF8:
+      launch_se_ws_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
                       arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
-                      rows * cs + 2.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + (double)b.f8_npad * b.f8_kp +
-                          2.0 * nc * cs + (next8 ? rows * ld8 : 0.0),
-                      next8, ld8);
-  } else if (sews) {
-    launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
-                 2.0 * rows * b.mid * b.cout,
-                 4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
-                 ws_report(), mid_f32, sw_.sews_rev, sw_.sews_half, sw_.se_ws_cfg);
-  } else if (kSplit<T> && sw_.se_sp && se_gemm_sp_supported(nh * nw, cs, co)) {
-    launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
-                      2.0 * rows * b.mid * b.cout,
-                      4.0 * rows * cs + 4.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
-                          4.0 * nc * cs,
-                      sw_.se_sp_waves);
-  } else {
-    ConvArgs q = pw_args(b.c2, M2, nxt, nc * nh * nw, nh * nw);
-    q.in_xform = IN_SE_SCALE;
-    q.in_scale = scale;
-    q.res = res;
-    run_conv<T>(q, b.c2, sw_.conv, s);
+                      rows * b.mid + 2.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + (double)b.cout * b.mid + 2.0 * nc * b.mid +
+                          (next8 ? rows * b.cout : 0.0),
+                      next8, ld8, ws_report(), sw_.sews_half);
+      break;
+    case IrPwl::SeGemmF8:
+      launch_se_gemm_f8(M2, nc * nh * nw, nh * nw, cs, arena_.ptr(b.f8_w), b.f8_kp, b.f8_npad, arena_.at<float>(b.f8_s),
+                        arena_.at<float>(b.f8_b), scale, res, nxt, co, s, 2.0 * rows * b.mid * b.cout,
+                        rows * cs + 2.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + (double)b.f8_npad * b.f8_kp +
+                            2.0 * nc * cs + (next8 ? rows * ld8 : 0.0),
+                        next8, ld8);
+      break;
+    case IrPwl::SeWs:
+      launch_se_ws(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
+                   2.0 * rows * b.mid * b.cout,
+                   4.0 * rows * b.mid + 4.0 * rows * b.cout * (b.skip ? 2.0 : 1.0) + 4.0 * b.cout * b.mid + 4.0 * nc * b.mid,
+                   ws_report(), r.mid_f32, sw_.sews_rev, sw_.sews_half, sw_.se_ws_cfg);
+      break;
+    case IrPwl::SeGemmSp:
+      launch_se_gemm_sp(M2, nc * nh * nw, nh * nw, cs, b.c2.w, b.c2.n_pad, b.c2.b, scale, res, nxt, co, s,
+                        2.0 * rows * b.mid * b.cout,
+                        4.0 * rows * cs + 4.0 * rows * (double)co * (b.skip ? 2.0 : 1.0) + 4.0 * b.c2.n_pad * b.c2.kp +
+                            4.0 * nc * cs,
+                        sw_.se_sp_waves);
+      break;
+    case IrPwl::Conv: {
+      ConvArgs q = pw_args(b.c2, M2, nxt, nc * nh * nw, nh * nw);
+      q.in_xform = IN_SE_SCALE;
+      q.in_scale = scale;
+      q.res = res;
+      run_conv<T>(q, b.c2, sw_.conv, s);
+      break;
+    }
   }
 }
 
@@ -388,29 +373,31 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
   p.b = effnet_bufs<T>(ws, N, H, W);
   p.s = s;
   T* const A = p.b.A;
-  int &oh = p.oh, &ow = p.ow;
   T*& cur = p.cur;
   const float *const stem_w = arena_.at<float>(p_.stem_w), *const stem_b = arena_.at<float>(p_.stem_b);
+  // the route table of a pass of nc frames: the full passes', and a shorter tail's
+  auto plan = [&](int nc) {
+    return cnn_route(p_.blocks, sw_, dtype_, nc, H, W, device_cus(), effnet_x8(H, W) != 0,
+                     probe && stop_after >= 0 && stop_after < 2);
+  };
+  const CnnRoute full = plan(nc_max), tail = N % nc_max ? plan(N % nc_max) : CnnRoute{};
   for (int n0 = 0; n0 < N; n0 += nc_max) {
     const int nc = std::min(nc_max, N - n0);
+    const CnnRoute& route = nc == nc_max ? full : tail;
     p.nc = nc;
     p.n0 = n0;
-    int pt, pl;
+    int oh, ow, pt, pl;
     same_pad(H, 3, 2, &oh, &pt);
     same_pad(W, 3, 2, &ow, &pl);
-    // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
     constexpr bool SPL = kSplit<T>;
-    const bool front = kNotF32<T> && sw_.stem_fused && !(probe && stop_after >= 0 && stop_after < 2) &&
-                       p_.blocks.size() >= 2 && p_.blocks[0].type == 0 && p_.blocks[0].stride == 1 && !p_.blocks[0].skip &&
-                       p_.blocks[0].cout == 16 && p_.blocks[0].c1.cs_in == 32 && p_.blocks[0].c1.kp == 288 &&
-                       p_.blocks[1].type == 0 && p_.blocks[1].stride == 1 && p_.blocks[1].skip && p_.blocks[1].cout == 16 &&
-                       p_.blocks[1].c1.cs_in == 16 && p_.blocks[1].c1.kp == 160 && chan_stride(16) == 16;
+    const bool front = route.stem == StemRoute::StemB0;
     cur = A;
     p.nxt = p.b.B;
     p.cur8 = nullptr;
     int cc = EFF_STEM;
     int bi = 0;
     if (front) {
+      // stem + blocks.0 (two 3x3 ConvBnAct at stride 1: 32 -> 16, 16 -> 16 + skip) in one kernel
       const double px = (double)nc * oh * ow;
       launch_stem_b0(frames + (size_t)n0 * H * W, nc, H, W, oh, ow, pt, pl, stem_w, stem_b, p_.blocks[0].c1.w,
                      p_.blocks[0].c1.b, p_.blocks[0].c1.kp, p_.blocks[1].c1.w, p_.blocks[1].c1.b, p_.blocks[1].c1.kp, A, SPL,
@@ -439,9 +426,10 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
     bool stopped = false;
     for (size_t k = front ? 2 : 0; k < p_.blocks.size(); ++k) {
       const Block& b = p_.blocks[k];
+      p.r = &route.blocks[k];
       p.next8 = nullptr;  // the e4m3 copy of this block's output, if the block wrote one
-      same_pad(oh, 3, b.stride, &p.nh, &p.qt);
-      same_pad(ow, 3, b.stride, &p.nw, &p.ql);
+      M2S_CHECK((!p.r->x8_in || p.r->convert8 || p.cur8) && (!(p.r->convert8 || p.r->y8_out) || p.b.X8[0]),
+                "effnet: an e4m3 hand-off of the route table has no buffer");
       if (b.type == 0) {
         effnet_cn(p, k);
       } else if (b.type == 1) {
@@ -453,8 +441,8 @@ void Acoustic::effnet_t(const float* frames, int N, int H, int W, float* feats, 
       }
       std::swap(cur, p.nxt);
       p.cur8 = p.next8;
-      oh = p.nh;
-      ow = p.nw;
+      oh = p.r->nh;
+      ow = p.r->nw;
       cc = b.cout;
       ++bi;
       if (tap(bi)) {

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/m2s.h"
+#include "cnn_route.hpp"
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
 
@@ -348,19 +349,19 @@ class Acoustic {
     LstmBufs d;  // the dense set at (B, Tmax)
   };
   RaggedLstmBufs ragged_lstm_bufs(Workspace& ws, const RaggedDims& d) const;
-  // One CNN pass at one block: frames n0 .. n0 + nc, input (oh x ow) and output (nh x nw, TF-SAME pads qt / ql)
-  // geometry.  A block function reads cur (fp8: and cur8, its e4m3 copy in X8[0] / X8[1] when one was written),
-  // writes nxt and sets next8 if it wrote an e4m3 copy; the loop then advances them.
+  // One CNN pass at one block: frames n0 .. n0 + nc and the block's record of the pass's route table (cnn_route.hpp:
+  // geometry, kernels, e4m3 hand-offs).  A block function reads cur (fp8: and cur8, its e4m3 copy in X8[0] / X8[1],
+  // where the record says the block reads one), writes nxt and, where the record says so, an e4m3 copy into next8;
+  // the loop then advances them.
   template <typename T>
   struct EffPass {
     EffBufs<T> b;
     hipStream_t s;
-    int nc, n0, oh, ow, nh, nw, qt, ql;
+    int nc, n0;
+    const BlockRoute* r;
     T *cur, *nxt;
     uint8_t *cur8, *next8;
-    // an InvertedResidual block's front half to its gated conv_pwl: e4m3 depthwise output -> the e4m3 SE GEMM; the
-    // conv_pwl runs on se_ws; ... and ir_ws handed it plain fp32 rows
-    bool f8, sews, mid_f32;
+    uint8_t* other8() const { return cur8 == b.X8[0] ? b.X8[1] : b.X8[0]; }  // the X8 buffer cur8 does not hold
   };
   // the recurrence for (B, T), shared by bilstm and bilstm_ragged: the kernel lstm_plan (lstm_route.hpp) chooses,
   // one record, one launch (or a launch per step).  seq_steps / rows: the recurrent steps and (b, t) rows that count
@@ -371,8 +372,8 @@ class Acoustic {
   template <typename T>
   void effnet_t(const float* frames, int N, int H, int W, float* feats, int stop_after, float* probe, int* probe_dims,
                 Workspace& ws, hipStream_t s);
-  // block k of a pass: ConvBnAct, EdgeResidual, and InvertedResidual as front half (expand + depthwise + SE mean),
-  // SE gates and the gated conv_pwl
+  // block k of a pass, executing p.r: ConvBnAct, EdgeResidual, and InvertedResidual as front half (expand +
+  // depthwise + SE mean), SE gates and the gated conv_pwl
   template <typename T>
   void effnet_cn(EffPass<T>& p, size_t k);
   template <typename T>
