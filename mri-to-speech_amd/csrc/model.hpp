@@ -9,6 +9,7 @@
 #include "cnn_route.hpp"
 #include "conv_igemm.hpp"
 #include "kernels.hpp"
+#include "voc_route.hpp"
 
 namespace m2s {
 
@@ -254,11 +255,10 @@ struct VocoderPlan {
   // reach in mel rows (interval propagation over the config): of the whole generator, and of what follows level l
   int back = 0, ahead = 0, lvl_back[8] = {}, lvl_ahead[8] = {};
 };
-// pack_vocoder.cpp: weight norm folded, every weight array staged in `ar`, and the reach.  f8_mrf64 / f8_mrf32:
-// fp8 engines also get e4m3 copies of the C = 64 / C = 32 resblock convs; pair128: split engines also get the
-// C = 128 resblock convs in conv1d_halo fragment order (the fused pair kernel at C = 128).  Host code only.
-void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f8_mrf64, bool f8_mrf32, Arena& ar,
-                  VocoderPlan& p, bool pair128 = false);
+// pack_vocoder.cpp: weight norm folded, every weight array staged in `ar`, and the reach.  wants =
+// voc_pack_wants(h, dtype, switches) (voc_route.hpp): the extra copies each resblock's convs get.  Host code only.
+void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, const VocPackWants& wants, Arena& ar,
+                  VocoderPlan& p);
 
 class Acoustic {
  public:
@@ -480,11 +480,18 @@ class Vocoder {
   ChunkPlan chunk_plan(const int* lengths, const int* context, const int* hold, int B, long rows) const;
   void ragged_run(const float* x, const float* mean, const float* std_, const int* lengths, int B, long N,
                   float* mel_db, float* mel_log, float* wav, Workspace& ws, hipStream_t s);
+  // the MRF of stage i on its route (route_.stages[i], voc_route.hpp): X -> S, L rows a clip
   template <typename T>
-  void mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out, hipStream_t s);
+  void mrf_stage_batched(int i, const GenBufs<T>& g, int B, int L, hipStream_t s);
+  template <typename T>
+  void mrf_stage_f8(int i, const GenBufs<T>& g, int B, int L, hipStream_t s);
+  template <typename T>
+  void mrf_stage_resblocks(int i, const GenBufs<T>& g, int B, int L, hipStream_t s);
   m2s_hifigan_h h_;
   int dtype_, device_;
   const Switches sw_;  // as Acoustic::sw_
+  const VocPackWants wants_;  // what pack_vocoder staged beside the conv_gemm rows
+  const VocRoute route_;      // every stage's MRF route and hand-offs, planned once (voc_route.hpp)
   Arena arena_;
   VocoderPlan p_;
   RaggedTable rtab_;

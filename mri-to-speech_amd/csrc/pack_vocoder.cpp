@@ -98,14 +98,13 @@ void generator_reach(const m2s_hifigan_h& h, VocoderPlan& p) {
 
 }  // namespace
 
-void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f8_mrf64, bool f8_mrf32, Arena& ar,
-                  VocoderPlan& p, bool pair128) {
-  M2S_CHECK(dtype == M2S_DT_F32 || dtype == M2S_DT_BF16 || dtype == M2S_DT_BF16X3 || dtype == M2S_DT_FP8, "bad dtype");
-  M2S_CHECK(h.resblock == 1 || h.resblock == 2, "resblock must be 1 or 2");
+void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, const VocPackWants& wants, Arena& ar,
+                  VocoderPlan& p) {
+  check_generator_config(h, dtype);
+  M2S_CHECK(wants.rbs.size() == (size_t)h.n_up * h.n_kernels, "pack_vocoder: one RbWants per resblock");
   // fp8 engines: e4m3 resblock (MRF) convs at C = 64 / 128 / 256; conv_pre, the upsamplers and the fused
   // C = 32 ResBlock1 kernel stay bf16
   const int io_dt = dtype == M2S_DT_FP8 ? M2S_DT_BF16 : dtype;
-  M2S_CHECK(h.n_up >= 1 && h.n_up <= 8 && h.n_kernels >= 1 && h.n_kernels <= 8, "bad generator config");
   const int c0 = h.upsample_initial_channel;
   {  // conv_pre: Conv1d(num_mels, c0, 7), no weight norm (models.py:94)
     const HostTensor& w = need(sd, "conv_pre.weight", {c0, h.num_mels, 7});
@@ -150,24 +149,11 @@ void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f
       RB rb;
       rb.k = h.resblock_kernel_sizes[j];
       const int kk = rb.k;
-      M2S_CHECK(h.n_dilations[j] >= 1 && h.n_dilations[j] <= 8, "resblock dilations: 1..8 per kernel size");
       for (int d = 0; d < h.n_dilations[j]; ++d) rb.dil.push_back(h.resblock_dilation_sizes[j][d]);
       const std::string q = "resblocks." + std::to_string(i * h.n_kernels + j);
       const bool fsplit = dtype == M2S_DT_BF16X3;
-      // which extra copies the resblock's convs get: the fused ResBlock1 kernel's (fp8 engines: the fused bf16
-      // ResBlock1 at C = 32 / 64, e4m3 convs at the wider stages)
-      const bool frag = (dtype == M2S_DT_BF16 || dtype == M2S_DT_FP8 || fsplit) && h.resblock == 1 &&
-                        rb1_fused_supported(co, chan_stride(co), kk, rb.dil.data(), (int)rb.dil.size(), kk * co, fsplit);
-      // fp8: the C = 128 / 256 (and, f8_mrf64, C = 64; f8_mrf32, C = 32) resblock convs as e4m3 bytes for conv1d_f8
-      // (K = 128 block-scaled MFMA; C = 64: two taps a K step)
-      const bool q8 = dtype == M2S_DT_FP8 && h.resblock == 1 &&
-                      ((co >= 128 && !frag) || (co == 64 && f8_mrf64) || (co == 32 && f8_mrf32)) &&
-                      conv1d_f8_supported(co, kk);
-      bool halo = fsplit && h.resblock == 1 && !frag;
-      // C = 64: the per-conv kernel and the fused pair share the fragments; C = 128 (pair128): the fused pair's only
-      for (size_t d = 0; d < rb.dil.size(); ++d)
-        halo = halo && (conv1d_halo_sp_supported(co, chan_stride(co), kk, rb.dil[d]) ||
-                        (pair128 && co == 128 && conv1d_halo_pair_supported(co, chan_stride(co), kk, rb.dil[d])));
+      // which extra copies the resblock's convs get (voc_route.hpp voc_pack_wants)
+      const RbWants& want = wants.rbs[(size_t)i * h.n_kernels + j];
       auto load = [&](const std::string& name) {
         return RbWeights{fold_wn(sd, name, {co, co, kk}), need(sd, name + ".bias", {co}).data, co, kk};
       };
@@ -198,15 +184,15 @@ void pack_vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, bool f
         rb.c1.push_back(dense(w1, rb.dil[d]));
         const RbWeights w2 = load(q + ".convs2." + std::to_string(d));
         rb.c2.push_back(dense(w2, 1));
-        if (frag) {
+        if (want.frag) {
           rb.f1_off.push_back(pack_rb1_frag(ar, w1, fsplit));
           rb.f2_off.push_back(pack_rb1_frag(ar, w2, fsplit));
         }
-        if (halo) {
+        if (want.halo) {
           rb.h1_off.push_back(pack_conv1d_halo(ar, w1));
           rb.h2_off.push_back(pack_conv1d_halo(ar, w2));
         }
-        if (q8) {
+        if (want.q8) {
           rb.q1.push_back(e4m3(w1));
           rb.q2.push_back(e4m3(w2));
         }

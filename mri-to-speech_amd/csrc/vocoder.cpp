@@ -1,5 +1,6 @@
-// Execution plan of the HiFi-GAN generator: which kernel runs for which stage, shape and switch, the scratch
-// layouts, and the ragged and chunk calls.  The weights are packed by pack_vocoder.cpp (host code); the constructor
+// Execution plan of the HiFi-GAN generator: the stage loop that executes the route table (voc_route.hpp: which
+// kernel runs for which stage, dtype and switch, planned once in the constructor), the scratch layouts, and the
+// ragged and chunk calls.  The weights are packed by pack_vocoder.cpp (host code); the constructor
 // here reads the switches, packs, uploads the arena and resolves device pointers.
 #include <algorithm>
 
@@ -9,12 +10,23 @@
 namespace m2s {
 
 Vocoder::Vocoder(const StateDict& sd, const m2s_hifigan_h& h, int dtype, int device)
-    : h_(h), dtype_(dtype), device_(device), sw_(Switches::from_env()) {
-  pack_vocoder(sd, h, dtype, sw_.f8_mrf64, sw_.f8_mrf32, arena_, p_, sw_.mrf_pair && sw_.mrf_pair128);
+    : h_(h), dtype_(dtype), device_(device), sw_(Switches::from_env()), wants_(voc_pack_wants(h, dtype, sw_)),
+      route_(voc_route(h, dtype, sw_, wants_)) {
+  pack_vocoder(sd, h, dtype, wants_, arena_, p_);
   arena_.upload(device);
   p_.pre.resolve(arena_);
   for (auto& u : p_.ups) u.resolve(arena_);
   for (auto& rb : p_.rbs) rb.resolve(arena_);
+  // a route whose kernel reads a copy the packer did not stage is refused here, once, not found at a launch
+  for (size_t q = 0; q < p_.rbs.size(); ++q) {
+    const StageRoute& r = route_.stages[q / h.n_kernels];
+    const RB& rb = p_.rbs[q];
+    const size_t np = rb.dil.size();
+    const bool fused = r.mrf == MrfRoute::PerResblock && r.rb[q % h.n_kernels] == RbRoute::Fused;
+    const bool halo = r.mrf == MrfRoute::Pair || r.mrf == MrfRoute::HaloBatched, f8 = r.mrf == MrfRoute::F8;
+    M2S_CHECK((!fused || rb.f2.size() == np) && (!halo || rb.h2.size() == np) && (!f8 || (dtype == M2S_DT_FP8 && rb.q2.size() == np)),
+              "vocoder: stage " + std::to_string(q / h.n_kernels) + " is routed to a kernel whose weights were not packed");
+  }
 }
 
 size_t Vocoder::act_elems(int B, int T) const {
@@ -252,27 +264,22 @@ static int mrf_accum(int j, int nk) { return j == 0 ? 0 : (j == nk - 1 ? 2 : 1);
 // operand fragments per K step; each c2 recovers its residual x from lrelu(x) (slope 0.1 is
 // invertible: x = a > 0 ? a : 10 a) and stores lrelu(xt + x) for the next pair's c1.  Per pair:
 // one launch for the c1 of every resblock, one for the c2 (the last pair's c2 accumulates the MRF
-// sum S = (x_0 + x_1 + ...) / num_kernels in resblock order, models.py:119-125, so it stays serial).
-// C = 64 (M2S_MRF_PAIR): one launch per pair instead, c1 and c2 fused with the tensor between them in LDS
+// sum S = (x_0 + x_1 + ...) / num_kernels in resblock order, models.py:119-125, so it stays serial); HaloBatched:
+// on conv1d_halo_sp, the input rows staged once per tile.  Pair: one launch per pair instead, c1 and c2 fused with the tensor between them in LDS
 // (conv1d_halo_pair_kernel); the last pairs chained in one launch where the pass fills the chip.
 template <typename T>
-void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int B, int L, bool act_out,
-                                hipStream_t s) {
+void Vocoder::mrf_stage_batched(int i, const GenBufs<T>& g, int B, int L, hipStream_t s) {
+  const StageRoute& r = route_.stages[i];
+  const T* const X = g.X;
+  T* const S = g.S;
+  T* const(*Bt)[3] = g.Bt;
+  const bool pair = r.mrf == MrfRoute::Pair, halo = r.mrf == MrfRoute::HaloBatched, act_out = r.mrf_act_out;
   const int nk = h_.n_kernels, np = (int)p_.rbs[i * nk].dil.size();
   int ord[CONV_BATCH];
   for (int j = 0; j < nk; ++j) ord[j] = j;
   std::sort(ord, ord + nk, [&](int x, int y) { return p_.rbs[i * nk + x].c1[0].kp > p_.rbs[i * nk + y].c1[0].kp; });
   auto a_in = [&](int j, int p) -> const T* { return p == 0 ? X : Bt[j][1 + ((p - 1) & 1)]; };  // lrelu(x) of pair p
-  bool halo = sw_.mrf_halo;  // input rows staged once per tile (conv1d_halo.hip) where the stage has the weights for it
-  for (int j = 0; j < nk; ++j) halo = halo && !p_.rbs[i * nk + j].h1.empty();
-  // each (c1, c2) pair in one launch (conv1d_halo_pair_kernel) where every pair of the stage is within its reach;
-  // a stage with one that is not runs as a whole on the launches below
   const int C = p_.ups[i].cout;
-  bool pair = halo && sw_.mrf_pair && kSplit<T> && (C == 64 || sw_.mrf_pair128);
-  for (int j = 0; j < nk && pair; ++j)
-    for (int d : p_.rbs[i * nk + j].dil) pair = pair && conv1d_halo_pair_supported(C, chan_stride(C), p_.rbs[i * nk + j].k, d);
-  for (int j = 0; j < nk; ++j)  // C = 128 has the fragments for the pair kernel only
-    for (int d : p_.rbs[i * nk + j].dil) halo = halo && conv1d_halo_sp_supported(C, chan_stride(C), p_.rbs[i * nk + j].k, d);
   if (pair) {
     const double es = kStoreBytes<T>, act = es * B * L * C;
     auto make = [&](int j, int p, double* fl, double* by) {
@@ -303,7 +310,7 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
     // the last pairs in resblock order: xs = sum_j resblock_j(x); S = xs / num_kernels, lrelu'd for an upsampler
     HaloPair hp[CONV_BATCH];
     double fl = 0.0, by = 0.0;
-    const bool chain = sw_.mrf_chain && conv1d_halo_pair_fills(C, B, L);
+    const bool chain = r.chain_wanted && conv1d_halo_pair_fills(C, B, L);
     for (int j = 0; j < nk; ++j) {
       double f = 0.0, b = 0.0;
       hp[j] = make(j, np - 1, &f, &b);
@@ -372,10 +379,107 @@ void Vocoder::mrf_stage_batched(int i, const T* X, T* S, T* const (*Bt)[3], int 
   }
 }
 
+// fp8 stage (C = 128 / 256; C = 64 / 32 by switch): e4m3 operands.  X8 = e4m3(lrelu(x)) once; per pair, c1 stores only
+// e4m3(lrelu(xt)) (its sole consumer is c2), c2 adds the bf16 residual and stores x (bf16, the next
+// residual) and e4m3(lrelu(x)) (the next c1's operand); the last c2 accumulates the MRF sum in S.
+template <typename T>
+void Vocoder::mrf_stage_f8(int i, const GenBufs<T>& g, int B, int L, hipStream_t s) {
+  const T* const X = g.X;
+  T *const *const Hb = g.Hb, *const T1 = g.T1, *const S = g.S, *const E8 = g.E8;
+  const int nk = h_.n_kernels, C = p_.ups[i].cout;
+  const long nel = (long)B * L * C;
+  uint8_t* X8 = reinterpret_cast<uint8_t*>(T1);  // T1 (2 bytes / element) holds X8 and T8
+  uint8_t* T8 = X8 + nel;
+  uint8_t* H8[2] = {reinterpret_cast<uint8_t*>(E8), reinterpret_cast<uint8_t*>(E8) + nel};
+  {
+    ProfScope ps("lrelu_e4m3_kernel", 0.0, 3.0 * nel, s);
+    launch_lrelu_e4m3(reinterpret_cast<const bf16_t*>(X), X8, nel, 0.1f, s);
+  }
+  const double rows = (double)B * L;
+  for (int j = 0; j < nk; ++j) {
+    const RB& rb = p_.rbs[i * nk + j];
+    const int np = (int)rb.dil.size();
+    const bf16_t* cur = reinterpret_cast<const bf16_t*>(X);
+    const uint8_t* cur8 = X8;
+    for (int p = 0; p < np; ++p) {
+      const double fl = 2.0 * rows * C * C * rb.k, wb = (double)C * C * rb.k;
+      launch_conv1d_f8(cur8, B, L, C, rb.k, rb.dil[p], rb.q1[p].wp, rb.q1[p].sp, rb.q1[p].bp, nullptr, nullptr, T8,
+                       0.1f, 0, 1.f, s, fl, 2.0 * nel + wb);
+      if (p == np - 1) {
+        const int accum = mrf_accum(j, nk);
+        launch_conv1d_f8(T8, B, L, C, rb.k, 1, rb.q2[p].wp, rb.q2[p].sp, rb.q2[p].bp, cur, S, nullptr, 0.f, accum,
+                         (float)nk, s, fl, nel * (1.0 + 2.0 + 2.0 + (accum ? 2.0 : 0.0)) + wb);
+      } else {
+        bf16_t* xo = reinterpret_cast<bf16_t*>(Hb[p & 1]);
+        launch_conv1d_f8(T8, B, L, C, rb.k, 1, rb.q2[p].wp, rb.q2[p].sp, rb.q2[p].bp, cur, xo, H8[p & 1], 0.1f, 0,
+                         1.f, s, fl, nel * (1.0 + 2.0 + 2.0 + 1.0) + wb);
+        cur = xo;
+        cur8 = H8[p & 1];
+      }
+    }
+  }
+}
+
+// Resblock by resblock: the fused ResBlock1 kernel (one launch for the resblock and its share of the MRF sum,
+// mrf_fused.hip) or run_conv pairs, as the route says for each
+template <typename T>
+void Vocoder::mrf_stage_resblocks(int i, const GenBufs<T>& g, int B, int L, hipStream_t s) {
+  constexpr bool SPL = kSplit<T>;
+  const StageRoute& r = route_.stages[i];
+  T *const X = g.X, *const *const Hb = g.Hb, *const T1 = g.T1, *const S = g.S;
+  const int nk = h_.n_kernels;
+  for (int j = 0; j < nk; ++j) {
+    const RB& rb = p_.rbs[i * nk + j];
+    const T* hcur = X;
+    const int np = (int)rb.dil.size();
+    const int accum = mrf_accum(j, nk);
+    if (r.rb[j] == RbRoute::Fused) {
+      const bf16_t* w1[8];
+      const bf16_t* w2[8];
+      const float* b1[8];
+      const float* b2[8];
+      double macs = 0.0;
+      for (int p = 0; p < np; ++p) {
+        w1[p] = rb.f1[p];
+        w2[p] = rb.f2[p];
+        b1[p] = rb.c1[p].b;
+        b2[p] = rb.c2[p].b;
+        macs += rb.c1[p].macs_per_row + rb.c2[p].macs_per_row;
+      }
+      const int C = rb.c1[0].cout;
+      const double rows = (double)B * L;
+      const double bytes = (SPL ? 2.0 : 1.0) * (2.0 * rows * C * (2 + (accum ? 1 : 0)) + 2.0 * np * 2 * C * C * rb.k);
+      launch_rb1_fused(reinterpret_cast<const bf16_t*>(X), reinterpret_cast<bf16_t*>(S), B, L, C, rb.k, np,
+                       rb.dil.data(), w1, b1, w2, b2, rb.c1[0].kp, accum, (float)nk, SPL, 2.0 * macs * rows, bytes,
+                       s);
+      continue;
+    }
+    for (int p = 0; p < np; ++p) {
+      const bool last = p == np - 1;
+      T* out = last ? S : Hb[p & 1];
+      ConvArgs c = conv1d_args(rb.c1[p], hcur, out, B, L);
+      c.in_xform = IN_LRELU;
+      c.in_slope = 0.1f;
+      if (h_.resblock == 1) {  // xt = c2(lrelu(c1(lrelu(x)))) ; x = xt + x
+        c.y = T1;
+        lrelu_out(c);
+        run_conv<T>(c, rb.c1[p], sw_.conv, s);
+        c = conv1d_args(rb.c2[p], T1, out, B, L);
+      }
+      c.res = hcur;
+      if (last) {  // xs = sum_j resblock_j(x); x = xs / num_kernels (models.py:119-125)
+        c.accum = accum;
+        c.accum_div = (float)nk;
+      }
+      run_conv<T>(c, h_.resblock == 1 ? rb.c2[p] : rb.c1[p], sw_.conv, s);
+      hcur = out;
+    }
+  }
+}
+
 template <typename T>
 void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab,
                     const Cone* cone) {
-  constexpr bool SPL = kSplit<T>;
   int Tc = Tn;              // rows per clip of the block as it stands (a cone shortens it between stages)
   const int* mtab = tab;    // ... and the clip table its tail masks read
   // ragged calls: zero the `halo` rows of S that the next consumer reads past the end of a short clip (they hold
@@ -387,10 +491,8 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     launch_ragged_tail_mask(S, mtab, B, L, L / Tc, halo, row_bytes, s);
   };
   const GenBufs<T> g = gen_bufs<T>(ws, B, Tn);
-  T *const X = g.X, *const *const Hb = g.Hb, *const T1 = g.T1, *const S = g.S, *const E8 = g.E8;
-  T* const(*Bt)[3] = g.Bt;
+  T *const *const Hb = g.Hb, *const S = g.S;
   int L = Tn;
-  const int nk = h_.n_kernels;
   // chunk calls: level l of the cone, on S as conv_pre (l = 0) or the MRF of stage l - 1 left it.  The kept rows go
   // to Hb[0], which nothing holds between an MRF stage and the next upsampler
   T* Sin = S;
@@ -408,139 +510,35 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     Tc = cone->keep[l];
     L = (int)keep;
   };
-  auto is_batched = [&](int i) {  // stage i's MRF runs as batched split launches (mrf_stage_batched)
-    const PConv& up = p_.ups[i];
-    const bool fused = kNotF32<T> && sw_.mrf_fused && !p_.rbs[i * nk].f1.empty();
-    bool b = SPL && sw_.mrf_batch && !fused && h_.resblock == 1 && nk <= CONV_BATCH && up.cout >= 32 && up.cout % 32 == 0;
-    for (int j = 0; j < nk; ++j) b = b && p_.rbs[i * nk + j].dil.size() == p_.rbs[i * nk].dil.size();
-    return b;
-  };
-  // split: the upsampler's input S may already hold lrelu(x) (slope 0.1, models.py:116-117), written so
-  // by its producer's epilogue (conv_pre, or a batched stage's final MRF accumulation), so the
-  // upsampler does not re-apply LeakyReLU to its operand fragments every K step
-  bool s_act = SPL;
   {
     StageTag tag("voc_pre");
     ConvArgs a = conv1d_args(p_.pre, mel_nlc, S, B, L);
-    if (s_act) lrelu_out(a);
+    if (route_.pre_act_out) lrelu_out(a);
     run_conv<T>(a, p_.pre, sw_.conv, s);
   }
   for (int i = 0; i < h_.n_up; ++i) {
     const PConv& up = p_.ups[i];
-    const bool batched = is_batched(i);
+    const StageRoute& r = route_.stages[i];
     crop(i);
     StageTag tag("ups_c" + std::to_string(up.cout));
     // a transposed conv of rate u and padding p reads floor((u - 1 + p) / u) input rows ahead of its output
     mask_tail(Sin, L, (up.ct_u - 1 + up.ct_pad) / up.ct_u, up.cs_in);
-    ConvArgs a = conv1d_args(up, Sin, X, B, L);  // M: rows per phase
+    ConvArgs a = conv1d_args(up, Sin, g.X, B, L);  // M: rows per phase
     a.L_out = L * up.ct_u;
-    if (!s_act) {
+    if (!r.in_act) {  // else the producer's epilogue stored lrelu(x) (slope 0.1, models.py:116-117; voc_route.hpp)
       a.in_xform = IN_LRELU;
       a.in_slope = 0.1f;
     }
-    if (batched) lrelu_out(a);  // X = lrelu(upsampled x): the MRF convs read it as is (mrf_stage_batched)
+    if (r.ups_act_out) lrelu_out(a);  // X = lrelu(upsampled x): a batched stage's convs read it as is
     run_conv<T>(a, up, sw_.conv, s);
     L *= up.ct_u;
     StageTag mrf("mrf_c" + std::to_string(up.cout));  // the stage's MRF (ResBlocks + sum), models.py:119-125
-    if (batched) {
-      // the last accumulation stores lrelu(S) when the next consumer is an upsampler (conv_post
-      // takes F.leaky_relu's default slope 0.01 on the raw S)
-      s_act = i + 1 < h_.n_up;
-      mrf_stage_batched<T>(i, X, S, Bt, B, L, s_act, s);
-      continue;
-    }
-    s_act = false;
-    // every resblock of the stage must carry e4m3 weights (q8 is decided per resblock: k <= 31)
-    bool stage_f8 = std::is_same<T, bf16_t>::value;
-    for (int j = 0; j < nk && stage_f8; ++j) {
-      const RB& rb = p_.rbs[i * nk + j];
-      stage_f8 = rb.q1.size() == rb.dil.size() && rb.q2.size() == rb.dil.size() && !rb.dil.empty();
-    }
-    if (stage_f8) {
-      // fp8 stage (C = 128 / 256): e4m3 operands.  X8 = e4m3(lrelu(x)) once; per pair, c1 stores only
-      // e4m3(lrelu(xt)) (its sole consumer is c2), c2 adds the bf16 residual and stores x (bf16, the next
-      // residual) and e4m3(lrelu(x)) (the next c1's operand); the last c2 accumulates the MRF sum in S.
-      const int C = up.cout;
-      const long nel = (long)B * L * C;
-      uint8_t* X8 = reinterpret_cast<uint8_t*>(T1);  // T1 (2 bytes / element) holds X8 and T8
-      uint8_t* T8 = X8 + nel;
-      uint8_t* H8[2] = {reinterpret_cast<uint8_t*>(E8), reinterpret_cast<uint8_t*>(E8) + nel};
-      {
-        ProfScope ps("lrelu_e4m3_kernel", 0.0, 3.0 * nel, s);
-        launch_lrelu_e4m3(reinterpret_cast<const bf16_t*>(X), X8, nel, 0.1f, s);
-      }
-      const double rows = (double)B * L;
-      for (int j = 0; j < nk; ++j) {
-        const RB& rb = p_.rbs[i * nk + j];
-        const int np = (int)rb.dil.size();
-        const bf16_t* cur = reinterpret_cast<const bf16_t*>(X);
-        const uint8_t* cur8 = X8;
-        for (int p = 0; p < np; ++p) {
-          const double fl = 2.0 * rows * C * C * rb.k, wb = (double)C * C * rb.k;
-          launch_conv1d_f8(cur8, B, L, C, rb.k, rb.dil[p], rb.q1[p].wp, rb.q1[p].sp, rb.q1[p].bp, nullptr, nullptr, T8,
-                           0.1f, 0, 1.f, s, fl, 2.0 * nel + wb);
-          if (p == np - 1) {
-            const int accum = mrf_accum(j, nk);
-            launch_conv1d_f8(T8, B, L, C, rb.k, 1, rb.q2[p].wp, rb.q2[p].sp, rb.q2[p].bp, cur, S, nullptr, 0.f, accum,
-                             (float)nk, s, fl, nel * (1.0 + 2.0 + 2.0 + (accum ? 2.0 : 0.0)) + wb);
-          } else {
-            bf16_t* xo = reinterpret_cast<bf16_t*>(Hb[p & 1]);
-            launch_conv1d_f8(T8, B, L, C, rb.k, 1, rb.q2[p].wp, rb.q2[p].sp, rb.q2[p].bp, cur, xo, H8[p & 1], 0.1f, 0,
-                             1.f, s, fl, nel * (1.0 + 2.0 + 2.0 + 1.0) + wb);
-            cur = xo;
-            cur8 = H8[p & 1];
-          }
-        }
-      }
-      continue;
-    }
-    for (int j = 0; j < nk; ++j) {
-      const RB& rb = p_.rbs[i * nk + j];
-      const T* hcur = X;
-      const int np = (int)rb.dil.size();
-      const int accum = mrf_accum(j, nk);
-      if (kNotF32<T> && sw_.mrf_fused && !rb.f1.empty()) {
-        // one launch for the whole resblock + MRF sum (mrf_fused.hip)
-        const bf16_t* w1[8];
-        const bf16_t* w2[8];
-        const float* b1[8];
-        const float* b2[8];
-        double macs = 0.0;
-        for (int p = 0; p < np; ++p) {
-          w1[p] = rb.f1[p];
-          w2[p] = rb.f2[p];
-          b1[p] = rb.c1[p].b;
-          b2[p] = rb.c2[p].b;
-          macs += rb.c1[p].macs_per_row + rb.c2[p].macs_per_row;
-        }
-        const int C = rb.c1[0].cout;
-        const double rows = (double)B * L;
-        const double bytes = (SPL ? 2.0 : 1.0) * (2.0 * rows * C * (2 + (accum ? 1 : 0)) + 2.0 * np * 2 * C * C * rb.k);
-        launch_rb1_fused(reinterpret_cast<const bf16_t*>(X), reinterpret_cast<bf16_t*>(S), B, L, C, rb.k, np,
-                         rb.dil.data(), w1, b1, w2, b2, rb.c1[0].kp, accum, (float)nk, SPL, 2.0 * macs * rows, bytes,
-                         s);
-        continue;
-      }
-      for (int p = 0; p < np; ++p) {
-        const bool last = p == np - 1;
-        T* out = last ? S : Hb[p & 1];
-        ConvArgs c = conv1d_args(rb.c1[p], hcur, out, B, L);
-        c.in_xform = IN_LRELU;
-        c.in_slope = 0.1f;
-        if (h_.resblock == 1) {  // xt = c2(lrelu(c1(lrelu(x)))) ; x = xt + x
-          c.y = T1;
-          lrelu_out(c);
-          run_conv<T>(c, rb.c1[p], sw_.conv, s);
-          c = conv1d_args(rb.c2[p], T1, out, B, L);
-        }
-        c.res = hcur;
-        if (last) {  // xs = sum_j resblock_j(x); x = xs / num_kernels (models.py:119-125)
-          c.accum = accum;
-          c.accum_div = (float)nk;
-        }
-        run_conv<T>(c, h_.resblock == 1 ? rb.c2[p] : rb.c1[p], sw_.conv, s);
-        hcur = out;
-      }
+    switch (r.mrf) {
+      case MrfRoute::Pair:
+      case MrfRoute::HaloBatched:
+      case MrfRoute::GemmBatched: mrf_stage_batched<T>(i, g, B, L, s); break;
+      case MrfRoute::F8: mrf_stage_f8<T>(i, g, B, L, s); break;
+      case MrfRoute::PerResblock: mrf_stage_resblocks<T>(i, g, B, L, s); break;
     }
   }
   StageTag tag("voc_post");

@@ -90,7 +90,10 @@ const char* const kDtype[4] = {"fp32", "bf16", "bf16x3", "fp8"};  // M2S_DT_F32 
 void vocoder(const std::string& name, const m2s::StateDict& sd, const m2s_hifigan_h& h, int dtype, bool mrf64, bool mrf32) {
   m2s::Arena ar;
   m2s::VocoderPlan p;
-  m2s::pack_vocoder(sd, h, dtype, mrf64, mrf32, ar, p);
+  m2s::Switches sw;  // the defaults, whatever the environment holds
+  sw.f8_mrf64 = mrf64;
+  sw.f8_mrf32 = mrf32;
+  m2s::pack_vocoder(sd, h, dtype, m2s::voc_pack_wants(h, dtype, sw), ar, p);
   report(name, ar);
 }
 

@@ -61,9 +61,12 @@ class Context:
         return self._engine(("ac", dtype, chunk),
                             lambda: self.rt.AcousticEngine(self.ac_sd, dtype=dtype, device=self.dev, **kw))
 
-    def vocoder(self, dtype):
-        return self._engine(("voc", dtype), lambda: self.rt.VocoderEngine(self.gen_sd, self.h, dtype=dtype,
-                                                                          device=self.dev))
+    def vocoder(self, dtype, h=None):  # h: another generator config than HIFIGAN_H, with weights of its own
+        if h is None:
+            return self._engine(("voc", dtype), lambda: self.rt.VocoderEngine(self.gen_sd, self.h, dtype=dtype,
+                                                                              device=self.dev))
+        return self._engine(("voc", dtype, json.dumps(h, sort_keys=True)), lambda: self.rt.VocoderEngine(
+            self.synth.synth_generator_state(12, h), h, dtype=dtype, device=self.dev))
 
     def pipeline(self, dtype):
         return self.rt.Pipeline(self.acoustic(dtype), self.vocoder(dtype), self.mean, self.std)
@@ -93,9 +96,9 @@ def _ac(method, dtype, *args, chunk=None, frames=None, feats=None, **kw):
     return make
 
 
-def _voc(method, dtype, mel, *args, **kw):
+def _voc(method, dtype, mel, *args, h=None, **kw):
     def make(ctx):
-        eng = ctx.vocoder(dtype)
+        eng = ctx.vocoder(dtype, h)
         x = ctx.mel(*mel) if isinstance(mel, tuple) else ctx.mel_rows(mel)
         return lambda: _as_list(getattr(eng, method)(x, *args, **kw))
     return make
@@ -130,6 +133,24 @@ def _as_list(out):
 
 DTYPES = ("fp32", "bf16", "bf16x3", "fp8")
 PERSISTENT = {"M2S_IRWS_MIN": "0", "M2S_SEWS_MIN": "0"}  # ir_ws / se_ws at any pass size
+
+# MRF routes of the generator (csrc/voc_route.hpp) that the voc_forward_* cases below do not take, each one forward of
+# 1 x 8 frames: (case suffix, dtype, switches, config or None for HIFIGAN_H).  tests/test_gpu_voc_route.py runs the same
+VOC_ROUTE_CASES = (
+    ("bf16_nofused", "bf16", {"M2S_MRF_FUSED": "0"}, None),
+    ("fp8_nofused", "fp8", {"M2S_MRF_FUSED": "0"}, None),
+    ("bf16x3_nobatch", "bf16x3", {"M2S_MRF_BATCH": "0"}, None),
+    ("bf16x3_nohalo_pair128", "bf16x3", {"M2S_MRF_HALO": "0", "M2S_MRF_PAIR128": "1"}, None),
+    ("fp8_mrf32", "fp8", {"M2S_F8_MRF32": "1"}, None),
+    ("fp8_mrf64_nofused", "fp8", {"M2S_F8_MRF64": "1", "M2S_MRF_FUSED": "0"}, None),
+    ("bf16x3_r2", "bf16x3", {}, "r2"),
+)
+
+
+def _h_r2():  # resblock "2": one conv per dilation (tests/test_pack_cpu.py H_R2)
+    from m2s.config import HIFIGAN_H
+    return dict(HIFIGAN_H, resblock="2", resblock_dilation_sizes=[[1, 3], [1, 3], [1, 3]])
+
 
 CASES = (
     # ---- acoustic
@@ -167,6 +188,9 @@ CASES = (
     # ---- pipeline
     + [Case(f"pipe_forward_1x3_{d}", {}, _pipe("forward", d, (1, 3))) for d in ("bf16x3", "fp32")]
     + [Case("pipe_forward_ragged_3_2", {}, _pipe("forward_ragged", "bf16x3", (1, 5), [3, 2]))]
+    # ---- vocoder, the other MRF routes (last: the golden's kernel and stage tables keep their order)
+    + [Case("voc_forward_1x8_" + name, env, _voc("forward", d, (1, 8), h=_h_r2() if h == "r2" else None))
+       for name, d, env, h in VOC_ROUTE_CASES]
 )
 
 
