@@ -237,7 +237,7 @@ void Acoustic::effnet_ir_front(EffPass<T>& p, size_t k) {
                  // block input, the split expand weights, taps and biases, the SE means out; the depthwise output
                  // map is a spill (written here only for the SE-gated conv_pwl to read back: m2s.h spill_bytes)
                  4.0 * nc * Pi * b.c1.cin + 4.0 * b.mid * (b.c1.cin + 11.0) + 4.0 * nc * b.mid, s, ws_report(), stride,
-                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, r.mid_f32, sw_.irws_parts);
+                 OH, OW, pad_t, pad_l, 4.0 * nc * Po * b.mid, r.mid_f32, sw_.irws_parts, sw_.irws_handoff);
   };
   // fp8, the expand on e4m3: x8 of the block input, or null where the expand stays bf16
   if (r.convert8) {  // no e4m3 producer wrote this input: convert it

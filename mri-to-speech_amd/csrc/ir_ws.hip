@@ -2,6 +2,9 @@
 // at 16x16 (blocks.5.0), as one persistent warp-specialised workgroup per CU:
 //   conv_pw (1x1 expand, 3-term MFMA) + bn1 + SiLU -> fp32 LDS tile -> conv_dw 3x3 + bn2 + SiLU -> HBM
 //   + the SE squeeze (per-image channel means).
+// The stride-1 16-wide maps of at most 16 rows run another form by default, one wave per (image, 16 channels) with
+// the depthwise on the expand's MFMA accumulators and no hand-offs: ir_ws_wave.hpp.  This file's own kernel is the
+// handed-off form, described next.
 // (timm InvertedResidual conv_pw/bn1/conv_dw/bn2/se.mean; mri_acoustic_model.py:28-34.)  Same outputs
 // as ir_pwdw_kernel<.., SP = 1> / ir_pwdw_s2_kernel<1> (ir_fused.hip), which launch one short workgroup per
 // (images, 32-channel slice) and spend most of their life waiting on a chain of loads and barriers.
@@ -111,11 +114,13 @@ __host__ __device__ inline WsLayout ws_layout(int H, int W, int cs_in, int cs_mi
 // same input bands; a band's output rows are its 4 stride-2 rows, one pixel a consumer lane (lanes of consumer
 // waves 0-3; waves 4-7 only take part in the hand-offs and the squeeze count).
 template <int W, int KS, int S>
-__global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
-    ir_ws_kernel(const bf16_t* __restrict__ x, int N, int H, int cs_mid, const bf16_t* __restrict__ wpw,
-                 const float* __restrict__ bpw, const float* __restrict__ wdw, const float* __restrict__ bdw,
-                 bf16_t* __restrict__ y, bf16_t* __restrict__ se_mean, unsigned long long* __restrict__ trace,
-                 unsigned spin_max, unsigned* __restrict__ err, int pad_t, int pad_l, int fm32, int n_full, int parts) {
+__device__ __forceinline__ void ir_ws_handoff(const bf16_t* __restrict__ x, int N, int H, int cs_mid,
+                                              const bf16_t* __restrict__ wpw, const float* __restrict__ bpw,
+                                              const float* __restrict__ wdw, const float* __restrict__ bdw,
+                                              bf16_t* __restrict__ y, bf16_t* __restrict__ se_mean,
+                                              unsigned long long* __restrict__ trace, unsigned spin_max,
+                                              unsigned* __restrict__ err, int pad_t, int pad_l, int fm32, int n_full,
+                                              int parts) {
   constexpr int par = IRWS_PAR;
   static_assert(S == 1 || (S == 2 && W == 16), "stride 2: the 16-wide maps");
   constexpr int OWS = W / S;                      // output row width
@@ -696,6 +701,32 @@ __global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
   }
 }
 
+#include "ir_ws_wave.hpp"
+
+// The kernel entries.  ir_ws_kernel<W, KS, S> is the default form of a shape: the per-wave form (ir_ws_wave.hpp) on
+// 16-wide stride-1 maps, the handed-off form above everywhere else.  ir_ws_kernel<W, KS, S, 1> is the handed-off
+// form where it is not the default (Switches::irws_handoff, and 16-wide maps of more than 16 rows).  Both take the
+// same arguments; the per-wave form has no waits, so it ignores trace / spin_max / err.
+constexpr bool ws_wave_shape(int W, int S) { return W == 16 && S == 1; }
+template <int W, int KS, int S>
+__global__ void __launch_bounds__(ws_wave_shape(W, S) ? 64 * WV_NW : 64 * (WS_NP + WS_NC), 1)
+    ir_ws_kernel(const bf16_t* __restrict__ x, int N, int H, int cs_mid, const bf16_t* __restrict__ wpw,
+                 const float* __restrict__ bpw, const float* __restrict__ wdw, const float* __restrict__ bdw,
+                 bf16_t* __restrict__ y, bf16_t* __restrict__ se_mean, unsigned long long* __restrict__ trace,
+                 unsigned spin_max, unsigned* __restrict__ err, int pad_t, int pad_l, int fm32, int n_full, int parts) {
+  if constexpr (ws_wave_shape(W, S)) ir_ws_wave16<KS>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, fm32, n_full, parts);
+  else ir_ws_handoff<W, KS, S>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, trace, spin_max, err, pad_t, pad_l, fm32, n_full, parts);
+}
+template <int W, int KS, int S, int HANDOFF>
+__global__ void __launch_bounds__(64 * (WS_NP + WS_NC), 1)
+    ir_ws_kernel(const bf16_t* __restrict__ x, int N, int H, int cs_mid, const bf16_t* __restrict__ wpw,
+                 const float* __restrict__ bpw, const float* __restrict__ wdw, const float* __restrict__ bdw,
+                 bf16_t* __restrict__ y, bf16_t* __restrict__ se_mean, unsigned long long* __restrict__ trace,
+                 unsigned spin_max, unsigned* __restrict__ err, int pad_t, int pad_l, int fm32, int n_full, int parts) {
+  static_assert(HANDOFF == 1, "the handed-off form");
+  ir_ws_handoff<W, KS, S>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, trace, spin_max, err, pad_t, pad_l, fm32, n_full, parts);
+}
+
 #ifdef IRWS_TRACE
 // Diagnostic build only (-DIRWS_TRACE, M2S_IR_WS_TRACE=1): per-phase s_memtime stamps of workgroup 0's
 // first producer and consumer waves for the first slices of each launch, printed to stderr.
@@ -765,7 +796,7 @@ bool ir_ws_supported(int H, int W, int cs_in, int kp, int cs_mid) {
 void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_mid, const void* wpw, const float* bpw,
                   const float* wdw, const float* bdw, void* y, void* se_mean, double flops, double bytes,
                   hipStream_t s, AsyncReport rep, int stride, int OH, int OW, int pad_t, int pad_l, double spill,
-                  bool fm32, int forced_parts) {
+                  bool fm32, int forced_parts, bool handoff) {
   M2S_CHECK(stride == 1 ? ir_ws_supported(H, W, cs_in, kp, cs_mid)
                         : stride == 2 && ir_ws_s2_supported(H, W, cs_in, kp, cs_mid, OH, OW, pad_t, pad_l),
             "ir_ws: unsupported shape");
@@ -799,19 +830,29 @@ void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_
   const bf16_t* wb = static_cast<const bf16_t*>(wpw);
   bf16_t* yb = static_cast<bf16_t*>(y);
   bf16_t* mb = static_cast<bf16_t*>(se_mean);
-#define M2S_IRWS(W_, KS_, S_, NAME_)                                                                    \
-  if (W == W_ && kp == KS_ * 32 && stride == S_) {                                                      \
-    allow_lds(reinterpret_cast<const void*>(&ir_ws_kernel<W_, KS_, S_>));                             \
+  // the per-wave form: 16-wide stride-1 maps of at most 16 rows (x in LDS whole: H x 16 positions x 512 B), unless
+  // the caller asks for the handed-off form (Switches::irws_handoff: A/B, tests)
+  const bool wave_form = ws_wave_shape(W, stride) && H <= 16 && !handoff;
+#define M2S_IRWS_GO(KERNEL_, THREADS_, LDS_, NAME_)                                                     \
+  {                                                                                                     \
+    allow_lds(reinterpret_cast<const void*>(&KERNEL_));                                                 \
     ProfScope ps(NAME_, flops, bytes, s, spill);                                                        \
-    hipLaunchKernelGGL((ir_ws_kernel<W_, KS_, S_>), grid, dim3(64 * (WS_NP + WS_NC)), L.total, s, xb, N, H, cs_mid, wb, \
-                       bpw, wdw, bdw, yb, mb, tr, rep.spin_max, rep.err, pad_t, pad_l, fm32 ? 1 : 0, n_full, parts); \
+    hipLaunchKernelGGL((KERNEL_), grid, dim3(THREADS_), LDS_, s, xb, N, H, cs_mid, wb, bpw, wdw, bdw, yb, mb, tr, \
+                       rep.spin_max, rep.err, pad_t, pad_l, fm32 ? 1 : 0, n_full, parts);               \
     M2S_IRWS_DUMP(NAME_)                                                                                \
     M2S_HIP(hipGetLastError());                                                                         \
     return;                                                                                             \
   }
   // (the launch log's names are rocprof's symbols, so the event and PMC records of a kernel share a key)
+  if (ws_wave_shape(W, stride) && kp == 128) {  // default: the per-wave form; the handed-off one under its own name
+    if (wave_form) M2S_IRWS_GO((ir_ws_kernel<16, 4, 1>), 64 * WV_NW, WV_NW * 1024 + H * W * 2 * ws_cpp(cs_in) * 16, "ir_ws_kernel<16, 4, 1>")
+    M2S_IRWS_GO((ir_ws_kernel<16, 4, 1, 1>), 64 * (WS_NP + WS_NC), L.total, "ir_ws_kernel<16, 4, 1, 1>")
+  }
+#define M2S_IRWS(W_, KS_, S_, NAME_)                                                                    \
+  if (W == W_ && kp == KS_ * 32 && stride == S_) M2S_IRWS_GO((ir_ws_kernel<W_, KS_, S_>), 64 * (WS_NP + WS_NC), L.total, NAME_)
   M2S_IRWS(8, 4, 1, "ir_ws_kernel<8, 4, 1>") M2S_IRWS(8, 7, 1, "ir_ws_kernel<8, 7, 1>")
-  M2S_IRWS(16, 4, 1, "ir_ws_kernel<16, 4, 1>") M2S_IRWS(16, 4, 2, "ir_ws_kernel<16, 4, 2>")
+  M2S_IRWS(16, 4, 2, "ir_ws_kernel<16, 4, 2>")
+#undef M2S_IRWS_GO
 #undef M2S_IRWS
 #undef M2S_IRWS_DUMP
   M2S_CHECK(false, "ir_ws: no variant for this shape");

@@ -37,6 +37,9 @@ struct Switches {
   // ---- CNN routes (acoustic_cnn.cpp) ----
   bool ir_fused = true;  // bf16: fused conv_pw + conv_dw + SE squeeze (env M2S_IR_FUSED=0 disables)
   bool ir_ws = true;     // split fp32: the persistent warp-specialised form of it (env M2S_IR_WS=0 disables)
+  // ... with the roles handed off through LDS on every shape (env M2S_IR_WS=handoff; A/B, tests), where the default
+  // runs 16-wide stride-1 maps per wave, the depthwise on the expand's accumulators (ir_ws_wave.hpp)
+  bool irws_handoff = false;
   bool ir_ws_s2 = true;  // ... also for the stride-2 block at 16x16 (env M2S_IR_WS_S2=0: ir_pwdw_s2)
   // ir_ws -> se_ws hand-off of the expanded map as plain fp32 rows instead of split pairs (env M2S_IRWS_F32=0: split)
   bool irws_f32 = true;
@@ -150,7 +153,8 @@ Switches Switches::from_env(Seen seen) {
   };
   // CNN routes (the last row: A/B and tests only)
   flag("M2S_IR_FUSED", w.ir_fused);
-  flag("M2S_IR_WS", w.ir_ws);
+  flag("M2S_IR_WS", w.ir_ws);  // one variable, three values: "0" off, "handoff" on in the handed-off form, else on
+  if (const char* e = std::getenv("M2S_IR_WS")) w.irws_handoff = std::strcmp(e, "handoff") == 0;
   flag("M2S_IR_WS_S2", w.ir_ws_s2);
   flag("M2S_IRWS_F32", w.irws_f32);
   flag("M2S_STEM_FUSED", w.stem_fused);
