@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import lstm_hard as LH  # tests/lstm_hard.py
 from m2s import synth
 from oracle import acoustic, effnet, gradcam
 
@@ -126,6 +127,36 @@ def test_bilstm_autograd_matches_torch(B, T):
         got = getattr(m.rnn.lstm, name).grad
         assert got is not None, name
         assert _rel(got.cpu(), p.grad) < 1e-5, name
+
+
+@pytest.mark.parametrize("kind", ["hard", "sat"])
+@pytest.mark.parametrize("B,T", LH.TRAIN_SHAPES)
+def test_bilstm_autograd_on_hard_weights(kind, B, T):
+    """The comparison above on weights where the backward has something to get wrong (tests/lstm_hard.py, DESIGN.md
+    §34): on synth weights no gate derivative is near zero and W_hh^T carries a fifth of dx.  "hard": forget gates
+    at 0.87, W_hh at gain one.  "sat": gates at exactly 0 and 1, whose derivatives are 0 and where a NaN would
+    come from 0 * inf.  Reference: torch autograd in float64 on the CPU; the bar stays 1e-5 relative to the largest
+    element (fp32 torch autograd is itself within 2e-6 of float64 here: test_lstm_hard_cpu.py)."""
+    sd = LH.state_of(kind)
+    m = _model(5).train()
+    m.load_state_dict(sd, strict=False)
+    m.rnn.dropout.train(False)
+    x, wy = LH.train_inputs(B, T)
+    xd = x.to(DEV).requires_grad_(True)
+    y = m.rnn(xd)
+    (y * wy.to(DEV)).sum().backward()
+    ref = LH.lstm_autograd(sd, x, wy)
+    errs = {"y": LH.rel(y.detach().cpu(), ref["y"]), "dx": LH.rel(xd.grad.cpu(), ref["dx"])}
+    for name in ref:
+        if name not in ("y", "dx"):
+            got = getattr(m.rnn.lstm, name).grad
+            assert got is not None, name
+            errs[name] = LH.rel(got.cpu(), ref[name])
+    print(f"bilstm autograd {kind} {B} x {T}: y {errs['y']:.1e}, dx {errs['dx']:.1e}, worst weight gradient "
+          f"{max(v for k, v in errs.items() if k not in ('y', 'dx')):.1e}")
+    assert torch.isfinite(y).all() and torch.isfinite(xd.grad).all()
+    for name, e in errs.items():
+        assert e < 1e-5, (name, e)
 
 
 def test_head_and_gap_autograd():

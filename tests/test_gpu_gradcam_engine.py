@@ -11,6 +11,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import lstm_hard as LH
 import ws_harness as H
 from m2s import _native, ops, synth
 from m2s.gradcam import GradCam
@@ -171,6 +172,37 @@ def test_backward_multi_matches_single_backward_and_torch(sd3, T):
         assert _bits(alone[0], dx_full[j]), f"cotangent {j} depends on its batch"
     shuffled = o.bilstm_train_backward_multi(full.flip(0).to(DEV), w, gates, cells)
     assert _bits(shuffled.flip(0), dx_full), "a cotangent's result depends on its position"
+
+
+@pytest.mark.parametrize("kind", ["hard", "sat"])
+@pytest.mark.parametrize("T", [9, 40])
+def test_train_forward_and_backward_multi_on_hard_weights(kind, T):
+    """bilstm_train_forward's y, gates, cells and hidden states against the float64 loop, and
+    bilstm_train_backward_multi with K = 3 (dense, all zeros, only t = 0) against float64 torch autograd and against
+    bilstm_train_backward, on the weights of tests/lstm_hard.py: "hard" has forget gates at 0.87 and
+    W_hh at gain one, "sat" gates at exactly 0 and 1 and cell states up to T.  1e-5 relative to the largest element,
+    the bar of the test above; everything finite, the zero cotangent exactly zero."""
+    o = ops.load()
+    sd = LH.state_of(kind)
+    w = [sd[n].to(DEV) for n in LSTM_NAMES]
+    x, _ = LH.train_inputs(1, T)
+    y, gates, cells, hid = o.bilstm_train_forward(x.to(DEV), w)
+    y64, st = LH.bilstm_f64(sd, x, state=True)
+    fwd = {"y": _rel(y.cpu(), y64), "gates": _rel(gates.cpu(), st["gates"]), "cells": _rel(cells.cpu(), st["c"]),
+           "hid": _rel(hid.cpu(), st["h"])}
+    dy = _cotangents(3, T, 640, seed=7 * T)
+    ref = LH.lstm_autograd(sd, x, dy[:, None])["dx"][:, 0]
+    dx = o.bilstm_train_backward_multi(dy.to(DEV), w, gates, cells)
+    assert dx.shape == (3, T, 208) and torch.isfinite(dx).all() and torch.isfinite(y).all()
+    assert torch.count_nonzero(dx[1]) == 0, "a zero cotangent must give exactly zero"
+    bwd = {}
+    for k in (0, 2):
+        single, _ = o.bilstm_train_backward(dy[k:k + 1].to(DEV), x.to(DEV), w, gates, cells, hid)
+        bwd[f"dx[{k}]"] = _rel(dx[k].cpu(), ref[k])
+        bwd[f"single[{k}]"] = _rel(single[0].cpu(), ref[k])
+    print(f"train {kind} 1 x {T}: " + ", ".join(f"{k} {v:.1e}" for k, v in {**fwd, **bwd}.items()))
+    for k, v in {**fwd, **bwd}.items():
+        assert v < 1e-5, (k, v)
 
 
 def test_backward_multi_launch_count(sd3):
