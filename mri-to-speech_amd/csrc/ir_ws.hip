@@ -2,9 +2,9 @@
 // at 16x16 (blocks.5.0), as one persistent warp-specialised workgroup per CU:
 //   conv_pw (1x1 expand, 3-term MFMA) + bn1 + SiLU -> fp32 LDS tile -> conv_dw 3x3 + bn2 + SiLU -> HBM
 //   + the SE squeeze (per-image channel means).
-// The stride-1 16-wide maps of at most 16 rows run another form by default, one wave per (image, 16 channels) with
-// the depthwise on the expand's MFMA accumulators and no hand-offs: ir_ws_wave.hpp.  This file's own kernel is the
-// handed-off form, described next.
+// The stride-1 16-wide maps of at most 16 rows and the stride-1 8 x 8 maps run another form by default, one wave per
+// (image, 16 channels) with the depthwise on the expand's MFMA accumulators and no hand-offs: ir_ws_wave.hpp.  This
+// file's own kernel is the handed-off form, described next.
 // (timm InvertedResidual conv_pw/bn1/conv_dw/bn2/se.mean; mri_acoustic_model.py:28-34.)  Same outputs
 // as ir_pwdw_kernel<.., SP = 1> / ir_pwdw_s2_kernel<1> (ir_fused.hip), which launch one short workgroup per
 // (images, 32-channel slice) and spend most of their life waiting on a chain of loads and barriers.
@@ -703,18 +703,26 @@ __device__ __forceinline__ void ir_ws_handoff(const bf16_t* __restrict__ x, int 
 
 #include "ir_ws_wave.hpp"
 
-// The kernel entries.  ir_ws_kernel<W, KS, S> is the default form of a shape: the per-wave form (ir_ws_wave.hpp) on
-// 16-wide stride-1 maps, the handed-off form above everywhere else.  ir_ws_kernel<W, KS, S, 1> is the handed-off
-// form where it is not the default (Switches::irws_handoff, and 16-wide maps of more than 16 rows).  Both take the
-// same arguments; the per-wave form has no waits, so it ignores trace / spin_max / err.
-constexpr bool ws_wave_shape(int W, int S) { return W == 16 && S == 1; }
+// The kernel entries.  ir_ws_kernel<W, KS, S> is the per-wave form (ir_ws_wave.hpp) on the stride-1 widths, 16 and 8,
+// and the handed-off form above on the stride-2 instance.  ir_ws_kernel<W, KS, S, 1> is the handed-off form of the
+// stride-1 widths: Switches::irws_handoff, 16-wide maps of more than 16 rows, 8-wide maps of other than 8 rows (whose
+// record keeps the plain name, launch_ir_ws).  Both take the same arguments; the per-wave form has no waits, so it
+// ignores trace / spin_max / err.
+constexpr bool ws_wave_shape(int W, int S) { return (W == 16 || W == 8) && S == 1; }
+// the heights of a per-wave width the form takes: at most 16 rows at 16 wide, exactly 8 at 8 wide
+constexpr bool ws_wave_height(int W, int H) { return W == 16 ? H <= 16 : H == 8; }
+// LDS of the per-wave form: the tap slots and the x rows (16 wide: the image's H rows; 8 wide: two images)
+inline int ws_wave_lds(int H, int W, int cs_in) {
+  return WV_NW * (W == 16 ? 1 : WV8_TS) * 1024 + (W == 16 ? H : 2 * H) * W * 2 * ws_cpp(cs_in) * 16;
+}
 template <int W, int KS, int S>
 __global__ void __launch_bounds__(ws_wave_shape(W, S) ? 64 * WV_NW : 64 * (WS_NP + WS_NC), 1)
     ir_ws_kernel(const bf16_t* __restrict__ x, int N, int H, int cs_mid, const bf16_t* __restrict__ wpw,
                  const float* __restrict__ bpw, const float* __restrict__ wdw, const float* __restrict__ bdw,
                  bf16_t* __restrict__ y, bf16_t* __restrict__ se_mean, unsigned long long* __restrict__ trace,
                  unsigned spin_max, unsigned* __restrict__ err, int pad_t, int pad_l, int fm32, int n_full, int parts) {
-  if constexpr (ws_wave_shape(W, S)) ir_ws_wave16<KS>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, fm32, n_full, parts);
+  if constexpr (ws_wave_shape(W, S) && W == 16) ir_ws_wave16<KS>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, fm32, n_full, parts);
+  else if constexpr (ws_wave_shape(W, S)) ir_ws_wave8<KS>(x, N, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, fm32, n_full, parts);
   else ir_ws_handoff<W, KS, S>(x, N, H, cs_mid, wpw, bpw, wdw, bdw, y, se_mean, trace, spin_max, err, pad_t, pad_l, fm32, n_full, parts);
 }
 template <int W, int KS, int S, int HANDOFF>
@@ -830,9 +838,11 @@ void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_
   const bf16_t* wb = static_cast<const bf16_t*>(wpw);
   bf16_t* yb = static_cast<bf16_t*>(y);
   bf16_t* mb = static_cast<bf16_t*>(se_mean);
-  // the per-wave form: 16-wide stride-1 maps of at most 16 rows (x in LDS whole: H x 16 positions x 512 B), unless
-  // the caller asks for the handed-off form (Switches::irws_handoff: A/B, tests)
-  const bool wave_form = ws_wave_shape(W, stride) && H <= 16 && !handoff;
+  // the per-wave form: 16-wide stride-1 maps of at most 16 rows (x in LDS whole: H x 16 positions x 512 B) and 8 x 8
+  // stride-1 maps (two images of 64 positions x 512 / 1024 B), unless the caller asks for the handed-off form
+  // (Switches::irws_handoff: A/B, tests)
+  const bool wave_form = ws_wave_shape(W, stride) && ws_wave_height(W, H) && !handoff;
+  const int wave_lds = ws_wave_lds(H, W, cs_in);
 #define M2S_IRWS_GO(KERNEL_, THREADS_, LDS_, NAME_)                                                     \
   {                                                                                                     \
     allow_lds(reinterpret_cast<const void*>(&KERNEL_));                                                 \
@@ -844,16 +854,24 @@ void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_
     return;                                                                                             \
   }
   // (the launch log's names are rocprof's symbols, so the event and PMC records of a kernel share a key)
-  if (ws_wave_shape(W, stride) && kp == 128) {  // default: the per-wave form; the handed-off one under its own name
-    if (wave_form) M2S_IRWS_GO((ir_ws_kernel<16, 4, 1>), 64 * WV_NW, WV_NW * 1024 + H * W * 2 * ws_cpp(cs_in) * 16, "ir_ws_kernel<16, 4, 1>")
+  if (W == 16 && stride == 1 && kp == 128) {  // default: the per-wave form; the handed-off one under its own name
+    if (wave_form) M2S_IRWS_GO((ir_ws_kernel<16, 4, 1>), 64 * WV_NW, wave_lds, "ir_ws_kernel<16, 4, 1>")
     M2S_IRWS_GO((ir_ws_kernel<16, 4, 1, 1>), 64 * (WS_NP + WS_NC), L.total, "ir_ws_kernel<16, 4, 1, 1>")
   }
-#define M2S_IRWS(W_, KS_, S_, NAME_)                                                                    \
-  if (W == W_ && kp == KS_ * 32 && stride == S_) M2S_IRWS_GO((ir_ws_kernel<W_, KS_, S_>), 64 * (WS_NP + WS_NC), L.total, NAME_)
-  M2S_IRWS(8, 4, 1, "ir_ws_kernel<8, 4, 1>") M2S_IRWS(8, 7, 1, "ir_ws_kernel<8, 7, 1>")
-  M2S_IRWS(16, 4, 2, "ir_ws_kernel<16, 4, 2>")
+  // 8 wide: the record's plain name is the default form of the shape, the per-wave form at 8 rows and the handed-off
+  // form at every other height.  The handed-off code is the four-parameter symbol at every height (one kernel has one
+  // register budget: 16 waves of 128 registers there, 8 of 256 in the per-wave form), so at H != 8 the record keeps
+  // the plain name over that symbol; at H == 8 under Switches::irws_handoff record and symbol agree
+#define M2S_IRWS8(KS_, NAME_)                                                                           \
+  if (W == 8 && kp == KS_ * 32 && stride == 1) {                                                        \
+    if (wave_form) M2S_IRWS_GO((ir_ws_kernel<8, KS_, 1>), 64 * WV_NW, wave_lds, NAME_)                  \
+    if (H == 8) M2S_IRWS_GO((ir_ws_kernel<8, KS_, 1, 1>), 64 * (WS_NP + WS_NC), L.total, "ir_ws_kernel<8, " #KS_ ", 1, 1>") \
+    M2S_IRWS_GO((ir_ws_kernel<8, KS_, 1, 1>), 64 * (WS_NP + WS_NC), L.total, NAME_)                     \
+  }
+  M2S_IRWS8(4, "ir_ws_kernel<8, 4, 1>") M2S_IRWS8(7, "ir_ws_kernel<8, 7, 1>")
+  if (W == 16 && kp == 128 && stride == 2) M2S_IRWS_GO((ir_ws_kernel<16, 4, 2>), 64 * (WS_NP + WS_NC), L.total, "ir_ws_kernel<16, 4, 2>")
 #undef M2S_IRWS_GO
-#undef M2S_IRWS
+#undef M2S_IRWS8
 #undef M2S_IRWS_DUMP
   M2S_CHECK(false, "ir_ws: no variant for this shape");
 }

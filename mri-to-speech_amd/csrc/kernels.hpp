@@ -116,9 +116,10 @@ void launch_ir_ws(const void* x, int N, int H, int W, int cs_in, int kp, int cs_
 // fm32: y is stored as plain fp32 rows [N * OH * OW][cs_mid] (for launch_se_ws(x_f32 = true)) instead of the
 // interleaved split layout: one 16-byte store per 4 channels, no split in the consumers.
 // parts > 0: that many slice ranges for the tail images instead of the launcher's rule (Switches::irws_parts).
-// 16-wide stride-1 maps of at most 16 rows run the per-wave form (ir_ws_wave.hpp: the depthwise on the expand's MFMA
-// accumulators, no hand-offs, so no waits and nothing to report through rep); handoff (Switches::irws_handoff): the
-// handed-off form there too, recorded as ir_ws_kernel<16, 4, 1, 1>.
+// 16-wide stride-1 maps of at most 16 rows and 8 x 8 stride-1 maps run the per-wave form (ir_ws_wave.hpp: the
+// depthwise on the expand's MFMA accumulators, no hand-offs, so no waits and nothing to report through rep); handoff
+// (Switches::irws_handoff): the handed-off form there too, recorded as ir_ws_kernel<16, 4, 1, 1> / <8, 4, 1, 1> /
+// <8, 7, 1, 1>.  8-wide maps of any other height run the handed-off form under the plain name in both settings.
 // Stride-2 IR front half on bands of 4 output rows (blocks.3.0: 32x32 -> 16x16), split fp32 or bf16: y =
 // the SE GEMM's operand (N, OH*OW, cs_mid; split: interleaved hi/lo), psum = squeeze partial sums
 // (N, OH / 4, cs_mid) for launch_se_mean.  wdw: fp32 tap-major [9][cs_mid].  (ir_s2band.hip)

@@ -38,7 +38,8 @@ struct Switches {
   bool ir_fused = true;  // bf16: fused conv_pw + conv_dw + SE squeeze (env M2S_IR_FUSED=0 disables)
   bool ir_ws = true;     // split fp32: the persistent warp-specialised form of it (env M2S_IR_WS=0 disables)
   // ... with the roles handed off through LDS on every shape (env M2S_IR_WS=handoff; A/B, tests), where the default
-  // runs 16-wide stride-1 maps per wave, the depthwise on the expand's accumulators (ir_ws_wave.hpp)
+  // runs 16-wide and 8 x 8 stride-1 maps per wave, the depthwise on the expand's accumulators (ir_ws_wave.hpp,
+  // DESIGN §33, §35)
   bool irws_handoff = false;
   bool ir_ws_s2 = true;  // ... also for the stride-2 block at 16x16 (env M2S_IR_WS_S2=0: ir_pwdw_s2)
   // ir_ws -> se_ws hand-off of the expanded map as plain fp32 rows instead of split pairs (env M2S_IRWS_F32=0: split)

@@ -9,6 +9,7 @@
 #   3. the source hash the files were made from (tools/evidence.py keys the JSON by it; bench.py only
 #      uses a traffic record of the tree it runs).
 # Usage: bash tools/gpu_evidence.sh <tag> [extra profile_step env, e.g. DTYPE=bf16]
+# C4FP8=0 leaves 2b out (a change that touches no fp8 kernel; tools/evidence.py then writes no c4fp8 record).
 set -o pipefail
 TAG=${1:-evidence}
 OUT=gpurun_out/$TAG
@@ -29,10 +30,11 @@ pmc() {  # pmc <dir> <counters...>
 && pmc write WRITE_SIZE \
 && pmc mfma SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
 && pmc valu SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES \
-&& DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc fetch8 FETCH_SIZE \
+&& { [ "${C4FP8:-1}" = 0 ] || {
+   DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc fetch8 FETCH_SIZE \
 && DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc write8 WRITE_SIZE \
 && DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc mfma8 SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE \
-&& DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc valu8 SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES
+&& DTYPE=fp8 CLIPS=8 FRAMES=1000 pmc valu8 SQ_INSTS_VALU SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_WAVE_CYCLES; }; }
 rc=$?
 cat "$OUT/src_sha.txt"; cut -c1-300 "$OUT/bench_under_rocprof.json"
 exit $rc
