@@ -252,6 +252,35 @@ int m2s_pipeline_forward(m2s_acoustic* m, m2s_vocoder* v, const float* frames, i
                          const float* mean, const float* std, float* mel_norm, float* mel_db, float* mel_log,
                          float* wav, void* ws, size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------------------------- graph capture ---- */
+/* The DENSE entry points may be called on a stream that is being captured into a HIP graph (hipStreamBeginCapture,
+ * torch.cuda.graph) and the graph replayed any number of times: m2s_acoustic_forward, m2s_effnet_forward,
+ * m2s_effnet_probe, m2s_bilstm_summerge, m2s_mel_glue, m2s_vocoder_forward, m2s_pipeline_forward, and the stateless
+ * calls that say so (m2s_preprocess_frames_resize, m2s_preprocess_frames_masked, m2s_occlusion_reduce,
+ * m2s_mel_metrics).  A replay computes, bit for bit, what the same engine's eager call computes on the buffers'
+ * contents at replay time (tests/test_gpu_graph.py).  The calls that stage a host table per call refuse a capturing
+ * stream with M2S_E_STATE before anything is launched: the ragged, windowed, pairs and chunk calls and
+ * m2s_gradcam_forward.  Profiling (m2s_prof_enable) records events around every launch: leave it off while capturing.
+ * What the caller owes:
+ *   - Inputs, outputs and the workspace are baked into the graph as addresses: all of them stay allocated, at those
+ *     addresses, for the graph's life, and no other work may use the workspace while a replay runs.
+ *   - One stream at a time per engine.  An acoustic engine owns the BiLSTM hand-off buffer and its error word (below),
+ *     so eager calls and replays on one engine must not overlap: order them on one stream or with events.
+ *   - Split K: small launches of the convolution GEMMs spread K over several workgroups through a scratch buffer the
+ *     library keeps per (device, stream) and grows on demand.  A capturing stream cannot allocate: it borrows the
+ *     device's largest such buffer, and where none is large enough the launch is recorded unsplit (correct, slower,
+ *     and rounded as the unsplit kernel rounds).  So run one eager call of the same shape on the device before the
+ *     capture if split K is to stay on, which the usual warm-up does.  The graph keeps the borrowed address: the
+ *     stream that owns the buffer must not run a larger call (which frees and regrows it) while the graph is alive,
+ *     nor split-K launches of its own while the graph replays on another stream.
+ *   - m2s_acoustic_status after synchronising, as for eager calls: a replay's hand-off timeout is reported the same way.
+ * The BiLSTM hand-off tags (lstm_small_kernel, lstm_x3g_kernel): eager calls continue one epoch count per engine and
+ * never clear the buffer.  A captured call records the zeroing of the buffer (a kernel node) and runs at epoch 0, so
+ * every replay RESTARTS the buffer's tags; the capture itself leaves the buffer alone and never lowers the engine's
+ * count (it raises it to T + 1 at least), so eager calls before, between and after captures and replays, in any
+ * order, never meet a tag they could take for their own (csrc/lstm_route.hpp lstm_epoch_rule).  The other
+ * recurrence kernels zero their sync words in the workspace per launch, under capture by a kernel node too. */
+
 /* ---------------------------------------------------------------- ragged batches ---- */
 /* Clips of different lengths in one call.  The data is PACKED: `lengths` is a HOST array of B integers, each
  * >= 1; N = sum(lengths); clip b owns rows off_b .. off_b + lengths[b] - 1 of every (N, ...) tensor, off = the

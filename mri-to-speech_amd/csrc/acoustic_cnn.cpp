@@ -27,6 +27,10 @@ Acoustic::Acoustic(const StateDict& sd, int n_mels, int hidden, int dtype, int d
   *err_host_ = 0;
   M2S_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&err_dev_), err_host_, 0));
   M2S_HIP(hipMalloc(&gsync_, lstm_sync_bytes(true)));
+  // zeroed here, not only by the first launch: where that launch is captured its memset is only recorded, and the
+  // eager launches after it continue the count without one (lstm_route.hpp lstm_epoch_rule)
+  M2S_HIP(hipMemset(gsync_, 0, lstm_sync_bytes(true)));
+  M2S_HIP(hipDeviceSynchronize());
 }
 
 Acoustic::~Acoustic() {

@@ -807,22 +807,46 @@ LstmKernel lstm_kernel(LstmRoute route, int inst) {
   return {};
 }
 
+// Zeroes a hand-off buffer ahead of its recurrence kernel on stream s.  Eager: a memset.  On a capturing stream: a
+// kernel node.  With a memset node there, the second replay of a graph went wrong in every route that zeroes its
+// sync words in the caller's workspace per launch: lstm_mid and lstm_x3 timed out in their waits and poisoned the
+// outputs, lstm_persistent returned finite, wrong rows (max |d y| 0.09, what a barrier count that was not restarted
+// gives).  The first replay, on words that were zero already, and every eager call were right, so the memset node
+// is not reliably done before the kernel behind it starts; whether it runs late or not at all was not established.
+// As a kernel node the zeroing is ordered like every other launch of the chain, and every replay gives the eager
+// bits (tests/test_gpu_graph.py, the bilstm_b8 / bilstm_b17 cases).
+//   bytes: a multiple of 16 at a 16-byte aligned address (every route's k.zero is a multiple of 256).
+__global__ void __launch_bounds__(256) lstm_zero_kernel(uint4* p, unsigned n16) {
+  for (unsigned i = blockIdx.x * 256u + threadIdx.x; i < n16; i += gridDim.x * 256u) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+
+void lstm_zero(void* sync, size_t bytes, bool capturing, hipStream_t s) {
+  if (!capturing) {
+    M2S_HIP(hipMemsetAsync(sync, 0, bytes, s));
+    return;
+  }
+  M2S_CHECK(bytes % 16 == 0 && bytes / 16 <= 0x7fffffffu && reinterpret_cast<uintptr_t>(sync) % 16 == 0,
+            "lstm_zero: the hand-off buffer is not a whole number of aligned 16-byte words");
+  const unsigned n16 = (unsigned)(bytes / 16);
+  hipLaunchKernelGGL(lstm_zero_kernel, dim3(std::min(1024u, (n16 + 255u) / 256u)), dim3(256), 0, s,
+                     static_cast<uint4*>(sync), n16);
+}
+
 // Epoch tags for the granule hand-off (lstm_small, lstm_x3g): a launch publishes tags ep + step + 1 and waits for
 // ep + step, its timeout mark is ep + 1, and the engine's counter advances by T + 1 a launch, so every tag and mark of
 // an older launch is below every tag this one waits for: no memset node before each call (a ~4.6 us launch of a
-// 30-frame pass's ~1 ms).  The buffer is zeroed (and the count restarted) on first use, near the wrap, and under
-// stream capture, whose replays would repeat one epoch.
+// 30-frame pass's ~1 ms).  The buffer is zeroed, and the launch runs at epoch 0, on first use, at the wrap guard and
+// under stream capture, whose replays repeat one epoch; a capture only RECORDS that zeroing, so it never lowers the
+// count (it raises it to T + 1 at least): the eager launches after it stay above the tags of the eager launches
+// before it and of every replay.  The rule is lstm_route.hpp's lstm_epoch_rule; this is its stream query and zeroing.
 unsigned lstm_epoch(void* sync, size_t bytes, int T, unsigned* epoch, hipStream_t s) {
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
   M2S_HIP(hipStreamIsCapturing(s, &cs));
-  if (!epoch || *epoch == 0 || cs != hipStreamCaptureStatusNone || *epoch > 0xF0000000u - (unsigned)T) {
-    M2S_HIP(hipMemsetAsync(sync, 0, bytes, s));
-    if (epoch) *epoch = (unsigned)T + 1u;
-    return 0u;
-  }
-  const unsigned e = *epoch;
-  *epoch += (unsigned)T + 1u;
-  return e;
+  const bool capturing = cs != hipStreamCaptureStatusNone;
+  const LstmEpoch e = lstm_epoch_rule(epoch ? *epoch : 0u, T, capturing);
+  if (e.zero) lstm_zero(sync, bytes, capturing, s);
+  if (epoch) *epoch = e.count;
+  return e.ep;
 }
 
 }  // namespace
@@ -848,10 +872,13 @@ void launch_lstm(const LstmPlan& p, const float* pre, const float* whh, float* h
   for (int b0 = 0; b0 < B; b0 += k.max_b) {  // c lives in LDS: at most max_b sequences per launch
     int nb = std::min(k.max_b, B - b0);
     unsigned ep = 0;
-    if (p.engine_sync)
+    if (p.engine_sync) {
       ep = lstm_epoch(sync, k.zero, T, epoch, s);
-    else
-      M2S_HIP(hipMemsetAsync(sync, 0, k.zero, s));
+    } else {
+      hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+      M2S_HIP(hipStreamIsCapturing(s, &cs));
+      lstm_zero(sync, k.zero, cs != hipStreamCaptureStatusNone, s);
+    }
     // each kernel's own parameter list
     void* a_bar[] = {&pre, &whh, &hs, &B, &b0, &nb, &T, &sync, &spin_max, &err_host};
     void* a_x3[] = {&pre, &whh, &hs, &B, &b0, &nb, &T, &sync, &hx, &spin_max, &err_host};

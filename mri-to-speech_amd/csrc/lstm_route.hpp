@@ -20,6 +20,38 @@ enum class LstmRoute { Step, Small, X3g, X3, Mid, Persistent };
 // lstm_epoch); the others in the call's workspace, zeroed per launch.
 constexpr bool lstm_engine_sync(LstmRoute r) { return r == LstmRoute::Small || r == LstmRoute::X3g; }
 
+// The epoch rule of that buffer (lstm_persistent.hip lstm_epoch queries the stream and issues the zeroing; the
+// decision is here, host arithmetic only, and tests/test_lstm_epoch_cpu.py enumerates it).  A launch with epoch ep
+// and length T publishes tag ep + s + 1 at step s < T - 1 into parity slot s & 1, accepts at step s >= 1 a granule of
+// slot (s - 1) & 1 whose tag EQUALS ep + s, and marks a timeout with ep + 1; steps 1 and 2 read slots the launch has
+// not rewritten yet.  So a launch that does not zero the buffer itself needs every tag and mark that an earlier eager
+// launch, or a replay of any graph captured so far, can have left to be below ep + 1:
+//  * eager: ep = count, count += T + 1 (an eager launch leaves tags <= ep + T - 1 and the mark ep + 1);
+//  * under capture the zeroing is only RECORDED: the launch is recorded with ep = 0 behind it, and every replay
+//    leaves tags <= T - 1 and the mark 1, whenever it runs.  The count is raised to at least T + 1 and never
+//    lowered, so later eager epochs stay above all of them (the buffer itself is untouched at capture time: a
+//    restart of the count there would let the next eager launch meet the tags of the eager launches before it);
+//  * first use (count 0; the constructor zeroes the buffer too): zero, ep = 0, count = T + 1;
+//  * at the wrap guard (count > LSTM_EPOCH_WRAP - T) the count cannot restart either, for a graph captured earlier
+//    may be replayed later: the launch zeroes the buffer, runs at ep = 0 and leaves the count where it is (its tags,
+//    <= T - 1, are below it).  From there on the long calls of an engine pay a memset node each (~4.6 us); the
+//    count gets there after 4.0e9 recurrence steps.
+constexpr unsigned LSTM_EPOCH_WRAP = 0xF0000000u;
+
+struct LstmEpoch {
+  unsigned ep;     // the launch's epoch
+  unsigned count;  // the engine's count after it
+  bool zero;       // zero the buffer (ahead of the launch, on its stream) first
+};
+
+inline LstmEpoch lstm_epoch_rule(unsigned count, int T, bool capturing) {
+  const unsigned span = (unsigned)T + 1u;
+  if (capturing) return {0u, count > span ? count : span, true};
+  if (count == 0) return {0u, span, true};
+  if (count > LSTM_EPOCH_WRAP - (unsigned)T) return {0u, count, true};
+  return {count, count + span, false};
+}
+
 // Switches' six lstm_* members (switches.hpp), as the engine read them
 struct LstmSwitches {
   bool persistent, mid, x3, x3g;

@@ -395,8 +395,8 @@ class Acoustic {
   unsigned* err_host_ = nullptr;  // pinned, host-mapped: set by a one-launch BiLSTM kernel whose hand-off wait timed out
   unsigned* err_dev_ = nullptr;
   // the hand-off buffer of the plans with engine_sync (lstm_route.hpp: lstm_small, lstm_x3g), lstm_sync_bytes(true),
-  // and its epoch count: zeroed on first use, near the tag wrap and under stream capture, else tags continue from
-  // the last call (lstm_persistent.hip lstm_epoch)
+  // and its epoch count: zeroed at creation, on first use, at the tag wrap guard and by every replay of a captured
+  // launch, else tags continue from the last call; a capture never lowers the count (lstm_route.hpp lstm_epoch_rule)
   void* gsync_ = nullptr;
   unsigned gsync_epoch_ = 0;
 };
