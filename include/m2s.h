@@ -244,6 +244,23 @@ size_t m2s_vocoder_workspace_bytes(const m2s_vocoder* v, int B, int T);
  * wav (B, T*prod(upsample_rates)) fp32. */
 int m2s_vocoder_forward(m2s_vocoder* v, const float* mel, int mel_layout, int B, int T, float* wav, void* ws,
                         size_t ws_bytes, void* stream);
+/* Debug tap (as m2s_effnet_probe for the CNN): the dense call m2s_vocoder_forward up to one stored tensor, which is
+ * then copied to `out` as fp32 (B, L, C), channel-last and dense; L (rows per clip) and C come back through the
+ * pointers (any of them may be NULL).  Taps: 0 = conv_pre's output (L = T, C = upsample_initial_channel);
+ * 2i + 1 = stage i's upsampler output; 2i + 2 = stage i's MRF output (the resblocks' mean), i = 0 .. n_up - 1
+ * (L = T * the rates up to stage i, C = upsample_initial_channel >> (i + 1)).
+ *   - The values are returned exactly as stored: in a bf16 / fp8 engine every float is a bf16 value, in a bf16x3
+ *     engine the sum of the two stored bf16 planes.
+ *   - Where the engine hands the tensor on as LeakyReLU(x) (slope 0.1; the split engine's batched stages and the
+ *     producers in front of them), the buffer is returned as it is and *lrelu is set to 1, else 0.  Nothing is
+ *     inverted.  m2s_vocoder_tap_info gives L, C and the flag without a launch.
+ *   - `ws` is that of m2s_vocoder_workspace_bytes(v, B, T); the launches are those of m2s_vocoder_forward up to the
+ *     tap plus one copy, and m2s_vocoder_forward itself is unchanged by the tap's existence.
+ *   - M2S_E_ARG before any launch: a null v, mel, out or ws, mel_layout other than 0 / 1, B or T < 1, tap outside
+ *     0 .. 2 n_up.  M2S_E_STATE if `stream` is capturing.  Dense calls only. */
+int m2s_vocoder_probe(m2s_vocoder* v, const float* mel, int mel_layout, int B, int T, int tap, float* out, int* L,
+                      int* C, int* lrelu, void* ws, size_t ws_bytes, void* stream);
+int m2s_vocoder_tap_info(const m2s_vocoder* v, int tap, int T, int* L, int* C, int* lrelu);
 
 /* ------------------------------------------------------------------- end to end ---- */
 size_t m2s_pipeline_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, int B, int T, int H, int W);

@@ -266,6 +266,32 @@ int m2s_vocoder_forward(m2s_vocoder* v, const float* mel, int mel_layout, int B,
   });
 }
 
+int m2s_vocoder_probe(m2s_vocoder* v, const float* mel, int mel_layout, int B, int T, int tap, float* out, int* L, int* C,
+                      int* lrelu, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(v && mel && out && ws, "null argument");
+    M2S_CHECK(mel_layout == 0 || mel_layout == 1, "mel_layout must be 0 or 1");
+    DeviceGuard g(v->impl.device());
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    M2S_HIP(hipStreamIsCapturing(S(stream), &cap));
+    if (cap != hipStreamCaptureStatusNone)
+      throw m2s::Error(M2S_E_STATE, "the vocoder probe is a test tap: it cannot be captured into a graph");
+    m2s::Workspace w(ws, ws_bytes);
+    v->impl.probe(mel, mel_layout, B, T, tap, out, L, C, lrelu, w, S(stream));
+  });
+}
+
+int m2s_vocoder_tap_info(const m2s_vocoder* v, int tap, int T, int* L, int* C, int* lrelu) {
+  return guarded([&] {
+    M2S_CHECK(v && T > 0, "bad argument");
+    int l = 0, c = 0;
+    const bool act = v->impl.tap_info(tap, T, &l, &c);
+    if (L) *L = l;
+    if (C) *C = c;
+    if (lrelu) *lrelu = act ? 1 : 0;
+  });
+}
+
 size_t m2s_pipeline_workspace_bytes(const m2s_acoustic* m, const m2s_vocoder* v, int B, int T, int H, int W) {
   return size_query(m && v, [&] {
     return m2s::Workspace::bytes([&](m2s::Workspace& w) { m2s::pipeline_bufs(w, m->impl, v->impl, B, T, H, W); });

@@ -409,6 +409,13 @@ class Vocoder {
   int num_mels() const { return h_.num_mels; }
   size_t workspace_bytes(int B, int T) const;
   void forward(const float* mel, int layout, int B, int T, float* wav, Workspace& ws, hipStream_t s);
+  // The stage tap (m2s_vocoder_probe): the dense call up to tap 0 (conv_pre's output), 2i + 1 (stage i's upsampler
+  // output, X) or 2i + 2 (stage i's MRF output, S), then that tensor as stored -> out fp32 (B, L, C) channel-last.
+  // *act: the buffer holds lrelu(x) (the route's hand-off flag of its producer); nothing is inverted
+  void probe(const float* mel, int layout, int B, int T, int tap, float* out, int* L, int* C, int* act, Workspace& ws,
+             hipStream_t s);
+  // L, C and that flag of a tap on T-row clips, from the config and the route table alone (M2S_E_ARG for a tap out of range)
+  bool tap_info(int tap, int T, int* L, int* C) const;
   // pipeline entry: mel glue (dB, ln-power; run_mri_video_inference.py:227-233) fused with the
   // cast to the channel-last vocoder input (ln_buf: rows x cs(num_mels) x 4 bytes), then the generator.
   void forward_from_norm(const float* mel_norm, const float* mean, const float* std_, int B, int T, float* mel_db,
@@ -445,9 +452,15 @@ class Vocoder {
     int drop[8], keep[8];
     const int* mask[8];
   };
+  struct Probe {  // a probe call's tap and destination; run_t fills in what it copied
+    int tap;
+    float* out;
+    int L, C;
+    bool act;
+  };
   template <typename T>
   void run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab = nullptr,
-             const Cone* cone = nullptr);
+             const Cone* cone = nullptr, Probe* probe = nullptr);
   template <typename T>
   struct GenBufs {  // the generator's activation buffers, act_elems(B, T) each
     T *X, *Hb[2], *T1, *S;

@@ -161,6 +161,26 @@ at::Tensor hifigan_forward(int64_t v, const at::Tensor& mel, int64_t layout, int
   return wav;
 }
 
+// mel as hifigan_forward -> the tensor stored at `tap` (include/m2s.h m2s_vocoder_probe), (B, channels, T*scale);
+// channels and scale are the caller's arithmetic on the config (the fake kernel's shape), checked against the engine's
+at::Tensor hifigan_features(int64_t v, const at::Tensor& mel, int64_t layout, int64_t tap, int64_t channels, int64_t scale) {
+  TORCH_CHECK(mel.dim() == 3 && (layout == 0 || layout == 1), "hifigan_features: mel must be 3-D, layout 0 or 1");
+  const Guard g(mel.device());
+  const at::Tensor x = f32_on_device(mel, "mel");
+  const int B = x.size(0), T = layout == 0 ? x.size(2) : x.size(1);
+  at::Tensor buf = at::empty({B, (int64_t)T * scale, channels}, x.options());
+  at::Tensor ws = workspace(m2s_vocoder_workspace_bytes(V(v), B, T), x);
+  int L = 0, C = 0;
+  // the sizes are the caller's: ask the engine for the tap's before anything is written
+  ok(m2s_vocoder_tap_info(V(v), (int)tap, T, &L, &C, nullptr), "hifigan_features");
+  TORCH_CHECK(L == (int64_t)T * scale && C == channels, "hifigan_features: tap ", tap, " is (B, ", C, ", ", L,
+              "), not (B, ", channels, ", ", (int64_t)T * scale, ")");
+  ok(m2s_vocoder_probe(V(v), x.data_ptr<float>(), (int)layout, B, T, (int)tap, buf.data_ptr<float>(), nullptr, nullptr,
+                       nullptr, ws.data_ptr(), ws.numel(), S()),
+     "hifigan_features");
+  return buf.permute({0, 2, 1}).contiguous();
+}
+
 // frames (B,T,H,W) -> (mel_norm, mel_db, mel_log (B,T,n_mels), wav (B,T*hop))
 std::tuple<at::Tensor, at::Tensor, at::Tensor, at::Tensor> pipeline_forward(int64_t h, int64_t v, const at::Tensor& frames,
                                                                             const at::Tensor& mean, const at::Tensor& std_,
@@ -777,6 +797,7 @@ TORCH_LIBRARY(m2s, m) {
   m.def("bilstm_summerge(int handle, Tensor feats, int hidden, int n_mels) -> (Tensor, Tensor)");
   m.def("mel_glue(Tensor mel_norm, Tensor mean, Tensor std) -> (Tensor, Tensor)");
   m.def("hifigan_forward(int handle, Tensor mel, int layout, int hop) -> Tensor");
+  m.def("hifigan_features(int handle, Tensor mel, int layout, int tap, int channels, int scale) -> Tensor");
   m.def("pipeline_forward(int acoustic, int vocoder, Tensor frames, Tensor mean, Tensor std, int n_mels, int hop)"
         " -> (Tensor, Tensor, Tensor, Tensor)");
   m.def("bilstm_summerge_ragged(int handle, Tensor feats, int[] lengths, int hidden, int n_mels) -> (Tensor, Tensor)");
@@ -821,6 +842,7 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("bilstm_summerge", &bilstm_summerge);
   m.impl("mel_glue", &mel_glue);
   m.impl("hifigan_forward", &hifigan_forward);
+  m.impl("hifigan_features", &hifigan_features);
   m.impl("pipeline_forward", &pipeline_forward);
   m.impl("bilstm_summerge_ragged", &bilstm_summerge_ragged);
   m.impl("acoustic_forward_ragged", &acoustic_forward_ragged);

@@ -79,6 +79,35 @@ void Vocoder::forward(const float* mel, int layout, int B, int T, float* wav, Wo
   });
 }
 
+bool Vocoder::tap_info(int tap, int T, int* L, int* C) const {
+  M2S_CHECK(tap >= 0 && tap <= 2 * h_.n_up, "vocoder probe: tap must be 0 .. 2 * n_up");
+  *L = T;
+  *C = h_.upsample_initial_channel;
+  if (tap == 0) return route_.pre_act_out;
+  const int i = (tap - 1) / 2;
+  for (int q = 0; q <= i; ++q) *L *= h_.upsample_rates[q];
+  *C = h_.upsample_initial_channel >> (i + 1);
+  const StageRoute& r = route_.stages[i];
+  return tap % 2 ? r.ups_act_out : r.mrf_act_out;
+}
+
+void Vocoder::probe(const float* mel, int layout, int B, int T, int tap, float* out, int* L, int* C, int* act,
+                    Workspace& ws, hipStream_t s) {
+  M2S_CHECK(B > 0 && T > 0, "vocoder: empty input");
+  int l = 0, c = 0;
+  tap_info(tap, T, &l, &c);  // refuses a tap out of range
+  void* mn = mel_in(ws, B, T);
+  Probe pr{tap, out, 0, 0, false};
+  dispatch_act(dtype_, [&](auto t) {
+    using A = typename decltype(t)::type;
+    launch_mel_to_nlc<A>(mel, B, h_.num_mels, T, layout, static_cast<A*>(mn), chan_stride(h_.num_mels), s);
+    run_t<A>(mn, B, T, nullptr, ws, s, nullptr, nullptr, &pr);
+  });
+  if (L) *L = pr.L;
+  if (C) *C = pr.C;
+  if (act) *act = pr.act ? 1 : 0;
+}
+
 void Vocoder::forward_from_norm(const float* mel_norm, const float* mean, const float* std_, int B, int T,
                                 float* mel_db, float* mel_log, void* ln_buf, float* wav, Workspace& ws, hipStream_t s) {
   M2S_CHECK(B > 0 && T > 0, "vocoder: empty input");
@@ -479,7 +508,7 @@ void Vocoder::mrf_stage_resblocks(int i, const GenBufs<T>& g, int B, int L, hipS
 
 template <typename T>
 void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& ws, hipStream_t s, const int* tab,
-                    const Cone* cone) {
+                    const Cone* cone, Probe* probe) {
   int Tc = Tn;              // rows per clip of the block as it stands (a cone shortens it between stages)
   const int* mtab = tab;    // ... and the clip table its tail masks read
   // ragged calls: zero the `halo` rows of S that the next consumer reads past the end of a short clip (they hold
@@ -493,6 +522,17 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
   const GenBufs<T> g = gen_bufs<T>(ws, B, Tn);
   T *const *const Hb = g.Hb, *const S = g.S;
   int L = Tn;
+  // probe calls: the run ends behind the tapped tensor, copied out as stored (fp32, rows x C), lrelu'd or not as the
+  // route's hand-off flag says
+  auto tapped = [&](int tap, const T* buf, int C, bool act) {
+    if (!probe || probe->tap != tap) return false;
+    StageTag tag("probe");
+    launch_unpad<T>(buf, (long)B * L, C, chan_stride(C), probe->out, s);
+    probe->L = L;
+    probe->C = C;
+    probe->act = act;
+    return true;
+  };
   // chunk calls: level l of the cone, on S as conv_pre (l = 0) or the MRF of stage l - 1 left it.  The kept rows go
   // to Hb[0], which nothing holds between an MRF stage and the next upsampler
   T* Sin = S;
@@ -516,6 +556,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     if (route_.pre_act_out) lrelu_out(a);
     run_conv<T>(a, p_.pre, sw_.conv, s);
   }
+  if (tapped(0, S, p_.pre.cout, route_.pre_act_out)) return;
   for (int i = 0; i < h_.n_up; ++i) {
     const PConv& up = p_.ups[i];
     const StageRoute& r = route_.stages[i];
@@ -532,6 +573,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
     if (r.ups_act_out) lrelu_out(a);  // X = lrelu(upsampled x): a batched stage's convs read it as is
     run_conv<T>(a, up, sw_.conv, s);
     L *= up.ct_u;
+    if (tapped(2 * i + 1, g.X, up.cout, r.ups_act_out)) return;
     StageTag mrf("mrf_c" + std::to_string(up.cout));  // the stage's MRF (ResBlocks + sum), models.py:119-125
     switch (r.mrf) {
       case MrfRoute::Pair:
@@ -540,6 +582,7 @@ void Vocoder::run_t(const void* mel_nlc, int B, int Tn, float* wav, Workspace& w
       case MrfRoute::F8: mrf_stage_f8<T>(i, g, B, L, s); break;
       case MrfRoute::PerResblock: mrf_stage_resblocks<T>(i, g, B, L, s); break;
     }
+    if (tapped(2 * i + 2, S, up.cout, r.mrf_act_out)) return;
   }
   StageTag tag("voc_post");
   mask_tail(S, L, CONV_POST_TAPS - 1, chan_stride(p_.post_c));

@@ -95,6 +95,8 @@ def lib():
         "m2s_vocoder_destroy": (None, [vp]),
         "m2s_vocoder_workspace_bytes": (sz, [vp, i, i]),
         "m2s_vocoder_forward": (i, [vp, fp, i, i, i, fp, vp, sz, vp]),
+        "m2s_vocoder_probe": (i, [vp, fp, i, i, i, i, fp, C.POINTER(i), C.POINTER(i), C.POINTER(i), vp, sz, vp]),
+        "m2s_vocoder_tap_info": (i, [vp, i, i, C.POINTER(i), C.POINTER(i), C.POINTER(i)]),
         "m2s_pipeline_workspace_bytes": (sz, [vp, vp, i, i, i, i]),
         "m2s_pipeline_forward": (i, [vp, vp, fp, i, i, i, i, fp, fp, fp, fp, fp, fp, vp, sz, vp]),
         # ragged batches: `lengths` is a host int array (C.POINTER(c_int)), rows = sum(lengths)
@@ -182,7 +184,8 @@ def exported_symbols() -> List[str]:
                         "m2s_mel_glue", "m2s_preprocess_frames", "m2s_preprocess_frames_resize", "m2s_preprocess_frames_masked",
                         "m2s_occlusion_reduce", "m2s_vocoder_create",
                         "m2s_vocoder_destroy",
-                        "m2s_vocoder_workspace_bytes", "m2s_vocoder_forward", "m2s_pipeline_workspace_bytes",
+                        "m2s_vocoder_workspace_bytes", "m2s_vocoder_forward", "m2s_vocoder_probe",
+                        "m2s_vocoder_tap_info", "m2s_pipeline_workspace_bytes",
                         "m2s_pipeline_forward", "m2s_acoustic_ragged_workspace_bytes", "m2s_bilstm_summerge_ragged",
                         "m2s_acoustic_forward_ragged", "m2s_vocoder_ragged_workspace_bytes",
                         "m2s_vocoder_forward_ragged", "m2s_pipeline_ragged_workspace_bytes",

@@ -35,6 +35,8 @@ METRIC_OPS = ("mel_metrics",)
 # streaming vocoder: the generator on spans of a stream, emitting only the rows that are final (packed like the ragged
 # ops; `context` / `hold` = leading / trailing rows per clip that are read but get no output)
 STREAM_OPS = ("hifigan_forward_chunk",)
+# the vocoder's stage tap (include/m2s.h m2s_vocoder_probe; VocoderEngine.probe): the tensor stored at `tap`
+PROBE_OPS = ("hifigan_features",)
 # analysis: waveform -> mel (m2s/melspec.py; handle = MelSpectrogram.handle)
 ANALYSIS_OPS = ("mel_spectrogram",)
 # frame front end: native-size uint8 frames -> resized, normalised fp32 frames (csrc/frames.hip); interp / norm are the
@@ -147,6 +149,11 @@ def _register_fakes():
     def _hifigan(handle, mel, layout, hop):
         t = mel.shape[2] if layout == 0 else mel.shape[1]
         return mel.new_empty((mel.shape[0], 1, t * hop), dtype=torch.float32)
+
+    @f("m2s::hifigan_features")
+    def _hifigan_features(handle, mel, layout, tap, channels, scale):
+        t = mel.shape[2] if layout == 0 else mel.shape[1]
+        return mel.new_empty((mel.shape[0], channels, t * scale), dtype=torch.float32)
 
     @f("m2s::pipeline_forward")
     def _pipeline(acoustic, vocoder, frames, mean, std, n_mels, hop):

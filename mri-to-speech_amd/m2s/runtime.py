@@ -247,6 +247,28 @@ class VocoderEngine:
             raise N.M2SError(f"mel has {C_} bins, generator expects {self.h['num_mels']}")
         return self.ops.hifigan_forward(self.handle, x, int(layout), self.hop)
 
+    def tap_shape(self, tap: int):
+        """(channels, rows per mel frame) of ``probe``'s tap: 0 = conv_pre's output, 2i + 1 = stage i's upsampler
+        output, 2i + 2 = stage i's MRF output."""
+        if not 0 <= tap <= 2 * len(self.h["upsample_rates"]):
+            raise N.M2SError(f"tap {tap} outside 0 .. {2 * len(self.h['upsample_rates'])}")
+        c, scale = int(self.h["upsample_initial_channel"]), 1
+        for u in self.h["upsample_rates"][: (tap + 1) // 2]:
+            c, scale = c // 2, scale * int(u)
+        return c, scale
+
+    def probe(self, mel: torch.Tensor, tap: int, layout: int = 0):
+        """The tensor the dense call stores at ``tap`` (see ``tap_shape``), exactly as stored: (B, C, L) fp32 (every
+        value a bf16 value in a bf16 / fp8 engine), and whether the engine holds it as LeakyReLU(x) (slope 0.1; the
+        split engine's batched stages), in which case it is returned as held."""
+        x = _as_f32(mel, self.device)
+        if x.dim() != 3:
+            raise N.M2SError(f"expected a 3-D mel, got {tuple(x.shape)}")
+        c, scale = self.tap_shape(int(tap))
+        act = C.c_int(0)
+        N.check(N.lib().m2s_vocoder_tap_info(self._h, int(tap), 1, None, None, C.byref(act)))
+        return self.ops.hifigan_features(self.handle, x, int(layout), int(tap), c, scale), bool(act.value)
+
     def forward_ragged(self, mel, lengths=None) -> torch.Tensor:
         """Mels of different lengths in one call: packed (N,num_mels) ln-mel (time-major rows), or a list of
         per-clip (T_b,num_mels) tensors -> packed waveform (N*hop,); ``split_packed(wav, lengths, hop)``."""

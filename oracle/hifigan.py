@@ -60,20 +60,29 @@ def resblock2(sd, p, x, k, dil):
     return x
 
 
-def generator(sd: Dict[str, torch.Tensor], h, mel: torch.Tensor) -> torch.Tensor:
-    """mel (B, num_mels, T) fp32 -> wav (B, 1, T * prod(upsample_rates))."""
+def generator(sd: Dict[str, torch.Tensor], h, mel: torch.Tensor, taps: list | None = None) -> torch.Tensor:
+    """mel (B, num_mels, T) fp32 -> wav (B, 1, T * prod(upsample_rates)).
+
+    ``taps``, if given, receives conv_pre's output (tap 0) and, per upsampling stage i, the transposed conv's output
+    (tap 2i + 1) and the MRF's output xs / num_kernels (tap 2i + 2): 1 + 2 n_up tensors, none of them activated."""
     x = F.pad(mel, (0, 6), "constant")
     x = F.conv1d(x, fold_weight(sd, "conv_pre"), sd["conv_pre.bias"])
+    if taps is not None:
+        taps.append(x)
     nk = len(h["resblock_kernel_sizes"])
     rb = resblock1 if h["resblock"] == "1" else resblock2
     for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
         x = F.leaky_relu(x, LRELU_SLOPE)
         x = F.conv_transpose1d(x, fold_weight(sd, f"ups.{i}"), sd[f"ups.{i}.bias"], u, (k - u) // 2)
+        if taps is not None:
+            taps.append(x)
         xs = None
         for j, (rk, rd) in enumerate(zip(h["resblock_kernel_sizes"], h["resblock_dilation_sizes"])):
             y = rb(sd, f"resblocks.{i * nk + j}", x, rk, rd)
             xs = y if xs is None else xs + y
         x = xs / nk
+        if taps is not None:
+            taps.append(x)
     x = F.leaky_relu(x)
     x = F.pad(x, (0, 6), "constant")
     x = F.conv1d(x, fold_weight(sd, "conv_post"), sd["conv_post.bias"])

@@ -325,6 +325,90 @@ def test_vocoder_forward(shared, gen_sd, dtype, rb, B, T, layout):
         _close(what, rep.outs["nan"]["wav"], ref, 1e-4)
 
 
+# ------------------------------------------------------------------------------------------ m2s_vocoder_probe
+@pytest.mark.parametrize("tap", [0, 3, 8])
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_vocoder_probe(shared, gen_sd, dtype, tap):
+    """The dense (B, L, C) tap at its exact size on the forward call's workspace (the probe lays out the same buffers,
+    so 256 bytes less is refused): conv_pre's output, stage 1's upsampler output and the last MRF output.  bf16 / fp8:
+    every value is a bf16 value; fp32 / bf16x3: the oracle's tap at 1e-4 of its scale (LeakyReLU applied to the
+    oracle's where the engine reports that it holds the tensor so)."""
+    B, T = 3, 17
+    key, voc = _vocoder(shared, gen_sd, dtype)
+    h = VOC_H["r1"]
+    mel = synth.synth_mel_log(B, h["num_mels"], T, seed=B * 100 + T)
+    Cc, scale = voc.tap_shape(tap)
+    L = _lib()
+    nws = L.m2s_vocoder_workspace_bytes(voc._h, B, T)
+    arena = H.Arena(DEV, [("mel", "in", mel), ("tap", "out", (B, T * scale, Cc)), ("ws", "ws", nws)])
+    dims = [C.c_int(-1) for _ in range(3)]
+
+    def call(a, n):
+        return L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, T, tap, a.ptr("tap"), C.byref(dims[0]), C.byref(dims[1]),
+                                   C.byref(dims[2]), a.ptr("ws"), n, _stream())
+
+    what = f"vocoder_probe {dtype} tap {tap} {B}x{T}"
+    rep = _run(shared, key, what, arena, call, tol={"tap": 1e-4} if dtype in EXACT else None)
+    assert [d.value for d in dims[:2]] == [T * scale, Cc] and dims[2].value in (0, 1)
+    info = [C.c_int(-1) for _ in range(3)]
+    assert L.m2s_vocoder_tap_info(voc._h, tap, T, C.byref(info[0]), C.byref(info[1]), C.byref(info[2])) == H.M2S_OK
+    assert [d.value for d in info] == [d.value for d in dims]
+    assert dims[2].value == 0 or dtype == "bf16x3"  # only the split engine's batched stages hand lrelu(x) on
+    got = rep.outs["nan"]["tap"].permute(0, 2, 1).cpu()
+    if dtype not in EXACT:
+        assert torch.equal(got, got.bfloat16().float()), f"{what}: not bf16 values"
+        return
+
+    def taps():
+        out = []
+        hifigan.generator(_t(gen_sd["r1"]), h, torch.from_numpy(mel), taps=out)
+        return [x.numpy() for x in out]
+
+    ref = _ref(shared, ("voc_taps", B, T), taps)[tap]
+    if dims[2].value:
+        ref = np.where(ref > 0, ref, ref * np.float32(0.1))
+    print(f"{what}: rel err vs oracle {_rel(got.numpy(), ref):.3e}")
+    assert got.shape == ref.shape and _rel(got.numpy(), ref) <= 1e-4, _rel(got.numpy(), ref)
+
+
+@pytest.mark.parametrize("dtype", DTYPES)
+def test_vocoder_probe_refusals(shared, gen_sd, dtype):
+    """Argument errors are M2S_E_ARG before any launch: the output and the workspace keep their fill."""
+    B, T = 1, 2
+    key, voc = _vocoder(shared, gen_sd, dtype)
+    h = VOC_H["r1"]
+    mel = synth.synth_mel_log(B, h["num_mels"], T, seed=5)
+    L = _lib()
+    nws = L.m2s_vocoder_workspace_bytes(voc._h, B, T)
+    arena = H.Arena(DEV, [("mel", "in", mel), ("tap", "out", (B, T, h["upsample_initial_channel"])), ("ws", "ws", nws)])
+    n_up = len(h["upsample_rates"])
+    calls = {
+        "tap -1": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, T, -1, a.ptr("tap"), None, None, None,
+                                                a.ptr("ws"), nws, _stream()),
+        "tap past the last": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, T, 2 * n_up + 1, a.ptr("tap"), None,
+                                                           None, None, a.ptr("ws"), nws, _stream()),
+        "null out": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, T, 0, None, None, None, None, a.ptr("ws"),
+                                                  nws, _stream()),
+        "null mel": lambda a: L.m2s_vocoder_probe(voc._h, None, 0, B, T, 0, a.ptr("tap"), None, None, None, a.ptr("ws"),
+                                                  nws, _stream()),
+        "null ws": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, T, 0, a.ptr("tap"), None, None, None, None,
+                                                 nws, _stream()),
+        "layout 2": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 2, B, T, 0, a.ptr("tap"), None, None, None,
+                                                  a.ptr("ws"), nws, _stream()),
+        "T = 0": lambda a: L.m2s_vocoder_probe(voc._h, a.ptr("mel"), 0, B, 0, 0, a.ptr("tap"), None, None, None,
+                                               a.ptr("ws"), nws, _stream()),
+    }
+    for name, call in calls.items():
+        arena.prepare("nan")
+        _sync()
+        assert call(arena) == H.M2S_E_ARG, name
+        _sync()
+        bad = arena.violations(outputs_written=False)
+        assert not bad, f"vocoder_probe {dtype} {name}: " + "; ".join(bad)
+        assert bool((arena.workspace_image() == H.POISON).all()), f"{name}: the workspace was written"
+        assert bool((arena.raw("tap") == H.POISON).all()), f"{name}: the output was written"
+
+
 # ------------------------------------------------------------------------------------------ m2s_pipeline_forward
 def _scaler_specs():
     mean, std = synth.synth_scaler()

@@ -32,6 +32,15 @@ def test_fake_shapes(m2s_ops):
     assert m2s_ops.preprocess_frames(torch.empty(3, 64, 48, 3, dtype=torch.uint8, device="meta")).shape == (3, 64, 48)
 
 
+def test_vocoder_tap_op(m2s_ops):
+    """hifigan_features: registered, and its fake kernel gives (B, channels, T * scale) in both mel layouts."""
+    assert ops.PROBE_OPS == ("hifigan_features",) and hasattr(m2s_ops, "hifigan_features")
+    assert not set(ops.PROBE_OPS) & (set(ops.OPS) | set(ops.RAGGED_OPS) | set(ops.STREAM_OPS))
+    meta = lambda *s: torch.empty(*s, device="meta")  # noqa: E731
+    assert m2s_ops.hifigan_features(2, meta(3, 64, 17), 0, 3, 128, 70).shape == (3, 128, 1190)
+    assert m2s_ops.hifigan_features(2, meta(3, 17, 64), 1, 0, 512, 1).shape == (3, 512, 17)
+
+
 @pytest.mark.parametrize("hw,n,shape", [((256, 256), 0, (32, 128, 128)), ((256, 256), 2, (16, 128, 128)),
                                         ((256, 256), 5, (32, 64, 64)), ((256, 256), 8, (56, 32, 32)),
                                         ((256, 256), 18, (120, 16, 16)), ((256, 256), 28, (208, 8, 8)),
