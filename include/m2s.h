@@ -588,6 +588,70 @@ size_t m2s_melspec_workspace_bytes(const m2s_melspec* m, int B, int L);
 int m2s_melspec_forward(m2s_melspec* m, const float* wav, int B, int L, float* mel, int layout, void* ws,
                         size_t ws_bytes, void* stream);
 
+/* ---------------------------------------------- fine-tuning: BiLSTM and mel head ---- */
+/* One optimisation step of OTNLikeTrainer.train_epoch (train_mri_acoustic_model.py) for one batch and one
+ * micro-batch, restricted to rnn.lstm.* and head.* with cnn.* frozen in eval mode (DESIGN.md "Fine-tuning"): the
+ * caller passes cached encoder features.  fp32 throughout (no autocast, no GradScaler), rnn_hidden = 640.
+ * Inputs are packed as in the pair calls: feats (rows,208) of B clips, lengths[B] on the HOST, target (rows,n_mels)
+ * standardised dB mels and mask (rows) floats (NULL = ones) PER FRAME ROW; pair p, row s is window i, frame i + s
+ * of its clip, P = sum(lengths[b] - window + 1) pairs in pass3_save_pairs order.  The calls gather targets and masks.
+ * Forward: nn.LSTM(208, 640, bidirectional) from zero state on every window, sum merge, Dropout(p) with scale
+ * 1 / (1 - p), Linear(640, n_mels).  Criterion: LOSS of m2s_mel_metrics on (P,window,n_mels) as ONE group, with the
+ * freq_w / time_w / coefficients of the last m2s_finetune_set_hyper.  Backward: exact gradients of the 10 tensors,
+ * in this order everywhere below: weight_ih_l0, weight_hh_l0, bias_ih_l0, bias_hh_l0, the same four with the
+ * _reverse suffix, head.weight, head.bias (bias_ih and bias_hh get equal gradients and separate moments).
+ * clip_grad_norm_: coef = min(1, max_norm / (norm + 1e-6)) over the 10 tensors, skipped when max_norm <= 0.
+ * torch.optim.AdamW(lr, (0.9, 0.999), 1e-8, weight_decay) on all 10: p *= 1 - lr wd, moments, bias-corrected
+ * update, step count from 1.
+ * Dropout mask: element e of (P,window,640) at optimiser step t (the step this update is, counted from 1) is kept
+ * iff mix(e, seed, t) >= floor(p 2^32), mix = the 32-bit integer hash of DESIGN.md "Fine-tuning"; the backward
+ * regenerates it.  p = 0 keeps every element and multiplies nothing.
+ * A step reads nothing back to the host.  Every reduction has a fixed partition and order and there are no
+ * floating-point atomics, waits or flags: equal inputs and state give equal bits.
+ * Capture: the window table of (lengths, window) is staged by the first call that sees them; after one eager
+ * m2s_finetune_step / m2s_finetune_forward, calls with the same lengths and window can be captured (one linear
+ * chain of launches) and a replay advances the device step count and the dropout stream as an eager step does.  A
+ * staged table keeps its device address until m2s_finetune_destroy, so eager calls with other lengths between two
+ * replays (each staging a table of its own, P + 3 rows ints) leave a captured step valid.  A capturing call with a
+ * table that is not staged returns M2S_E_STATE, and so does m2s_finetune_set_hyper on a capturing stream.
+ * M2S_E_ARG, before any launch: a null handle, feats, target, lengths or ws; the pair calls' argument errors (window
+ * outside 1..16, a lengths[b] < window, B < 1, sum(lengths) != rows); a window other than the last set_hyper's (or
+ * no set_hyper yet); an undersized workspace.  The workspace contract above applies as written. */
+typedef struct m2s_finetune m2s_finetune;
+typedef struct m2s_finetune_hyper {
+  float lr, weight_decay, max_norm, dropout; /* dropout in [0, 1) */
+  unsigned seed;
+  float delta_coeff, accel_coeff, latest_coeff;
+} m2s_finetune_hyper;
+enum { M2S_FT_TENSORS = 10, M2S_FT_SLOTS = 8 };
+/* Takes rnn.lstm.* and head.* from a full or partial state dict (a missing one: M2S_E_ARG naming it); 1 <= n_mels
+ * <= 256.  Moments and step count start at zero.  Synchronous. */
+int m2s_finetune_create(const m2s_tensor* sd, int n, int n_mels, int device, m2s_finetune** out);
+void m2s_finetune_destroy(m2s_finetune* ft);
+int m2s_finetune_n_mels(const m2s_finetune* ft);
+/* Host values -> the device hyper-parameter block, stream-ordered: freq_w[n_mels], time_w[window] host arrays. */
+int m2s_finetune_set_hyper(m2s_finetune* ft, const m2s_finetune_hyper* h, const float* freq_w, const float* time_w,
+                           int window, void* stream);
+/* Exact size for m2s_finetune_step AND for m2s_finetune_forward: the forward call takes the step's layout, so either
+ * call refuses a workspace 256 bytes smaller.  0 for arguments the calls reject. */
+size_t m2s_finetune_workspace_bytes(const m2s_finetune* ft, const int* lengths, int B, int window);
+/* out_slots (device, M2S_FT_SLOTS floats, may be NULL): LOSS, MSE, MAE, DELTA, ACCEL, LATEST of the batch BEFORE the
+ * update (train-mode predictions), the gradient norm before clipping, coef. */
+int m2s_finetune_step(m2s_finetune* ft, const float* feats, const float* target, const float* mask, const int* lengths,
+                      int B, int rows, int window, float* out_slots, void* ws, size_t ws_bytes, void* stream);
+/* Predictions mel_norm (P,window,n_mels) with dropout on (train != 0: the mask of the next step) or off; no update. */
+int m2s_finetune_forward(m2s_finetune* ft, const float* feats, const int* lengths, int B, int rows, int window,
+                         int train, float* mel_norm, void* ws, size_t ws_bytes, void* stream);
+/* The last step's gradients before clipping -> grads10[i] (device, the tensor's shape; an entry may be NULL). */
+int m2s_finetune_grads(m2s_finetune* ft, float* const* grads10, void* stream);
+/* Parameters, first and second moments (device arrays of the tensors' shapes) and the step count (device int64);
+ * any pointer, and any entry of an array, may be NULL. */
+int m2s_finetune_export(m2s_finetune* ft, float* const* params10, float* const* m10, float* const* v10, int64_t* step,
+                        void* stream);
+/* The inverse of the export's m, v and step (device pointers), for resuming; m10 and v10 non-NULL with 10 entries. */
+int m2s_finetune_import_moments(m2s_finetune* ft, const float* const* m10, const float* const* v10,
+                                const int64_t* step, void* stream);
+
 /* -------------------------------------------------------------------- profiling ---- */
 /* While enabled, every kernel launch is bracketed by HIP events on its own stream. */
 typedef struct m2s_prof_stat {

@@ -5,6 +5,7 @@
 
 #include "../../include/m2s.h"
 #include "cam.hpp"
+#include "finetune.hpp"
 #include "melspec.hpp"
 #include "model.hpp"
 
@@ -20,6 +21,10 @@ struct m2s_cam {
 struct m2s_gradcam {
   m2s::GradCam impl;
   m2s_gradcam(const m2s::StateDict& sd, int device) : impl(sd, device) {}
+};
+struct m2s_finetune {
+  m2s::FineTune impl;
+  m2s_finetune(const m2s_tensor* sd, int n, int n_mels, int device) : impl(sd, n, n_mels, device) {}
 };
 struct m2s_melspec {
   m2s::MelSpec impl;
@@ -701,6 +706,82 @@ int m2s_melspec_forward(m2s_melspec* m, const float* wav, int B, int L, float* m
     M2S_CHECK(m && wav && mel && ws, "null argument");
     DeviceGuard g(m->impl.device());
     m->impl.forward(wav, B, L, mel, layout, ws, ws_bytes, S(stream));
+  });
+}
+
+int m2s_finetune_create(const m2s_tensor* sd, int n, int n_mels, int device, m2s_finetune** out) {
+  return guarded([&] {
+    M2S_CHECK(out && (sd || n == 0), "null argument");
+    check_device(device);
+    DeviceGuard g(device);
+    *out = new m2s_finetune(sd, n, n_mels, device);
+  });
+}
+
+void m2s_finetune_destroy(m2s_finetune* ft) {
+  if (!ft) return;
+  guarded([&] {
+    DeviceGuard g(ft->impl.device());
+    delete ft;
+  });
+}
+
+int m2s_finetune_n_mels(const m2s_finetune* ft) { return ft ? ft->impl.n_mels() : 0; }
+
+int m2s_finetune_set_hyper(m2s_finetune* ft, const m2s_finetune_hyper* h, const float* freq_w, const float* time_w,
+                           int window, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft && h, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.set_hyper(*h, freq_w, time_w, window, S(stream));
+  });
+}
+
+size_t m2s_finetune_workspace_bytes(const m2s_finetune* ft, const int* lengths, int B, int window) {
+  return size_query(ft, [&] { return ft->impl.workspace_bytes(lengths, B, window); });
+}
+
+int m2s_finetune_step(m2s_finetune* ft, const float* feats, const float* target, const float* mask, const int* lengths,
+                      int B, int rows, int window, float* out_slots, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft && feats && target && lengths && ws, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.step(feats, target, mask, lengths, B, rows, window, out_slots, ws, ws_bytes, S(stream));
+  });
+}
+
+int m2s_finetune_forward(m2s_finetune* ft, const float* feats, const int* lengths, int B, int rows, int window,
+                         int train, float* mel_norm, void* ws, size_t ws_bytes, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft && feats && lengths && mel_norm && ws, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.forward(feats, lengths, B, rows, window, train != 0, mel_norm, ws, ws_bytes, S(stream));
+  });
+}
+
+int m2s_finetune_grads(m2s_finetune* ft, float* const* grads10, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.grads(grads10, S(stream));
+  });
+}
+
+int m2s_finetune_export(m2s_finetune* ft, float* const* params10, float* const* m10, float* const* v10, int64_t* step,
+                        void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.export_state(params10, m10, v10, step, S(stream));
+  });
+}
+
+int m2s_finetune_import_moments(m2s_finetune* ft, const float* const* m10, const float* const* v10,
+                                const int64_t* step, void* stream) {
+  return guarded([&] {
+    M2S_CHECK(ft, "null argument");
+    DeviceGuard g(ft->impl.device());
+    ft->impl.import_moments(m10, v10, step, S(stream));
   });
 }
 

@@ -787,6 +787,114 @@ at::Tensor mel_spectrogram(int64_t h, const at::Tensor& wav, int64_t layout) {
   return out;
 }
 
+// ---- fine-tuning engine (m2s/finetune.py; handle = HeadTuner.handle) ---------------------------------------------
+m2s_finetune* Ft(int64_t h) {
+  TORCH_CHECK(h != 0, "null finetune handle");
+  return reinterpret_cast<m2s_finetune*>(h);
+}
+
+const int64_t kFtRows[M2S_FT_TENSORS] = {2560, 2560, 2560, 2560, 2560, 2560, 2560, 2560, 0, 0};
+const int64_t kFtCols[M2S_FT_TENSORS] = {208, 640, 0, 0, 208, 640, 0, 0, 640, 0};
+std::vector<at::Tensor> ft_tensors(int64_t h, const at::TensorOptions& opt) {
+  const int64_t nm = m2s_finetune_n_mels(Ft(h));
+  std::vector<at::Tensor> out;
+  for (int i = 0; i < M2S_FT_TENSORS; ++i) {
+    const int64_t r = kFtRows[i] ? kFtRows[i] : nm;
+    out.push_back(kFtCols[i] ? at::empty({r, kFtCols[i]}, opt) : at::empty({r}, opt));
+  }
+  return out;
+}
+std::vector<float*> ft_ptrs(std::vector<at::Tensor>& v) {
+  std::vector<float*> p;
+  for (auto& t : v) p.push_back(t.data_ptr<float>());
+  return p;
+}
+
+// feats (rows,208), target (rows,n_mels), mask (rows) or None -> the step's 8 slots (device); no host sync
+at::Tensor finetune_step(int64_t h, const at::Tensor& feats, const at::Tensor& target,
+                         const c10::optional<at::Tensor>& mask, at::IntArrayRef lengths, int64_t window) {
+  TORCH_CHECK(feats.dim() == 2 && feats.size(1) == 208, "finetune_step: feats must be (rows,208)");
+  const Guard g(feats.device());
+  const at::Tensor x = f32_on_device(feats, "feats"), t = f32_on_device(target, "target");
+  const int nm = m2s_finetune_n_mels(Ft(h));
+  TORCH_CHECK(t.dim() == 2 && t.size(0) == x.size(0) && t.size(1) == nm, "finetune_step: target must be (rows,n_mels)");
+  at::Tensor mk;
+  if (mask.has_value() && mask->defined()) {
+    mk = f32_on_device(*mask, "mask");
+    TORCH_CHECK(mk.dim() == 1 && mk.size(0) == x.size(0), "finetune_step: mask must be (rows)");
+  }
+  const std::vector<int> len = host_lengths(lengths, "finetune_step lengths");
+  const size_t wsb = m2s_finetune_workspace_bytes(Ft(h), len.data(), (int)len.size(), (int)window);
+  TORCH_CHECK(wsb > 0, "libm2s finetune_step: ", m2s_last_error());
+  at::Tensor ws = workspace(wsb, x);
+  at::Tensor slots = at::empty({(int64_t)M2S_FT_SLOTS}, x.options());
+  ok(m2s_finetune_step(Ft(h), x.data_ptr<float>(), t.data_ptr<float>(), mk.defined() ? mk.data_ptr<float>() : nullptr,
+                       len.data(), (int)len.size(), (int)x.size(0), (int)window, slots.data_ptr<float>(), ws.data_ptr(),
+                       ws.numel(), S()),
+     "finetune_step");
+  return slots;
+}
+
+// feats (rows,208) -> predictions (P,window,n_mels), dropout on (train) or off; no update
+at::Tensor finetune_forward(int64_t h, const at::Tensor& feats, at::IntArrayRef lengths, int64_t window, bool train) {
+  TORCH_CHECK(feats.dim() == 2 && feats.size(1) == 208, "finetune_forward: feats must be (rows,208)");
+  const Guard g(feats.device());
+  const at::Tensor x = f32_on_device(feats, "feats");
+  const std::vector<int> len = host_lengths(lengths, "finetune_forward lengths");
+  const size_t wsb = m2s_finetune_workspace_bytes(Ft(h), len.data(), (int)len.size(), (int)window);
+  TORCH_CHECK(wsb > 0, "libm2s finetune_forward: ", m2s_last_error());
+  int64_t P = 0;
+  for (int v : len) P += v - window + 1;
+  at::Tensor ws = workspace(wsb, x);
+  at::Tensor out = at::empty({P, window, (int64_t)m2s_finetune_n_mels(Ft(h))}, x.options());
+  ok(m2s_finetune_forward(Ft(h), x.data_ptr<float>(), len.data(), (int)len.size(), (int)x.size(0), (int)window,
+                          train ? 1 : 0, out.data_ptr<float>(), ws.data_ptr(), ws.numel(), S()),
+     "finetune_forward");
+  return out;
+}
+
+// the last step's gradients before clipping, in the order of m2s.h; `like` names the device
+std::vector<at::Tensor> finetune_grads(int64_t h, const at::Tensor& like) {
+  TORCH_CHECK(like.is_cuda(), "finetune_grads: `like` must be a HIP (cuda) tensor");
+  const Guard g(like.device());
+  std::vector<at::Tensor> out = ft_tensors(h, like.options().dtype(at::kFloat));
+  const std::vector<float*> p = ft_ptrs(out);
+  ok(m2s_finetune_grads(Ft(h), p.data(), S()), "finetune_grads");
+  return out;
+}
+
+// (params[10], m[10], v[10], step (1,) int64 on the device)
+std::tuple<std::vector<at::Tensor>, std::vector<at::Tensor>, std::vector<at::Tensor>, at::Tensor> finetune_export(
+    int64_t h, const at::Tensor& like) {
+  TORCH_CHECK(like.is_cuda(), "finetune_export: `like` must be a HIP (cuda) tensor");
+  const Guard g(like.device());
+  const at::TensorOptions opt = like.options().dtype(at::kFloat);
+  std::vector<at::Tensor> pp = ft_tensors(h, opt), mm = ft_tensors(h, opt), vv = ft_tensors(h, opt);
+  at::Tensor step = at::empty({1}, like.options().dtype(at::kLong));
+  const std::vector<float*> a = ft_ptrs(pp), b = ft_ptrs(mm), c = ft_ptrs(vv);
+  ok(m2s_finetune_export(Ft(h), a.data(), b.data(), c.data(), step.data_ptr<int64_t>(), S()), "finetune_export");
+  return {pp, mm, vv, step};
+}
+
+// the inverse of finetune_export's m, v and step
+void finetune_import(int64_t h, at::TensorList m, at::TensorList v, const at::Tensor& step) {
+  TORCH_CHECK(m.size() == M2S_FT_TENSORS && v.size() == M2S_FT_TENSORS, "finetune_import: 10 tensors each");
+  TORCH_CHECK(step.is_cuda() && step.scalar_type() == at::kLong && step.numel() == 1 && step.is_contiguous(),
+              "finetune_import: step must be a device int64 tensor of one element");
+  const Guard g(step.device());
+  std::vector<at::Tensor> ref = ft_tensors(h, step.options().dtype(at::kFloat)), keep;
+  std::vector<const float*> mp, vp;
+  for (int i = 0; i < M2S_FT_TENSORS; ++i) {
+    TORCH_CHECK(m[i].numel() == ref[i].numel() && v[i].numel() == ref[i].numel(), "finetune_import: tensor ", i,
+                " has the wrong size");
+    keep.push_back(f32_on_device(m[i], "m"));
+    mp.push_back(keep.back().data_ptr<float>());
+    keep.push_back(f32_on_device(v[i], "v"));
+    vp.push_back(keep.back().data_ptr<float>());
+  }
+  ok(m2s_finetune_import_moments(Ft(h), mp.data(), vp.data(), step.data_ptr<int64_t>(), S()), "finetune_import");
+}
+
 }  // namespace
 
 TORCH_LIBRARY(m2s, m) {
@@ -833,6 +941,11 @@ TORCH_LIBRARY(m2s, m) {
   m.def("linear_backward(Tensor dy, Tensor x, Tensor weight) -> (Tensor, Tensor, Tensor)");
   m.def("gap_forward(Tensor x) -> Tensor");
   m.def("gap_backward(Tensor dy, int h, int w) -> Tensor");
+  m.def("finetune_step(int handle, Tensor feats, Tensor target, Tensor? mask, int[] lengths, int window) -> Tensor");
+  m.def("finetune_forward(int handle, Tensor feats, int[] lengths, int window, bool train) -> Tensor");
+  m.def("finetune_grads(int handle, Tensor like) -> Tensor[]");
+  m.def("finetune_export(int handle, Tensor like) -> (Tensor[], Tensor[], Tensor[], Tensor)");
+  m.def("finetune_import(int handle, Tensor[] m, Tensor[] v, Tensor step) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
@@ -870,4 +983,9 @@ TORCH_LIBRARY_IMPL(m2s, CUDA, m) {  // CUDA = the HIP device key of PyTorch-ROCm
   m.impl("gap_forward", &gap_forward);
   m.impl("gap_backward", &gap_backward);
   m.impl("mel_spectrogram", &mel_spectrogram);
+  m.impl("finetune_step", &finetune_step);
+  m.impl("finetune_forward", &finetune_forward);
+  m.impl("finetune_grads", &finetune_grads);
+  m.impl("finetune_export", &finetune_export);
+  m.impl("finetune_import", &finetune_import);
 }

@@ -47,6 +47,11 @@ class MelspecCfg(C.Structure):
                 ("power", C.c_int), ("out", C.c_int), ("preemph", C.c_float)]
 
 
+class FinetuneHyper(C.Structure):
+    _fields_ = [("lr", C.c_float), ("weight_decay", C.c_float), ("max_norm", C.c_float), ("dropout", C.c_float),
+                ("seed", C.c_uint), ("delta_coeff", C.c_float), ("accel_coeff", C.c_float), ("latest_coeff", C.c_float)]
+
+
 class ProfStat(C.Structure):
     _fields_ = [("name", C.c_char * 96), ("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double),
                 ("bytes", C.c_double)]
@@ -156,6 +161,18 @@ def lib():
         "m2s_melspec_frames": (i, [vp, i]),
         "m2s_melspec_workspace_bytes": (sz, [vp, i, i]),
         "m2s_melspec_forward": (i, [vp, fp, i, i, fp, i, vp, sz, vp]),
+        # fine-tuning engine: `lengths`, the hyper struct, freq_w and time_w are host memory; grads10 / params10 / m10 /
+        # v10 are host arrays of 10 device pointers
+        "m2s_finetune_create": (i, [C.POINTER(Tensor), i, i, i, C.POINTER(vp)]),
+        "m2s_finetune_destroy": (None, [vp]),
+        "m2s_finetune_n_mels": (i, [vp]),
+        "m2s_finetune_set_hyper": (i, [vp, C.POINTER(FinetuneHyper), C.POINTER(C.c_float), C.POINTER(C.c_float), i, vp]),
+        "m2s_finetune_workspace_bytes": (sz, [vp, C.POINTER(i), i, i]),
+        "m2s_finetune_step": (i, [vp, fp, fp, fp, C.POINTER(i), i, i, i, fp, vp, sz, vp]),
+        "m2s_finetune_forward": (i, [vp, fp, C.POINTER(i), i, i, i, i, fp, vp, sz, vp]),
+        "m2s_finetune_grads": (i, [vp, C.POINTER(vp), vp]),
+        "m2s_finetune_export": (i, [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]),
+        "m2s_finetune_import_moments": (i, [vp, C.POINTER(vp), C.POINTER(vp), vp, vp]),
         "m2s_prof_enable": (i, [i]),
         "m2s_prof_collect": (i, [C.POINTER(ProfStat), i, C.POINTER(i)]),
         "m2s_prof_launches": (i, [C.POINTER(ProfLaunch), i, C.POINTER(i)]),
@@ -205,6 +222,9 @@ def exported_symbols() -> List[str]:
                         "m2s_linear_forward", "m2s_linear_backward", "m2s_gap_forward", "m2s_gap_backward",
                         "m2s_melspec_create", "m2s_melspec_destroy", "m2s_melspec_n_mels", "m2s_melspec_frames",
                         "m2s_melspec_workspace_bytes", "m2s_melspec_forward",
+                        "m2s_finetune_create", "m2s_finetune_destroy", "m2s_finetune_n_mels", "m2s_finetune_set_hyper",
+                        "m2s_finetune_workspace_bytes", "m2s_finetune_step", "m2s_finetune_forward", "m2s_finetune_grads",
+                        "m2s_finetune_export", "m2s_finetune_import_moments",
                         "m2s_prof_enable", "m2s_prof_collect", "m2s_prof_launches")]
 
 

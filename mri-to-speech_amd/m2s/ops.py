@@ -50,6 +50,13 @@ OCCLUSION_OPS = ("preprocess_frames_masked", "occlusion_reduce")
 # Grad-CAM engine (m2s/gradcam.py; handle = GradCam.handle): every band and target frame of a clip in one call, and
 # its stages (include/m2s.h "Grad-CAM engine")
 GRADCAM_OPS = ("gradcam", "gradcam_cotangents", "bilstm_train_backward_multi", "cam_heatmap")
+# fine-tuning engine (m2s/finetune.py; handle = HeadTuner.handle): one optimisation step of the BiLSTM and mel head on
+# cached encoder features, its forward alone, the last gradients, and the state out of / into the engine
+FINETUNE_OPS = ("finetune_step", "finetune_forward", "finetune_grads", "finetune_export", "finetune_import")
+FINETUNE_SLOTS = ("loss", "mse", "mae", "delta", "accel", "latest", "grad_norm", "clip_coef")
+# the engine's 10 tensors in its order (include/m2s.h "fine-tuning"), under the reference's key names
+FINETUNE_KEYS = tuple(f"rnn.lstm.{n}_l0{sfx}" for sfx in ("", "_reverse")
+                      for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh")) + ("head.weight", "head.bias")
 
 # timm tf_efficientnetv2_b2 (features_only): stride and output channels of the stem (index 0) and of
 # the 29 blocks that follow (effnet_features' n_blocks = how many of them ran)
@@ -95,6 +102,17 @@ def melspec_geometry(handle: int):
         return _MELSPEC_GEOMETRY[int(handle)]
     except KeyError:
         raise M2SError(f"mel_spectrogram: handle {handle:#x} was not created by m2s.melspec.MelSpectrogram") from None
+
+
+# m2s_finetune* handle -> n_mels, for finetune_forward's fake kernel; HeadTuner registers itself here
+_FINETUNE_MELS = {}
+
+
+def target_mels(handle: int) -> int:
+    try:
+        return _FINETUNE_MELS[int(handle)]
+    except KeyError:
+        raise M2SError(f"finetune: handle {handle:#x} was not created by m2s.finetune.HeadTuner") from None
 
 
 def load():
@@ -280,6 +298,32 @@ def _register_fakes():
     @f("m2s::linear_backward")
     def _lin_bwd(dy, x, weight):
         return torch.empty_like(x), torch.empty_like(weight), weight.new_empty((weight.shape[0],))
+
+    @f("m2s::finetune_step")
+    def _ft_step(handle, feats, target, mask, lengths, window):
+        return feats.new_empty((len(FINETUNE_SLOTS),), dtype=torch.float32)
+
+    @f("m2s::finetune_forward")
+    def _ft_forward(handle, feats, lengths, window, train):
+        return feats.new_empty((_pairs(lengths, window), window, target_mels(handle)), dtype=torch.float32)
+
+    def _ft_list(handle, like):
+        nm = target_mels(handle)
+        shapes = [(2560, 208), (2560, 640), (2560,), (2560,)] * 2 + [(nm, 640), (nm,)]
+        return [like.new_empty(s, dtype=torch.float32) for s in shapes]
+
+    @f("m2s::finetune_grads")
+    def _ft_grads(handle, like):
+        return _ft_list(handle, like)
+
+    @f("m2s::finetune_export")
+    def _ft_export(handle, like):
+        return (_ft_list(handle, like), _ft_list(handle, like), _ft_list(handle, like),
+                like.new_empty((1,), dtype=torch.int64))
+
+    @f("m2s::finetune_import")
+    def _ft_import(handle, m, v, step):
+        return None
 
     @f("m2s::gap_forward")
     def _gap(x):
